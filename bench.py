@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- LiDAR frames/sec, MinkUNet-34 cr1.0 training step at SemanticKITTI shape.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch: forward (hash-grid voxelise, 9 rulebook
@@ -11,14 +12,18 @@ synthetic ~120k-point scans (openpcseg_amd/workloads/synthetic.py), voxelised on
 the reference's dataset transform BEFORE the timed region and resident in HBM; rulebooks are
 rebuilt every step (no cross-iteration cache, as in the reference).
 Prints ONE JSON line (rank 0): `value` = the fp32 step (fp32 MFMA convolutions; weight gradient policy in
-`config.wgrad`) with the roofline of the dominant kernel (fused gather-GEMM conv) measured live with HIP
-events on the launch stream; `amp_bf16` = the same step under torch.autocast(bf16) (the reference trains
-under --amp); `fp32_bf16x3` = the fp32 step with the forward / input-gradient convolutions on the
-three-plane split kernel (fp32 in / out on the bf16 MFMAs, opt-in, fp32-grade); `comm` (N > 1) = RCCL time
+`config.wgrad`), `ms_per_step` = one of the K timed steps. A plain run does only that: set-up, W warm-up steps,
+K timed steps, the line. --dump-outputs DIR also writes what the last timed step returned (dump_outputs).
+--full adds the records that take runs or measurements of their own: a clock pre-heat before each record
+(preheat), the roofline of the dominant kernel (fused gather-GEMM conv) measured live with HIP events on the
+launch stream; `amp_bf16` = the same step under torch.autocast(bf16) (the reference trains under --amp);
+`fp32_bf16x3` = the fp32 step with the forward / input-gradient convolutions on the three-plane split kernel
+(fp32 in / out on the bf16 MFMAs, opt-in, fp32-grade); `device_input`; `models`; `comm` (N > 1) = RCCL time
 per step and its overlap with backward from a device trace; `cpu_baseline` = the reference's own compiled
 CPU backend on ONE full frame of the workload (N = 1 only, baseline only).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -269,6 +274,43 @@ def to_device(batch, dev):
 def fresh(b):
     """New containers over the SAME device tensors: every step rebuilds all maps."""
     return {"lidar": SparseTensor(b["lidar"].F, b["lidar"].C), "targets": SparseTensor(b["targets"].F, b["targets"].C)}
+
+
+DUMP_LOGIT_ROWS = 1 << 18       # 262 144 rows x 20 classes x 4 B = 21 MB
+DUMP_PARAM_ENTRIES = 1 << 20    # 4 MB each for the gradients and the updated weights
+
+
+def _sample(n, k):
+    """A fixed, seeded, sorted sample of k of range(n) (all of it when n <= k): the same rows in every run and build."""
+    import numpy as np
+    if n <= k:
+        return None
+    return torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, k, replace=False)))
+
+
+def dump_outputs(path, out, params):
+    """What the last timed step handed back, as float32 / float64 .npy files under `path`:
+    loss.npy (the step's loss), logits.npy (point logits; rows = _sample(rows, DUMP_LOGIT_ROWS) of a larger batch),
+    grads.npy / weights.npy (the step's gradients and the weights after its optimizer update, all parameters flattened and
+    concatenated in model.parameters() order; entries = _sample(total, DUMP_PARAM_ENTRIES)), grad_norms.npy (float64 L2 norm
+    of every parameter's gradient, same order). About 29 MB at the default batch."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    logits = out["logits"].detach()
+    rows = _sample(logits.shape[0], DUMP_LOGIT_ROWS)
+    if rows is not None:
+        logits = logits[rows.to(logits.device)]
+    grads = [p.grad.detach() if p.grad is not None else torch.zeros_like(p) for p in params]
+    flat_g = torch.cat([g.float().flatten() for g in grads])
+    flat_w = torch.cat([p.detach().float().flatten() for p in params])
+    idx = _sample(flat_g.numel(), DUMP_PARAM_ENTRIES)
+    if idx is not None:
+        idx = idx.to(flat_g.device)
+        flat_g, flat_w = flat_g[idx], flat_w[idx]
+    arrays = {"loss": out["loss"].detach().float().reshape(1), "logits": logits.float(), "grads": flat_g, "weights": flat_w,
+              "grad_norms": torch.stack([g.double().norm() for g in grads])}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
 
 
 CPU_BASELINE_THREADS = 8      # the reference's CPU code forks an OpenMP team per row: more threads = slower
@@ -569,7 +611,18 @@ def main():
                          "(round / shift / sparse_quantize / collate of all frames on the device); the default fp32 run carries the bf16 one")
     ap.add_argument("--no-device-input-line", action="store_true", help="skip the secondary `device_input` record")
     ap.add_argument("--verbose-json", action="store_true", help="print the long records (notes, clocks) instead of the compact line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary records: clock pre-heat, roofline and clocks, amp_bf16, fp32_bf16x3, device_input, models, "
+                         "comm, cpu_baseline (the --no-* / --models / --device-input options shape this run)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (loss, logits, gradients, updated weights; "
+                         "fixed seeded samples of the large ones) as DIR/<name>.npy, rank 0. With --full the clock pre-heat "
+                         "runs a varying number of steps first: set PCS_BENCH_PREHEAT=0 to compare such runs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full and (args.device_input or args.models not in ("auto", "none")):
+        ap.error("--device-input and --models select records of the --full run")
     if args.cpu_baseline_worker:
         _cpu_baseline_worker()
         return
@@ -617,8 +670,9 @@ def main():
 
     raw_dev = None
 
-    def measure(amp, conv="fp32", wgrad="fp32", device_input=False):
-        """One bench line: fresh model / optimizer (same seed), preheat, W warm-up steps, K timed steps.
+    def measure(amp, conv="fp32", wgrad="fp32", device_input=False, dump=None):
+        """One bench line: fresh model / optimizer (same seed), W warm-up steps, K timed steps; with --full a preheat first
+        and the conv meter / clock sampler over the timed steps. dump: directory for dump_outputs of the last timed step.
         device_input: every step starts from the RAW scans in HBM (dataset transform + voxel dedup + collate on the device,
         workloads/synthetic.py::device_collate) instead of the pre-voxelised batch."""
         nonlocal raw_dev
@@ -655,10 +709,10 @@ def main():
             return fresh(batch)
 
         def step():
-            loss = step_body()
+            out = step_body()
             if device_input and pipe is not None:
                 pipe.prefetch()
-            return loss
+            return out
 
         def step_body():
             opt.zero_grad(set_to_none=True)
@@ -674,14 +728,15 @@ def main():
                     torch.nn.utils.clip_grad_norm_(params, 10.0)
                     scaler.step(opt)
                     scaler.update()
-                    return out["loss"]
+                    return out
                 out["loss"].backward()
             torch.nn.utils.clip_grad_norm_(params, 10.0)
             opt.step()
-            return out["loss"]
+            return out
 
-        with ConvMeter(be) as meter:
-            preheat(step, distributed, dev)
+        with ConvMeter(be) if args.full else contextlib.nullcontext() as meter:
+            if args.full:
+                preheat(step, distributed, dev)
             for _ in range(args.warmup):
                 step()
             if distributed:
@@ -705,20 +760,26 @@ def main():
                         blocks[flag].append(time.perf_counter() - t0)
                 base_dt, dev_dt = sorted(blocks[False])[1], sorted(blocks[True])[1]
                 device_input = True
-            meter.enabled = True
-            with ClockSampler(dev_index) as clocks:
+            if meter is not None:
+                meter.enabled = True
+            with ClockSampler(dev_index) if args.full else contextlib.nullcontext() as clocks:
                 t0 = time.perf_counter()
                 for _ in range(args.steps):
-                    loss = step()
+                    out = step()
                 torch.cuda.synchronize()
                 if distributed:
                     dist.barrier()
                 dt = time.perf_counter() - t0
+            loss = out["loss"]
+            if dump is not None and rank == 0:
+                dump_outputs(dump, out, params)
             if dev_dt is not None:
                 dt = dev_dt   # the median block (this last block served the conv meter and the clock sampler)
-            meter.enabled = False
-            roof = meter.summary(amp, split=(conv == "bf16x3"))
-            clk = clocks.summary()
+            roof = None
+            if meter is not None:
+                meter.enabled = False
+                roof = meter.summary(amp, split=(conv == "bf16x3"))
+                clk = clocks.summary()
             if roof is not None:
                 roof["clock"] = clk
                 if clk.get("sclk_mhz_mean") and roof["bound"] == "mfma":
@@ -729,7 +790,7 @@ def main():
             tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
-        comm = comm_profile(step, rank) if distributed and not one_dev else None
+        comm = comm_profile(step, rank) if args.full and distributed and not one_dev else None
         pcsF.set_conv_policy("fp32")
         pcsF.set_wgrad_policy("fp32")
         frames = args.frames_per_gpu * world * args.steps
@@ -746,16 +807,16 @@ def main():
     amp = None if args.amp == "off" else args.amp
     # the reference trains under --amp (R:dist_train.sh:18): the default run carries the bf16 step as a secondary record. It is
     # measured FIRST [r5]: whatever a fresh process / box still ramps (see preheat) is not charged to the headline record
-    second = measure("bf16") if amp is None and not args.no_amp_line else None
+    second = measure("bf16") if args.full and amp is None and not args.no_amp_line else None
     # headline: fp32 storage and fp32 MFMA arithmetic throughout (convolutions, weight gradient) unless --wgrad says otherwise
-    head = measure(amp, wgrad=args.wgrad if amp is None else "fp32")
+    head = measure(amp, wgrad=args.wgrad if amp is None else "fp32", dump=args.dump_outputs)
     # third record: the fp32 step with BOTH fp32-grade split policies (forward / input-gradient convolutions and the weight gradient
     # of the wide layers with fp32 operands as three bf16 planes on the 16-bit MFMAs); opt-in arithmetic, never the headline value
-    third = measure(None, conv="bf16x3", wgrad="bf16x3") if amp is None and not args.no_split_line else None
+    third = measure(None, conv="bf16x3", wgrad="bf16x3") if args.full and amp is None and not args.no_split_line else None
     # SURVEY section 8 f1 with its number: the same step (bf16: the fastest step, where input work shows most) starting from the RAW
     # scans resident in HBM -- dataset transform + voxel dedup + collate of the 12 frames on the device inside every timed step
     dev_in = None
-    if args.device_input or (amp is None and world == 1 and not args.no_amp_line and not args.no_device_input_line):
+    if args.full and (args.device_input or (amp is None and world == 1 and not args.no_amp_line and not args.no_device_input_line)):
         d_amp = amp if args.device_input else "bf16"
         base = head if d_amp == amp else second
         di = measure(d_amp, device_input=True)
@@ -772,7 +833,7 @@ def main():
                   "collate_ms": round((time.perf_counter() - t0) / 20 * 1e3, 2),              # the device pass alone, 12 frames
                   "loss": di["loss"]}
     models = None
-    if world == 1 and args.models != "none" and (args.models != "auto" or amp is None):
+    if args.full and world == 1 and args.models != "none" and (args.models != "auto" or amp is None):
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         try:
             import modelbench
@@ -800,8 +861,9 @@ def main():
                                    % (args.frames_per_gpu, "fp32" if amp is None else "autocast " + amp),
                        "global_batch": args.frames_per_gpu * world, "voxels_per_gpu_batch": n_vox, "parallelism": "dp%d" % world,
                        "wgrad": "fp32" if amp is not None else args.wgrad, "loss": head["loss"], "notes": "profiles/bench_notes.json"},
-            "roofline": pick(head["roofline"]),
         }
+        if args.full:
+            res["roofline"] = pick(head["roofline"])
         if head["comm"] is not None:
             res["comm"] = head["comm"]
         if second is not None:
@@ -832,7 +894,7 @@ def main():
                     row[o], row[o + 1] = r1(v.get("f32")), r1(v.get("bf16"))
                 models = short
             res["models"] = models
-        if world == 1 and not args.no_cpu_baseline and amp is None:
+        if args.full and world == 1 and not args.no_cpu_baseline and amp is None:
             res["cpu_baseline"] = cpu_baseline(compact=not args.verbose_json)
         print(json.dumps(res, separators=(",", ":")) if args.verbose_json else fit_line(res), flush=True)
     if distributed:

@@ -100,7 +100,7 @@ def range_view(feats, h=RANGE_H, w=RANGE_W):
 def cylinder_frame(seed, n_points=None):
     """One scan through the reference's OWN dataset transform (SemkittiCylinderDataset.get_single_sample inference
     branch + collate_batch, R:pcseg/data/dataset/semantickitti/semantickitti_cylinder.py:99-213) on the shipped cy480
-    grid. The dataset module is pure NumPy and is staged to the GPU box (tests/golden/stage_reference.py EXTRA)."""
+    grid. The dataset module is pure NumPy, read from the reference's tree (tests/golden/stage_reference.py)."""
     import importlib
     from openpcseg_amd.workloads.synthetic import make_scan
     if not hasattr(np, "int"):

@@ -195,7 +195,7 @@ def import_reference_minkunet():
     from stage_reference import reference_root
     root = reference_root()
     if root is None:
-        raise RuntimeError("neither /root/reference nor the staged tests/_refsrc is present")
+        raise RuntimeError("the reference's sources are not present")
     if root not in sys.path:
         sys.path.insert(0, root)
     import importlib

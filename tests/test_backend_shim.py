@@ -28,7 +28,7 @@ def ref_functional():
     for name in TS_FUNCTIONAL:
         src = functional_source(name)
         if src is None:
-            pytest.skip("the reference's functional sources are not available (no /root/reference, nothing staged)")
+            pytest.skip("the reference's functional sources are not present")
         m = types.ModuleType("ref_ts_functional_" + name)
         exec(compile(src, "<TS:torchsparse/nn/functional/%s.py>" % name, "exec"), m.__dict__)
         mods[name] = m

@@ -14,6 +14,8 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+from stage_reference import reference_root  # noqa: E402
 
 
 def _free_port():
@@ -171,7 +173,7 @@ def test_bench_two_ranks_on_one_device():
     env = dict(os.environ, PCS_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1", PCS_BENCH_PREHEAT_MIN_S="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--frames-per-gpu", "2", "--no-amp-line", "--no-split-line"]
+           "--frames-per-gpu", "2", "--no-amp-line", "--no-split-line", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -194,7 +196,7 @@ def test_bench_one_rank_over_rccl():
     def run(env_extra, launcher, extra=()):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", PCS_BENCH_PREHEAT="0", **env_extra)  # same number of optimizer steps
         cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames-per-gpu", "2",
-                          "--no-cpu-baseline", "--models", "none"] + list(extra)
+                          "--no-cpu-baseline", "--models", "none", "--full"] + list(extra)
         out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
         assert out.returncode == 0, out.stderr[-3000:]
         lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -286,7 +288,7 @@ def test_bench_two_ranks_over_rccl():
     env.pop("PCS_BENCH_ONE_DEVICE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--frames-per-gpu", "2"]
+           "--frames-per-gpu", "2", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=560)
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -361,7 +363,7 @@ def test_fused_reference_block_with_syncbatchnorm_matches_global_batch(oracle_ba
     `openpcseg_amd.fuse`, two ranks with one frame each over gloo == the same block with plain BatchNorm over both frames in one
     process (the SyncBatchNorm contract): outputs, input gradients, parameter gradients (DDP would average
     them: per-rank sums add up to the global gradient), running statistics."""
-    if not os.path.isdir("/root/reference") and not os.path.isdir(os.path.join(ROOT, "tests", "_refsrc")):
+    if reference_root() is None:
         pytest.skip("reference sources not present")
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
@@ -458,7 +460,7 @@ def test_fused_reference_minkunet_under_ddp_matches_the_concatenated_batch(oracl
     fused by `openpcseg_amd.fuse`: two ranks with one frame each, and four ranks with 1 / 2 / 1 / 2 frames, over gloo. Per-frame mean losses averaged over the ranks = the gradient of
     0.5 (loss_0 + loss_1) with BatchNorm statistics over both frames: reproduced in ONE process by the unfused model with plain
     BatchNorm on the two-frame batch, backpropagating the two per-frame losses. Running statistics agree as well."""
-    if not os.path.isdir("/root/reference") and not os.path.isdir(os.path.join(ROOT, "tests", "_refsrc")):
+    if reference_root() is None:
         pytest.skip("reference sources not present")
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

@@ -30,7 +30,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import fullsize as fs  # noqa: E402
 from stage_reference import reference_root  # noqa: E402
 
-pytestmark = pytest.mark.skipif(reference_root() is None, reason="neither /root/reference nor tests/_refsrc present")
+
+def _need_reference():
+    """The reference's model sources (and config 4's dataset transform) are read where its tree is; this package's workload runs
+    against the stored fixtures alone."""
+    if reference_root() is None:
+        pytest.skip("the reference's sources are not present")
+
 
 # Bounds (absolute for logits / loss, relative for gradients), each at most ~2x the value measured on MI355X in round 3
 # (profiles/round3_fullsize_parity.json holds the measured values). Gradients: "matrix" = every >= 2-D parameter
@@ -101,8 +107,9 @@ def _inputs(cfg, g):
     from openpcseg_amd.sparse import SparseTensor
     openpcseg_amd.install_reference_aliases()
     if cfg == "config4":
+        _need_reference()
         import make_golden
-        make_golden.import_reference_minkunet()  # import stubs + sys.path for the (staged) reference tree
+        make_golden.import_reference_minkunet()  # import stubs + sys.path for the reference tree
     batch = fs.build_inputs(cfg, SparseTensor)
     for k, v in fs.input_crcs(cfg, batch).items():
         assert int(v) == int(g[k]), "input %s differs from the frame the reference ran on" % k
@@ -110,6 +117,7 @@ def _inputs(cfg, g):
 
 
 def _reference_model(cfg):
+    _need_reference()
     import make_golden as mg
     import openpcseg_amd
     from seeded import seeded_state

@@ -22,7 +22,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from stage_reference import reference_root  # noqa: E402
 from test_reference_models import _Env, _load, _np  # noqa: E402
 
-pytestmark = pytest.mark.skipif(reference_root() is None, reason="neither /root/reference nor tests/_refsrc present")
+REFERENCE_FREE = {"test_dense_linear_and_batchnorm_match_torch_on_hip"}   # stock torch modules only
+
+
+@pytest.fixture(autouse=True)
+def _needs_reference(request):
+    if reference_root() is None and request.function.__name__ not in REFERENCE_FREE:
+        pytest.skip("the reference's sources are not present")
 
 
 @pytest.fixture(scope="module")

@@ -79,7 +79,7 @@ def _model(route, dev):
                          dropout=cfg["DROPOUT_P"])
     else:
         if reference_root() is None:
-            pytest.skip("neither /root/reference nor tests/_refsrc present")
+            pytest.skip("the reference's sources are not present")
         import make_golden as mg
         import openpcseg_amd
         openpcseg_amd.install_reference_aliases()

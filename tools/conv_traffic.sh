@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 : > $R/gpurun_out/conv_traffic_pmc.txt
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$c
-  PCS_BENCH_PREHEAT=0 rocprofv3 --pmc $c --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-split-line --no-device-input-line --models none > /tmp/pmc_$c.log 2>&1
+  PCS_BENCH_PREHEAT=0 rocprofv3 --pmc $c --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-split-line --no-device-input-line --models none > /tmp/pmc_$c.log 2>&1
   f=$(find /tmp/pmc_$c -name "*counter_collection.csv" | head -1)
   cp "$f" /tmp/pmc_$c.csv
   python $R/tools/pmc_summary.py "$f" conv_os >> $R/gpurun_out/conv_traffic_pmc.txt
@@ -20,8 +20,8 @@ def total(path, pred):
             s += float(r["Counter_Value"]); n += 1
     return s, n
 out = {"kernel_revision": lib.pcs_conv_kernel_revision().decode(),
-       "command": "bash tools/conv_traffic.sh: rocprofv3 --pmc FETCH_SIZE -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline ; same with "
-                  "--pmc WRITE_SIZE (separate passes); the default bench run holds the fp32 step and the bf16 step",
+       "command": "bash tools/conv_traffic.sh: rocprofv3 --pmc FETCH_SIZE -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline ; "
+                  "same with --pmc WRITE_SIZE (separate passes); the --full bench run holds the fp32 step and the bf16 step",
        "correction": "FETCH_SIZE doubled (gfx950 reports 1/2 of wide coalesced reads, MI355X_MICROARCH.md section HBM); WRITE_SIZE as reported"}
 for key, pred in (("f32", lambda n: "conv_os" in n and "conv_os5h" not in n and "conv_os6h" not in n and "conv_os5x" not in n), ("half", lambda n: "conv_os5h" in n or "conv_os6h" in n)):
     f, nf = total("/tmp/pmc_FETCH_SIZE.csv", pred)

@@ -10,8 +10,8 @@ MinkUNet workload. One record per (model, source, dtype) for BASELINE configs 2-
   fusion/rpvnet/rpvnet.py; batch sizes from R:tools/cfgs/{voxel,fusion}/semantic_kitti/*.yaml.
 
 A step = zero_grad + forward + loss + backward + SGD step on synthetic 120k-point scans resident in HBM (every kernel map
-rebuilt each step, as in the reference). The reference sources are read from /root/reference or their staged copy
-tests/_refsrc (bench plumbing: nothing under openpcseg_amd/ imports this file).
+rebuilt each step, as in the reference). The reference sources are read in place (tests/golden/stage_reference.py; bench
+plumbing: nothing under openpcseg_amd/ imports this file).
 
     python tools/modelbench.py [spec]        spec = "auto" | comma list of name[:reference|fuse|workload][:f32|bf16]
 
