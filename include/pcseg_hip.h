@@ -34,7 +34,7 @@ extern "C" {
 #define PCS_ELAUNCH (-3)  /* hipLaunch / hipMemsetAsync failed (pcs_last_error has text) */
 #define PCS_EUNSUPPORTED (-4)
 
-#define PCS_ABI_VERSION 11
+#define PCS_ABI_VERSION 12
 
 int pcs_abi_version(void);
 const char *pcs_last_error(void);
@@ -200,8 +200,7 @@ int pcs_rulebook_tile_segments(const int32_t *pairs, const int32_t *koff, int32_
 /* Heaviest-first order of the row tiles of a segment table (work of a tile = its 16-row MFMA blocks over all
  * offsets): order[i] = the tile the i-th workgroup slot of the fused convolution runs. Workgroups are dispatched in
  * index order, so the light tiles run last and the launch drains evenly (+4..8 % on the deep levels). The order among
- * equally heavy tiles is unspecified; results never depend on the order. (PCS_TILE_ORDER_XCD=1, measured and not the
- * default: the slots of one XCD (i % 8) walk one contiguous eighth of the tiles, heaviest first inside it.) */
+ * equally heavy tiles is unspecified; results never depend on the order. */
 int pcs_rulebook_tile_order(const int32_t *seg, int32_t K, int64_t ntiles, int32_t *order, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -253,18 +252,10 @@ int pcs_conv_gather_gemm_f32(const float *src, int64_t n_src, int32_t cin, const
  *            (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:88-129 `relu(net(x) + downsample(x))`): the gradient the skip path
  *            hands back rides in, instead of a separate elementwise sum of the two gradients (what autograd does around
  *            TS:torchsparse/backend/convolution/convolution_cuda.cu:167-278).
- *   bn_x / bn_mask / bn_stat : this launch is the dgrad that produces dy of a BatchNorm (+ ReLU) OUTPUT (minkunet.py:31-129:
- *            conv -> BatchNorm -> ReLU -> conv): bn_x = that BatchNorm's input rows (n_dst, cout) in dst's dtype, bn_mask = its ReLU
- *            gate, one bit per element ((n_dst, cout / 32) words as pcs_bn_apply_* writes them; NULL = no ReLU), bn_stat = its
- *            mean[cout] | invstd[cout]. The write-back then leaves the BatchNorm's BACKWARD statistics sum(g), sum(g xhat),
- *            g = dy [y > 0], per tile in `bn_partial` ([tiles][2][cout] doubles; reduce with pcs_bn_bwd_reduce_partials) -- the
- *            statistics pass of torch's batch_norm_backward over (dy, x) disappears. Needs pcs_conv_emits_bn_partials() == 1.
- * Shapes the wave kernels do not serve (pcs_conv_supports_epilogue() == 0) return PCS_EUNSUPPORTED when any extra is set. */
+ * Shapes the wave kernels do not serve (pcs_conv_supports_epilogue() == 0) return PCS_EUNSUPPORTED when any extra is set.
+ * ABI v12: the struct no longer carries the BatchNorm backward-statistics inputs between addend and act_slope. */
 typedef struct pcs_conv_epilogue {
   const void *addend;
-  const void *bn_x;
-  const uint32_t *bn_mask;
-  const double *bn_stat;
   float act_slope;   /* LeakyReLU fused into the write-back: dst = v < 0 ? v * act_slope : v, applied before the store and before the
                       * forward BatchNorm statistics (R:pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:88-190: conv -> LeakyReLU
                       * -> BatchNorm1d). 0 is read as 1 (no activation), so a zero-initialised struct is the plain call. */
@@ -372,7 +363,7 @@ int pcs_range_sample_bwd_csr_f32(const float *gout, const int64_t *order, const 
  *             (3c doubles of storage): the parameter gradients in the parameters' dtype without a conversion launch.
  *             ABI v8: the caller states the size of `sums2` in doubles (`sums2_doubles` >= 3c, else PCS_EWORKSPACE) -- a v6 caller's
  *             2c-double buffer fails loudly instead of being overrun. (v8 also drops pcs_conv_ring_enable / pcs_conv_ring_applies:
- *             the experimental ring kernels left the product library, tools/experimental/.)
+ *             the experimental ring kernels left the product library.)
  *   single process, statistics from the convolution's write-back: pcs_bn_reduce_partials_finalize = pcs_bn_reduce_partials +
  *             pcs_bn_finalize_f32 (count = n) in one launch (ABI v7; `sums` may be NULL there).
  * partial_ws: pcs_bn_num_partials() * 2 * c floats.
@@ -382,9 +373,6 @@ int pcs_range_sample_bwd_csr_f32(const float *gout, const int64_t *order, const 
 int32_t pcs_bn_num_partials(void);
 int pcs_bn_stats_f32(const float *x, int64_t n, int32_t c, float *partial_ws, double *sums, void *stream);
 int pcs_bn_reduce_partials(const double *partial, int64_t nrows, int32_t c, int64_t n, double *sums, void *stream);
-/* Backward twin: [sum g | sum g xhat] (2c doubles followed by the same values as 2c floats; sums2_doubles >= 3c) from the per-tile
- * partials of a dgrad write-back (pcs_conv_gather_gemm_*_ex with bn_x): replaces pcs_bn_bwd_stats_* for that BatchNorm. */
-int pcs_bn_bwd_reduce_partials(const double *partial, int64_t nrows, int32_t c, double *sums2, int64_t sums2_doubles, void *stream);
 int pcs_bn_reduce_partials_finalize(const double *partial, int64_t nrows, int32_t c, int64_t n, double eps, double momentum,
                                     float *running_mean, float *running_var, double *sums, double *stat, void *stream);
 int pcs_bn_finalize_f32(const double *sums, double count, const double *count_dev, int32_t c, double eps,
@@ -499,7 +487,7 @@ int pcs_conv_gather_gemm_h(const void *src, int64_t n_src, int32_t cin, const vo
                            const int32_t *pairs, int32_t src_col, const int32_t *seg, int32_t tile_rows,
                            int64_t n_dst, const float *bias, void *dst, int32_t dtype, double *bn_partial,
                            const int32_t *tile_order, void *stream);
-/* with the write-back extras of pcs_conv_gather_gemm_f32_ex (addend / bn_x in the storage dtype) */
+/* with the write-back extras of pcs_conv_gather_gemm_f32_ex (addend in the storage dtype) */
 int pcs_conv_gather_gemm_h_ex(const void *src, int64_t n_src, int32_t cin, const void *Wp, int32_t K, int32_t cout,
                               const int32_t *pairs, int32_t src_col, const int32_t *seg, int32_t tile_rows,
                               int64_t n_dst, const float *bias, const pcs_conv_epilogue *ep, void *dst, int32_t dtype,

@@ -132,12 +132,8 @@ def bn_forward(bn, input, residual=None, relu=False, cat_with=None, in_slope=Non
         if pre is not None:
             sums, of, ver = pre
             pre = sums if (of is x and x._version == ver) else None
-        from . import fused as _fz
-        link = _fz.BNLink() if (_fz.LINK_BN_BWD and tail is None and torch.is_grad_enabled()) else None
         y = _FusedBN.apply(x, r, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu,
-                           isinstance(bn, nn.SyncBatchNorm), input.cmaps, input.stride, pre, tail, link, in_slope)
-        if link is not None and link.x is not None:
-            y._pcs_bn_link = link   # the one sparse convolution that consumes y leaves this BatchNorm's backward statistics (fused.BNLink)
+                           isinstance(bn, nn.SyncBatchNorm), input.cmaps, input.stride, pre, tail, in_slope)
     else:
         inv = torch.rsqrt(bn.running_var.double() + bn.eps)
         stat = torch.cat([bn.running_mean.double(), inv]).contiguous()

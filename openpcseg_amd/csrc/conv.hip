@@ -56,7 +56,7 @@ extern "C" int pcs_transpose_kab_f32(const float *src, int32_t K, int32_t A, int
 
 // Bumped whenever a fused-conv kernel, its launch shape picker or its epilogue changes: measurements keyed to kernels
 // (profiles/*_conv_traffic.json) carry the revision they were taken on and bench.py refuses a stale one.
-extern "C" const char *pcs_conv_kernel_revision(void) { return "r6.0"; }
+extern "C" const char *pcs_conv_kernel_revision(void) { return "r6.1"; }
 
 extern "C" int32_t pcs_conv_tile_rows(int32_t cin, int32_t cout) {
   (void)cin;
@@ -207,35 +207,23 @@ extern "C" int pcs_conv_gather_gemm_f32_ex(const float *src, int64_t n_src, int3
   a.order = tile_order;
   a.addend = addend;
   if (addend && ((uintptr_t)addend & 15)) { set_error("pcs_conv_gather_gemm_f32_ex: misaligned addend"); return PCS_EINVAL; }
-  if (ep && ep->bn_x) {
-    if (!bn_partial || !ep->bn_stat || ((uintptr_t)ep->bn_x & 15) || (ep->bn_mask && (cout & 31))) {
-      set_error("pcs_conv_gather_gemm_f32_ex: BatchNorm backward statistics need bn_partial, bn_stat, 16-byte aligned bn_x and cout %% 32 == 0 with a gate mask");
-      return PCS_EINVAL;
-    }
-    a.gs_x = ep->bn_x; a.gs_mask = ep->bn_mask; a.gs_stat = ep->bn_stat;
-  }
   if (ep && ep->act_slope != 0.f && ep->act_slope != 1.f) a.act_slope = ep->act_slope;
   if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, 0)) {
     set_error("pcs_conv_gather_gemm_f32: this shape / tile height does not produce BatchNorm partials (ask pcs_conv_emits_bn_partials)");
     return PCS_EUNSUPPORTED;
   }
-  static const int xcd = getenv("PCS_CONV_XCD") ? atoi(getenv("PCS_CONV_XCD")) : 1;  // 0: no XCD-contiguous tile order (debug)
-  // 1: tiles in row order, one contiguous range per XCD; 2 (with a tile order): tiles dealt round-robin over the XCDs,
-  // the column tiles of a row tile back to back on one XCD (they gather the same A rows: +0.5..1 %)
-  a.xcd_remap = xcd ? (tile_order ? 2 : 1) : 0;
   const bool vec = (cin % 4 == 0) && (cout % 4 == 0) && (((uintptr_t)src | (uintptr_t)W | (uintptr_t)dst | (uintptr_t)bias) & 15) == 0;
   hipStream_t st = as_stream(stream);
-  static const int generic = getenv("PCS_CONV_V1") ? atoi(getenv("PCS_CONV_V1")) : 0;  // 1: generic kernel only (debug)
-  if (bn_partial && (!vec || generic || (!conv5_applies(cin, cout, K) && K > 32))) {
+  if (bn_partial && (!vec || (!conv5_applies(cin, cout, K) && K > 32))) {
     set_error("pcs_conv_gather_gemm_f32: BatchNorm partials need the 16-byte-granular wave kernels");
     return PCS_EUNSUPPORTED;
   }
-  if ((addend || a.gs_x || a.act_slope != 1.f) && !(vec && !generic && K <= 32)) {
+  if ((addend || a.act_slope != 1.f) && !(vec && K <= 32)) {
     set_error("pcs_conv_gather_gemm_f32_ex: this shape runs on the generic kernel, which takes no write-back extras (pcs_conv_supports_epilogue)");
     return PCS_EUNSUPPORTED;
   }
-  if (vec && !generic && conv5_applies(cin, cout, K)) return launch_conv_wave5(a, st);
+  if (vec && conv5_applies(cin, cout, K)) return launch_conv_wave5(a, st);
   if (tile_rows != 64 && tile_rows != 128) { set_error("pcs_conv_gather_gemm_f32: this shape takes tile_rows 64 or 128"); return PCS_EUNSUPPORTED; }
-  if (vec && !generic && K <= 32) return launch_conv_wave4(a, st);
+  if (vec && K <= 32) return launch_conv_wave4(a, st);
   return launch_conv_block(a, vec, st);
 }

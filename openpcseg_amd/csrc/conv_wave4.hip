@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os4_kernel(ConvArgs a) {
   // Give every XCD one CONTIGUOUS range of tiles so that neighbouring tiles -- which gather
   // overlapping src rows -- share that XCD's L2 (bijective remap for any grid size).
   unsigned bid = blockIdx.x;
-  if (a.xcd_remap) {
+  {
     const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
@@ -274,7 +274,6 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os4_kernel(ConvArgs a) {
   const int rows = (int)((a.n_dst - row0) < (int64_t)T ? (a.n_dst - row0) : (int64_t)T);
   float *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
-  const GStat gstat{a.gs_x, a.gs_mask, a.gs_stat, kGsF32};
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
                                    [&](int r, int cq, const float4 &v0) {
                                      float4 v = v0;
@@ -288,7 +287,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os4_kernel(ConvArgs a) {
                                      }
                                      *reinterpret_cast<float4 *>(drow + (int64_t)r * ldd + cq) = v;
                                      return v;
-                                   }, a.gs_x ? &gstat : nullptr, row0);
+                                   });
 }
 
 template <int NCTT, int T, int NW, int MINW>

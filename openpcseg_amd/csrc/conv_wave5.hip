@@ -34,7 +34,7 @@ struct Conv5Cfg {
   static constexpr int N2 = (NCTT % 4) / 2;
   static constexpr int N1 = NCTT % 2;
   static constexpr int NWL = N4 + N2 + N1;  // W loads per contraction step
-  static constexpr int SINK = kConvSinkRows;  // atomic commit: padding rows of lane group g accumulate into sink row T + g
+  static constexpr int SINK = kConvSinkRows;
   static constexpr size_t lds_bytes(int T) { return (size_t)((T + SINK) * ACS) * 4 + 5 * 33 * 4 + 16; }
 };
 
@@ -58,13 +58,13 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // a scalar: wave-level loops and branches stay uniform
   const int g = lane >> 4, l15 = lane & 15;
   unsigned bid = blockIdx.x;
-  if (a.xcd_remap && !a.order) {  // row order: one contiguous tile range per XCD; heaviest-first order: dealt round-robin
+  if (!a.order) {  // row order: one contiguous tile range per XCD; heaviest-first order: dealt round-robin
     const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   int64_t slot = bid / a.ncoltiles;
   int ctile = bid % a.ncoltiles;
-  if (a.xcd_remap == 2) {  // the column tiles of one row tile on ONE XCD, back to back (they gather the same A rows)
+  if (a.order) {  // the column tiles of one row tile on ONE XCD, back to back (they gather the same A rows)
     const unsigned xcd = bid & 7, idx = bid >> 3;
     slot = (int64_t)(idx / a.ncoltiles) * 8 + xcd;
     ctile = idx % a.ncoltiles;
@@ -336,13 +336,8 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int dl = __shfl(cur.dloc[r], 4 * g + j, 64);
-#if PCS_COMMIT_ATOMIC
-        doff[r][j] = (dl >= T ? T + g : dl) * C::ACS;  // padding rows: a sink row of this lane group's own (no same-address adds)
-#else
         doff[r][j] = dl * C::ACS;
-#endif
       }
-#if PCS_COMMIT_PHASED && !PCS_COMMIT_ATOMIC
     unsigned dq[R][4], dp[R][4];  // LDS byte addresses of this lane's pieces of the rows it commits
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -352,61 +347,13 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
         dp[r][j] = acc_lds + 4u * (unsigned)doff[r][j] + 256u * C::N4 + (C::N2 ? 8u : 4u) * l15;
         asm volatile("" : "+v"(dq[r][j]), "+v"(dp[r][j]));  // formed BEFORE the ticket wait, not sunk into the critical section
       }
-#elif PCS_COMMIT_ATOMIC
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(doff[r][j]));
-#endif
     if (lane == 0) {
       while (__hip_atomic_load(commit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != grp)
         __builtin_amdgcn_s_sleep(1);
     }
-#if PCS_COMMIT_ATOMIC
-    // Round 3: the accumulate is ONE ds_add_f32 per lane and tile element, issued while the wave holds the ticket and
-    // never waited for. The LDS executes a wave's instructions in order, so the adds of this group reach every address
-    // before the ticket store that follows them, and the next owner -- who starts issuing only after it has read the
-    // new ticket -- adds after us: the per-address order is the ticket order (bit-reproducible sums, the same fp32
-    // additions as the read-add-write form), but the chain link shrinks from [LDS read latency + add + write +
-    // completion wait] to the issue time of the adds.
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_setprio(3);
-    PCS_T(const long long tr_c = wall_clock64();)
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (r < nr) {  // wave-uniform
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float *d = acc_l + doff[r][j];
-#pragma unroll
-          for (int q = 0; q < C::N4; ++q) {
-            lds_add(d + 64 * q + 4 * l15 + 0, acc[r][4 * q + 0][j]);
-            lds_add(d + 64 * q + 4 * l15 + 1, acc[r][4 * q + 1][j]);
-            lds_add(d + 64 * q + 4 * l15 + 2, acc[r][4 * q + 2][j]);
-            lds_add(d + 64 * q + 4 * l15 + 3, acc[r][4 * q + 3][j]);
-          }
-          if (C::N2) {
-            lds_add(d + 64 * C::N4 + 2 * l15 + 0, acc[r][4 * C::N4 + 0][j]);
-            lds_add(d + 64 * C::N4 + 2 * l15 + 1, acc[r][4 * C::N4 + 1][j]);
-          }
-          if (C::N1) lds_add(d + 64 * C::N4 + 32 * C::N2 + l15, acc[r][NCTT - 1][j]);
-        }
-      }
-    }
-#if PCS_COMMIT_NOWAIT
-    // the ticket store stays behind the adds in program order and the LDS keeps that order; written as a bare
-    // ds_write_b32 -- the compiler puts s_waitcnt lgkmcnt(0) in front of its own store, i.e. the completion wait back
-    if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(grp + 1) : "memory");
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    if (lane == 0) __hip_atomic_store(commit, grp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-    __builtin_amdgcn_s_setprio(0);
-#else
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
     __builtin_amdgcn_s_setprio(3);
     PCS_T(const long long tr_c = wall_clock64();)
-#if PCS_COMMIT_PHASED
     {
       // Three phases, each behind a compiler barrier: every LDS read of the group (one latency for all of them), every
       // add, every write. Round 2's interleaving went through ~8 read-wait-add rounds per group, each a full LDS
@@ -464,52 +411,11 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
         asm volatile("" ::: "memory");
       }
     }
-#else
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (r < nr) {  // wave-uniform
-        // all LDS reads of the block first (one latency), then the adds, then the writes
-        float *d[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = acc_l + doff[r][j];
-        float4 v4[4][C::N4 > 0 ? C::N4 : 1];
-        float2 v2[4];
-        float v1[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-          for (int q = 0; q < C::N4; ++q) v4[j][q] = *reinterpret_cast<const float4 *>(d[j] + 64 * q + 4 * l15);
-          if (C::N2) v2[j] = *reinterpret_cast<const float2 *>(d[j] + 64 * C::N4 + 2 * l15);
-          if (C::N1) v1[j] = d[j][64 * C::N4 + 32 * C::N2 + l15];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-          for (int q = 0; q < C::N4; ++q) {
-            v4[j][q].x += acc[r][4 * q + 0][j]; v4[j][q].y += acc[r][4 * q + 1][j];
-            v4[j][q].z += acc[r][4 * q + 2][j]; v4[j][q].w += acc[r][4 * q + 3][j];
-            *reinterpret_cast<float4 *>(d[j] + 64 * q + 4 * l15) = v4[j][q];
-          }
-          if (C::N2) {
-            v2[j].x += acc[r][4 * C::N4 + 0][j]; v2[j].y += acc[r][4 * C::N4 + 1][j];
-            *reinterpret_cast<float2 *>(d[j] + 64 * C::N4 + 2 * l15) = v2[j];
-          }
-          if (C::N1) d[j][64 * C::N4 + 32 * C::N2 + l15] = v1[j] + acc[r][NCTT - 1][j];
-        }
-      }
-    }
-#endif
-#if PCS_COMMIT_NOWAIT
     // the ticket store stays behind the tile writes in program order and the LDS keeps a wave's instructions in order; a
     // bare ds_write_b32 because the compiler puts the completion wait (s_waitcnt lgkmcnt(0)) in front of its own store
+    // (the hardware assumption is stated once)
     if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(grp + 1) : "memory");
     __builtin_amdgcn_s_setprio(0);
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    if (lane == 0) __hip_atomic_store(commit, grp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
     PCS_T(const long long tr_d = wall_clock64(); tr_loop += tr_b - tr_a; tr_ticket += tr_c - tr_b; tr_commit += tr_d - tr_c; ++tr_groups;)
     cur = nxt;
     i = in;
@@ -524,7 +430,6 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
   const int rows = (int)((a.n_dst - row0) < (int64_t)T ? (a.n_dst - row0) : (int64_t)T);
   float *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
-  const GStat gstat{a.gs_x, a.gs_mask, a.gs_stat, kGsF32};
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
                                    [&](int r, int cq, const float4 &v0) {
                                      float4 v = v0;
@@ -538,7 +443,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
                                      }
                                      *reinterpret_cast<float4 *>(drow + (int64_t)r * ldd + cq) = v;
                                      return v;
-                                   }, a.gs_x ? &gstat : nullptr, row0);
+                                   });
 #if PCS_TRACE
   if (lane == 0 && blockIdx.x < kTraceBlocks && g_conv_trace) {
     long long *t = g_conv_trace + ((int64_t)blockIdx.x * 8 + wid) * 8;
@@ -562,7 +467,7 @@ void trace_prepare(hipStream_t st) {
 template <int NCTT, int NW, int MINW, int R, bool TAIL>
 int launch_conv5(const ConvArgs &a, hipStream_t st) {
   using C = Conv5Cfg<NCTT, NW, R>;
-  const int64_t nblocks = a.xcd_remap == 2 ? ceil_div(a.ntiles, 8) * 8 * a.ncoltiles : a.ntiles * a.ncoltiles;
+  const int64_t nblocks = a.order ? ceil_div(a.ntiles, 8) * 8 * a.ncoltiles : a.ntiles * a.ncoltiles;
   if (nblocks <= 0) return PCS_OK;
   if (nblocks > 0x7FFFFFFF) { set_error("pcs_conv: grid too large"); return PCS_EUNSUPPORTED; }
   auto kern = conv_os5_kernel<NCTT, NW, MINW, R, TAIL>;

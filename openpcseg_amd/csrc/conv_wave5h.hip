@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // a scalar: wave-level loops and branches stay uniform
   const int g = lane >> 4, l15 = lane & 15;
   unsigned bid = blockIdx.x;
-  if (a.xcd_remap && !a.order) {
+  if (!a.order) {
     const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
@@ -325,13 +325,8 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int dl = __shfl(cur.dloc[r], 4 * g + j, 64);
-#if PCS_COMMIT_ATOMIC
-        doff[r][j] = (dl >= T ? T + g : dl) * C::ACS;  // padding rows: a sink row of this lane group's own
-#else
         doff[r][j] = dl * C::ACS;
-#endif
       }
-#if PCS_COMMIT_PHASED && !PCS_COMMIT_ATOMIC
     unsigned dq[R][4], dp[R][4];  // LDS byte addresses of this lane's pieces of the rows it commits
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -341,12 +336,6 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
         dp[r][j] = acc_lds + 4u * (unsigned)doff[r][j] + 256u * C::N4 + (C::N2 ? 8u : 4u) * l15;
         asm volatile("" : "+v"(dq[r][j]), "+v"(dp[r][j]));  // formed BEFORE the ticket wait, not sunk into the critical section
       }
-#elif PCS_COMMIT_ATOMIC
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(doff[r][j]));
-#endif
 #if PCS_ABLATEH == 3 || PCS_ABLATEH == 4   /* timing only: no ticket, no commit */
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -358,34 +347,9 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
       while (__hip_atomic_load(commit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != grp)
         __builtin_amdgcn_s_sleep(1);
     }
-#if PCS_COMMIT_ATOMIC
-    // ds_add_f32 accumulate in ticket order, never waited for (see conv_wave5.hip); columns 16 t + l15: conflict-free rows
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_setprio(3);
-    PCS_T(const long long tr_c = wall_clock64();)
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (r < nr) {  // wave-uniform
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float *d = acc_l + doff[r][j] + l15;
-#pragma unroll
-          for (int t = 0; t < NCTT; ++t) lds_add(d + 16 * t, acc[r][t][j]);
-        }
-      }
-    }
-#if PCS_COMMIT_NOWAIT
-    if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(grp + 1) : "memory");  // see conv_wave5.hip
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    if (lane == 0) __hip_atomic_store(commit, grp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-    __builtin_amdgcn_s_setprio(0);
-#else
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
     __builtin_amdgcn_s_setprio(3);
     PCS_T(const long long tr_c = wall_clock64();)
-#if PCS_COMMIT_PHASED
     {
       // Three phases, each behind a compiler barrier: every LDS read of the group (one latency for all of them), every
       // add, every write. Round 2's interleaving went through ~8 read-wait-add rounds per group, each a full LDS
@@ -443,51 +407,10 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
         asm volatile("" ::: "memory");
       }
     }
-#else
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (r < nr) {  // wave-uniform
-        float *d[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = acc_l + doff[r][j];
-        float4 v4[4][C::N4 > 0 ? C::N4 : 1];
-        float2 v2[4];
-        float v1[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-          for (int q = 0; q < C::N4; ++q) v4[j][q] = *reinterpret_cast<const float4 *>(d[j] + 64 * q + 4 * l15);
-          if (C::N2) v2[j] = *reinterpret_cast<const float2 *>(d[j] + 64 * C::N4 + 2 * l15);
-          if (C::N1) v1[j] = d[j][64 * C::N4 + 32 * C::N2 + l15];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-          for (int q = 0; q < C::N4; ++q) {
-            v4[j][q].x += acc[r][4 * q + 0][j]; v4[j][q].y += acc[r][4 * q + 1][j];
-            v4[j][q].z += acc[r][4 * q + 2][j]; v4[j][q].w += acc[r][4 * q + 3][j];
-            *reinterpret_cast<float4 *>(d[j] + 64 * q + 4 * l15) = v4[j][q];
-          }
-          if (C::N2) {
-            v2[j].x += acc[r][4 * C::N4 + 0][j]; v2[j].y += acc[r][4 * C::N4 + 1][j];
-            *reinterpret_cast<float2 *>(d[j] + 64 * C::N4 + 2 * l15) = v2[j];
-          }
-          if (C::N1) d[j][64 * C::N4 + 32 * C::N2 + l15] = v1[j] + acc[r][NCTT - 1][j];
-        }
-      }
-    }
-#endif
-#if PCS_COMMIT_NOWAIT
     // the ticket store stays behind the tile writes in program order and the LDS keeps a wave's instructions in order; a
     // bare ds_write_b32 because the compiler puts the completion wait (s_waitcnt lgkmcnt(0)) in front of its own store
     if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(grp + 1) : "memory");
     __builtin_amdgcn_s_setprio(0);
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    if (lane == 0) __hip_atomic_store(commit, grp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
 #endif  // PCS_ABLATEH 3 / 4
     PCS_T(const long long tr_d = wall_clock64(); tr_loop += tr_b - tr_a; tr_ticket += tr_c - tr_b; tr_commit += tr_d - tr_c; ++tr_groups;)
     cur = nxt;
@@ -509,7 +432,6 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
   const int rows = (int)((a.n_dst - row0) < (int64_t)T ? (a.n_dst - row0) : (int64_t)T);
   uint16_t *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
-  const GStat gstat{a.gs_x, a.gs_mask, a.gs_stat, GsType<HT>::value};
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
                                    [&](int r, int cq, const float4 &v0) {
                                      float4 v = v0;
@@ -528,7 +450,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
                                      o.y = hz | ((uint32_t)hw << 16);
                                      *reinterpret_cast<uint2 *>(drow + (int64_t)r * ldd + cq) = o;
                                      return make_float4(h2f(HT{}, hx), h2f(HT{}, hy), h2f(HT{}, hz), h2f(HT{}, hw));
-                                   }, a.gs_x ? &gstat : nullptr, row0);
+                                   });
 #if PCS_TRACE
   if (lane == 0 && blockIdx.x < kTraceBlocksH && g_convh_trace) {
     long long *t = g_convh_trace + ((int64_t)blockIdx.x * 8 + wid) * 8;
@@ -667,16 +589,9 @@ extern "C" int pcs_conv_gather_gemm_h_ex(const void *src, int64_t n_src, int32_t
   a.src = reinterpret_cast<const char *>(src); a.Wp = reinterpret_cast<const char *>(Wp); a.bias = bias;
   a.dst = reinterpret_cast<uint16_t *>(dst); a.pairs = pairs; a.seg = seg;
   a.n_dst = n_dst; a.ntiles = ceil_div(n_dst, tile_rows); a.tile_rows = tile_rows;
-  a.cin = cin; a.cout = cout; a.K = K; a.src_col = src_col; a.ncoltiles = 1; a.xcd_remap = 1; a.stats = bn_partial; a.order = tile_order;
+  a.cin = cin; a.cout = cout; a.K = K; a.src_col = src_col; a.ncoltiles = 1; a.stats = bn_partial; a.order = tile_order;
   a.addend = reinterpret_cast<const uint16_t *>(addend);
   if (addend && ((uintptr_t)addend & 7)) { set_error("pcs_conv_gather_gemm_h_ex: misaligned addend"); return PCS_EINVAL; }
-  if (ep && ep->bn_x) {
-    if (!bn_partial || !ep->bn_stat || ((uintptr_t)ep->bn_x & 7) || (ep->bn_mask && (cout & 31))) {
-      set_error("pcs_conv_gather_gemm_h_ex: BatchNorm backward statistics need bn_partial, bn_stat, aligned bn_x and cout %% 32 == 0 with a gate mask");
-      return PCS_EINVAL;
-    }
-    a.gs_x = ep->bn_x; a.gs_mask = ep->bn_mask; a.gs_stat = ep->bn_stat;
-  }
   if (ep && ep->act_slope != 0.f && ep->act_slope != 1.f) a.act_slope = ep->act_slope;
   if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, dtype)) {
     set_error("pcs_conv_gather_gemm_h: this shape / tile height does not produce BatchNorm partials");

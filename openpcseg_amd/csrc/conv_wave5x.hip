@@ -401,15 +401,9 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5x_kernel(ConvArgsX a) {
         asm volatile("" ::: "memory");
       }
     }
-#if PCS_COMMIT_NOWAIT
     // as conv_wave5.hip: the ticket store stays behind the tile writes in program order and the LDS executes one wave's
-    // instructions in order (the hardware assumption is stated once); PCS_COMMIT_NOWAIT=0 is the
-    // fenced form, bit-identical (tests/test_dense_parity.py::test_commit_variants_bit_identical on a variant library)
+    // instructions in order (the hardware assumption is stated once)
     if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(grp + 1) : "memory");
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    if (lane == 0) __hip_atomic_store(commit, grp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
     __builtin_amdgcn_s_setprio(0);
     cur = nxt;
     i = in;

@@ -24,10 +24,9 @@
 //
 // Shapes: cin % 32 == 0 with NS x NCTT <= 32 fragments (instances below); everything else stays on conv_wave5h.hip. Padding rows
 // of a row block re-read the slice's last pair and land in the sink row (never read).
-// Rejected on the way (profiles/round6_convh_ws.md): units of <= RU row blocks dealt round-robin (v1,
-// tools/experimental/csrc/conv_wave6h_v1_units.hip.txt); gathering with 4 consecutive lanes per row + a ds_bpermute transpose
-// (0 .. -3 %); 64-column tiles for the 256-channel layers (0.8 - 1.08x); one 8-wave workgroup per CU on 384 rows (the 8-wave
-// ticket chain: 33 % of the wave time in the ticket wait).
+// Rejected on the way (profiles/round6_convh_ws.md): units of <= RU row blocks dealt round-robin (v1, in git history);
+// gathering with 4 consecutive lanes per row + a ds_bpermute transpose (0 .. -3 %); 64-column tiles for the 256-channel layers
+// (0.8 - 1.08x); one 8-wave workgroup per CU on 384 rows (the 8-wave ticket chain: 33 % of the wave time in the ticket wait).
 #include "conv_half.h"
 
 using namespace pcs;
@@ -157,7 +156,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, l15 = lane & 15;
   unsigned bid = blockIdx.x;
-  if (a.xcd_remap && !a.order) {
+  if (!a.order) {
     const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
@@ -414,7 +413,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
         asm volatile("" ::: "memory");
       }
     }
-    // the ticket store stays behind the tile writes (the LDS keeps one wave's instructions in order, PCS_COMMIT_NOWAIT)
+    // the ticket store stays behind the tile writes (the LDS keeps one wave's instructions in order)
     if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(ticket + 1) : "memory");
     __builtin_amdgcn_s_setprio(0);
 #if PCS_TRACE
@@ -446,8 +445,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
   uint16_t *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
   double *stats = a.stats ? a.stats + tile * 2 * a.cout : nullptr;
-  const GStat gstat{a.gs_x, a.gs_mask, a.gs_stat, GsType<HT>::value};
-  if (!a.gs_x && (a.cout & 7) == 0 && (((uintptr_t)a.dst | (uintptr_t)a.addend) & 15) == 0 && (!stats || T + C::SINK >= 2 * C::NRG8 + 1)) {
+  if ((a.cout & 7) == 0 && (((uintptr_t)a.dst | (uintptr_t)a.addend) & 15) == 0 && (!stats || T + C::SINK >= 2 * C::NRG8 + 1)) {
     half_tile_epilogue8<HT, C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, stats, tid, drow, ldd,
                                           a.addend ? a.addend + row0 * a.cout + n0 : nullptr, a.act_slope);
   } else {
@@ -468,7 +466,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
       o.y = hz | ((uint32_t)hw << 16);
       *reinterpret_cast<uint2 *>(drow + (int64_t)r * ldd + cq4) = o;
       return make_float4(h2f(HT{}, hx), h2f(HT{}, hy), h2f(HT{}, hz), h2f(HT{}, hw));
-    }, a.gs_x ? &gstat : nullptr, row0);
+    });
   }
 #if PCS_TRACE
   if (lane == 0 && g_ws_trace && (int)blockIdx.x < g_ws_trace_blocks) {

@@ -338,11 +338,6 @@ class _SparseConv(Function):
         w3 = weight if weight.dim() == 3 else weight.unsqueeze(0)
         k, cin, cout = w3.shape
         kmap = entry.rev if transposed else entry.fwd
-        # the input is a fused BatchNorm's output: when this convolution is its only consumer, its dgrad write-back leaves that
-        # BatchNorm's backward statistics (fused.BNLink)
-        ctx.bn_link = getattr(input, "_pcs_bn_link", None)
-        if ctx.bn_link is not None:
-            ctx.bn_link.consumers += 1
         got = [] if want_stats else None
         kw = {"bn_sums": got} if want_stats else {}
         if want_stats and getattr(be, "supports_bn_raw", False):
@@ -398,24 +393,15 @@ class _SparseConv(Function):
             out_dtype = x.dtype if hd is None else hd   # the gradient leaves in the dtype the forward input arrived in
             rides = (grad_skip is not None and grad_skip.is_cuda and grad_skip.dtype == out_dtype and
                      hasattr(be, "conv_supports_addend"))   # the skip gradient as the dgrad kernel's write-back addend
-            link, bnb, bnb_out = ctx.bn_link, None, []
-            if (link is not None and link.consumers == 1 and link.x is not None and link.x.dtype == out_dtype and
-                    tuple(link.x.shape) == (dmap.n_dst, cin) and hasattr(be, "conv_emits_stats") and
-                    (grad_skip is None or rides)):
-                bnb = (link.x, link.mask, link.stat)
             if hd is not None and be.conv_h_applies(cout, cin, k):
                 if _WeightPrep.usable(be, weight):
                     wp = _WEIGHT_PREP.get(be, weight, (hd, True))
                 else:
                     wp = be.prepare_weights_h(w3.detach().float().contiguous(), hd, transpose=True)
-                ok = be.conv_supports_addend(cout, cin, k, 1) if (rides or bnb) else False
-                if bnb is not None and not (ok and be.conv_emits_stats(cout, cin, k, dmap, hd)):
-                    bnb = None
+                ok = be.conv_supports_addend(cout, cin, k, 1) if rides else False
                 kw = {}
                 if rides and ok:
                     kw["addend"], grad_skip = grad_skip, None
-                if bnb is not None and grad_skip is None:
-                    kw["bn_bwd"], kw["bn_bwd_out"] = bnb, bnb_out
                 grad_input = be.conv_gather_gemm_h(grad_output.contiguous().to(hd), wp, k, cin, dmap, **kw)
             elif hd is None and grad_output.is_cuda and _CONV_POLICY["mode"] == "bf16x3" and be.conv_x3_applies(cout, cin, k):
                 wp = be.prepare_weights_x3(w3.detach().float().contiguous(), transpose=True)
@@ -425,18 +411,12 @@ class _SparseConv(Function):
                     wt = _WEIGHT_PREP.get(be, weight, ("t",))
                 else:
                     wt = be.transpose_weights(w3.detach().float().contiguous())
-                ok = (hd is None and out_dtype == torch.float32 and be.conv_supports_addend(cout, cin, k, 0)) if (rides or bnb) else False
-                if bnb is not None and not (ok and be.conv_emits_stats(cout, cin, k, dmap, None)):
-                    bnb = None
+                ok = (hd is None and out_dtype == torch.float32 and be.conv_supports_addend(cout, cin, k, 0)) if rides else False
                 kw = {}
                 if rides and ok:
                     kw["addend"], grad_skip = grad_skip, None
-                if bnb is not None and grad_skip is None:
-                    kw["bn_bwd"], kw["bn_bwd_out"] = bnb, bnb_out
                 grad_input = be.conv_gather_gemm(grad_output.contiguous().float(), wt, dmap, **kw)
             grad_input = grad_input.to(out_dtype)
-            if bnb_out:   # this tensor IS the BatchNorm's dy: its backward recognises it by storage address and version
-                link.partials, link.dy_ptr, link.dy_version = bnb_out[0], grad_input.data_ptr(), grad_input._version
             if grad_skip is not None:   # a kernel that takes no addend (generic shapes, the split kernels, other backends)
                 grad_input = grad_input + grad_skip.to(out_dtype)
         elif grad_skip is not None:

@@ -14,26 +14,17 @@ from .. import native
 from ..sparse import PointTensor, SparseTensor, get_kernel_offsets
 
 
-VOXEL_ORDER = os.environ.get("PCS_VOXEL_ORDER", "hash")  # "hash" (the reference's row order) | "spatial" (experiment)
-
-
 def initial_voxelize(z, init_res, after_res):
     """Points -> stride-1 voxels ordered by ascending 60-bit hash (utils.py:11-36). That order scatters spatial
     neighbours over the whole tensor (every row a stride-1 convolution gathers is its own fetch: 3.7x the algorithmic
-    bytes at the fabric counters). PCS_VOXEL_ORDER=spatial orders the voxels by (batch, x, y, z) instead -- same voxel
-    set, same per-point results. Measured (12-frame batch, fp32 and bf16 steps): no difference, 88.7 vs 88.2 and 159.8
-    vs 160.1 frames/s -- the gathers of a 220-450 MB level are served by the 256 MB Infinity Cache either way -- so the
-    reference's order stays the default."""
+    bytes at the fabric counters). Voxels in (batch, x, y, z) order made no difference at the step level
+    (profiles/round6_voxel_order_ab.txt), so the reference's order stays."""
     fc = torch.cat([(z.C[:, :3] * init_res) / after_res, z.C[:, -1:].clone()], dim=1)
     cell = torch.floor(fc)
     icell = cell.int()
     pc_hash = F.sphash(icell)
     be = native.backend()
-    if VOXEL_ORDER == "spatial" and icell.is_cuda and hasattr(be, "downsample"):
-        voxel_hash = F.sphash(be.downsample(icell.contiguous(), [1, 1, 1]))  # unique cells in (b, x, y, z) order
-        idx_query = F.sphashquery(pc_hash, voxel_hash)
-        counts = F.spcount(idx_query.int(), len(voxel_hash))
-    elif icell.is_cuda and hasattr(be, "unique_inverse_csr") and os.environ.get("PCS_FUSED_VOXELIZE", "1") != "0":
+    if icell.is_cuda and hasattr(be, "unique_inverse_csr") and os.environ.get("PCS_FUSED_VOXELIZE", "1") != "0":
         # torch.unique + sphashquery + spcount of the reference (utils.py:17-19) from ONE stable sort of the point
         # hashes: unique hashes (ascending), point -> voxel map, counts; the sort is also the CSR of the two
         # segmented spvoxelize passes below (SURVEY.md section 8 f1/f2: no table build + probe, no second sort)

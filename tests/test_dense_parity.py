@@ -111,10 +111,7 @@ def test_conv_forward_dense_map(hip, levels, stride, cin, cout, tile):
 
 @pytest.mark.parametrize("stride,tile", [(1, 384), (2, 128), (4, 224), (8, 288), (8, 112)])
 def test_tile_order_heaviest_first(hip, levels, stride, tile):
-    """pcs_rulebook_tile_order: a permutation of the row tiles, work (16-row blocks over all offsets) non-increasing. With
-    PCS_TILE_ORDER_XCD=1 (opt-in): the slots of XCD c (launch position % 8 == c) hold exactly the c-th contiguous eighth of the
-    tiles (lengths differ by at most one), work non-increasing inside it."""
-    import os
+    """pcs_rulebook_tile_order: a permutation of the row tiles, work (16-row blocks over all offsets) non-increasing."""
     entry = level_map(levels, stride)[0]
     km = entry.fwd
     seg = hip._segments(km, tile).view(27, -1).cpu().numpy().astype(np.int64)
@@ -122,31 +119,8 @@ def test_tile_order_heaviest_first(hip, levels, stride, tile):
     ntiles = (km.n_dst + tile - 1) // tile
     assert order.shape == (ntiles,) and np.array_equal(np.sort(order), np.arange(ntiles))
     work = ((seg[:, 1:] - seg[:, :-1] + 15) // 16).sum(0)
-    if os.environ.get("PCS_TILE_ORDER_XCD", "0") == "0":
-        w = work[order]
-        assert (w[:-1] >= w[1:]).all() and w[0] == work.max()
-        return
-    q, r = divmod(ntiles, 8)
-    for c in range(8):
-        lo, ln = c * q + min(c, r), q + (1 if c < r else 0)
-        mine = order[c::8]
-        assert np.array_equal(np.sort(mine), np.arange(lo, lo + ln))
-        w = work[mine]
-        assert (w[:-1] >= w[1:]).all() and (ln == 0 or w[0] == work[lo:lo + ln].max())
-
-
-def test_tile_order_per_xcd_variant():
-    """PCS_TILE_ORDER_XCD=1 (the opt-in order: heaviest first inside each XCD's contiguous eighth) is read once per process: the
-    order property and the order-independence of the convolution results are checked in a subprocess started with it."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PCS_TILE_ORDER_XCD="1")
-    p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_dense_parity.py"), "-q", "-x", "-m", "gpu",
-                        "-k", "test_tile_order_heaviest_first or test_conv_is_independent_of_the_tile_order", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=900, cwd=root)
-    assert p.returncode == 0 and " passed" in p.stdout, (p.stdout + p.stderr)[-1500:]
+    w = work[order]
+    assert (w[:-1] >= w[1:]).all() and w[0] == work.max()
 
 
 @pytest.mark.parametrize("stride,cin,cout,tile", [(4, 128, 128, None), (8, 256, 256, None), (1, 96, 96, 384), (2, 64, 64, 128)])
@@ -444,54 +418,6 @@ def test_skip_gradient_rides_in_the_dgrad_write_back(hip, levels):
         assert float((gw1 - gw0).abs().max()) <= 1e-6 * float(gw0.abs().max())
 
 
-@pytest.mark.parametrize("amp", [None, torch.bfloat16])
-def test_batchnorm_backward_statistics_from_the_dgrad_write_back(hip, levels, amp, monkeypatch):
-    """conv -> BatchNorm -> ReLU -> conv (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:31-129): the second convolution's dgrad
-    launch writes the BatchNorm's dy and leaves sum(g), sum(g xhat) per tile (pcs_conv_gather_gemm_*_ex, bn_x); the BatchNorm's
-    backward reduces those instead of running pcs_bn_bwd_stats_*. Same gradients as the statistics pass; a second consumer of
-    the activation (autograd then sums gradients) falls back to the pass."""
-    from openpcseg_amd import fused, modules as spnn, native
-    from openpcseg_amd.sparse import SparseTensor
-    coords = t(levels[4])
-    n = coords.shape[0]
-    torch.manual_seed(3)
-    c1, c2 = spnn.Conv3d(64, 96, 3).to(DEV), spnn.Conv3d(96, 64, 3).to(DEV)
-    bn = fused.FusedBatchNorm(96).to(DEV).train()
-    x0 = torch.randn(n, 64, device=DEV)
-    gy = torch.randn(n, 64, device=DEV)
-    calls = {"link": 0, "pass": 0}
-    be = native.backend()
-    real_link, real_pass = be.bn_bwd_reduce_partials, be.bn_bwd_stats
-    monkeypatch.setattr(be, "bn_bwd_reduce_partials", lambda *a, **k: (calls.__setitem__("link", calls["link"] + 1), real_link(*a, **k))[1])
-    monkeypatch.setattr(be, "bn_bwd_stats", lambda *a, **k: (calls.__setitem__("pass", calls["pass"] + 1), real_pass(*a, **k))[1])
-
-    def run(link, second_consumer=False):
-        monkeypatch.setattr(fused, "LINK_BN_BWD", link)
-        for m in (c1, c2, bn):
-            m.zero_grad(set_to_none=True)
-        x = x0.clone().requires_grad_(True)
-        with torch.autocast("cuda", dtype=amp, enabled=amp is not None):
-            h = bn(c1(SparseTensor(x, coords, 4)), relu=True)
-            out = c2(h).feats.float()
-            if second_consumer:
-                out = out + h.feats.float()[:, :64] * 0.5
-        out.backward(gy)
-        return [x.grad.clone()] + [p.grad.clone() for m in (c1, bn, c2) for p in m.parameters()]
-
-    base = run(False)
-    assert calls == {"link": 0, "pass": 1}
-    got = run(True)
-    assert calls == {"link": 1, "pass": 1}                      # the statistics came out of the dgrad write-back
-    tol = 2e-5 if amp is None else 2e-3
-    for a, b in zip(got, base):
-        assert float((a - b).abs().max()) <= tol * max(float(b.abs().max()), 1e-6)
-    both = run(True, second_consumer=True)
-    assert calls == {"link": 1, "pass": 2}                      # two consumers of the activation: the pass runs
-    ref = run(False, second_consumer=True)
-    for a, b in zip(both, ref):
-        assert float((a - b).abs().max()) <= tol * max(float(b.abs().max()), 1e-6)
-
-
 def _ws_mode(hip, mode):
     import ctypes
     f = hip.lib.pcs_debug_convh_ws
@@ -685,49 +611,6 @@ def test_conv_x3_nonfinite_inputs_follow_the_fp32_kernel(hip, levels):
     assert bool(torch.isnan(y3[nan_touched]).all()) and bool(torch.isnan(y32[nan_touched]).all())
     ok = ~touched
     assert float((y3[ok] - y32[ok]).abs().max()) <= 2e-5 * float(y32[ok].abs().max())
-
-
-def test_commit_variants_bit_identical(hip, levels):
-    """PCS_COMMIT_NOWAIT=0 / PCS_COMMIT_PHASED=0 (the fenced ticket hand-over and the compiler-interleaved commit kept behind
-    macros in conv_wave5.hip, conv_wave5h.hip and conv_wave5x.hip) produce the same bits as the default build: a variant
-    library is built here (hipcc is on the GPU box too) and both libraries run the same launches in subprocesses."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run(["bash", os.path.join(root, "tools", "build_variant_lib.sh"), "fenced", "-DPCS_COMMIT_NOWAIT=0",
-                        "-DPCS_COMMIT_PHASED=0"], capture_output=True, text=True, timeout=900)
-    lib = os.path.join(root, "openpcseg_amd", "lib", "dbg", "fenced.so")
-    if r.returncode != 0 or not os.path.exists(lib):
-        pytest.skip("variant library did not build here: " + r.stderr[-300:])
-    code = r"""
-import hashlib, sys, numpy as np, torch
-sys.path.insert(0, %r)
-from openpcseg_amd import functional as F, native
-from openpcseg_amd.workloads.synthetic import make_batch
-be = native.backend()
-c = make_batch([0], n_points=30000)["lidar"].C.cuda()
-c = c[torch.argsort(F.sphash(c))].contiguous()
-e = F.build_kernel_map(c, c, (3, 3, 3), (1, 1, 1), (1, 1, 1))
-torch.manual_seed(0)
-h = hashlib.sha256()
-for cin, cout in [(64, 64), (96, 96), (128, 96), (32, 32)]:
-    x = torch.randn(c.shape[0], cin, device="cuda"); w = torch.randn(27, cin, cout, device="cuda") * 0.05
-    h.update(be.conv_gather_gemm(x, w, e.fwd).cpu().numpy().tobytes())
-    if cin >= 64:
-        h.update(be.conv_gather_gemm_x3(x, be.prepare_weights_x3(w, transpose=False), 27, cout, e.fwd).cpu().numpy().tobytes())
-        xb = x.bfloat16()
-        h.update(be.conv_gather_gemm_h(xb, be.prepare_weights_h(w, torch.bfloat16, transpose=False), 27, cout, e.fwd).float().cpu().numpy().tobytes())
-print("HASH", h.hexdigest())
-""" % root
-    out = []
-    for extra in ({}, {"PCS_LIB_PATH": lib}):
-        env = dict(os.environ, **extra)
-        p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-800:]
-        out.append([l for l in p.stdout.splitlines() if l.startswith("HASH")][-1])
-    os.remove(lib)
-    assert out[0] == out[1]
 
 
 @pytest.mark.parametrize("amp", [None, torch.bfloat16])

@@ -32,7 +32,7 @@ def test_library_exports_every_declared_symbol():
                           capture_output=True, text=True).stdout
     exported = set(re.findall(r" T (pcs_[a-z0-9_]+)$", syms, re.M))
     assert exported and exported <= declared, exported - declared
-    assert lib.pcs_abi_version() == native.ABI_VERSION == 11
+    assert lib.pcs_abi_version() == native.ABI_VERSION == 12
     assert lib.pcs_hashtable_capacity(1000) == 2048
     assert lib.pcs_hashtable_bytes(2048) == 2048 * 12
     assert lib.pcs_conv_tile_rows(32, 32) in (64, 128)
@@ -68,20 +68,31 @@ def test_product_never_imports_oracle():
 
 def test_product_sources_hold_no_retired_kernels():
     """The column-parallel "ring" kernels of round 4 (0.47-0.70x the wave kernels, profiles/round4_ring.md) are retired: no
-    hook, stub header or export of them is left in the product sources, the C ABI or the built library; their text is kept as a
-    record under tools/experimental/csrc/*.txt (not compiled by anything)."""
+    hook, stub header or export of them is left in the product sources, the C ABI or the built library, and their parked text
+    is gone (git history keeps it). So are the variants that lost their A/B: the ds_add_f32 / fenced / interleaved commits of
+    the wave kernels (profiles/round3_commit_ab.txt) and the BatchNorm backward statistics in the dgrad write-back
+    (profiles/round6_bn_link_ab.txt)."""
     import subprocess
-    csrc = os.path.join(ROOT, "openpcseg_amd", "csrc")
+    pkg = os.path.join(ROOT, "openpcseg_amd")
+    csrc = os.path.join(pkg, "csrc")
     for f in os.listdir(csrc):
         assert not f.startswith("conv_ring"), f
         assert "conv_ring" not in open(os.path.join(csrc, f)).read() and "PCS_WITH_RING" not in open(os.path.join(csrc, f)).read(), f
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith((".py", ".hip", ".h")):
+                src = open(os.path.join(d, f)).read()
+                for name in ("PCS_COMMIT_", "gs_x", "BNLink"):
+                    assert name not in src, (f, name)
     hdr = open(os.path.join(ROOT, "include", "pcseg_hip.h")).read()
     assert "pcs_conv_ring_enable(" not in hdr and "pcs_conv_ring_applies(" not in hdr
-    assert all(f.endswith(".txt") for f in os.listdir(os.path.join(ROOT, "tools", "experimental", "csrc")))
-    lib = os.path.join(ROOT, "openpcseg_amd", "lib", "libpcseg_hip.so")
+    assert "bn_x" not in hdr and "pcs_bn_bwd_reduce_partials" not in hdr
+    assert not os.path.exists(os.path.join(ROOT, "tools", "experimental"))
+    lib = os.path.join(pkg, "lib", "libpcseg_hip.so")
     if os.path.exists(lib):
         syms = subprocess.run(["nm", "-D", lib], capture_output=True, text=True).stdout
         assert "pcs_conv_ring" not in syms and "conv_ring6" not in syms
+        assert "pcs_bn_bwd_reduce_partials" not in syms
 
 
 def test_reference_import_names():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B variant of the library: bash tools/build_variant_lib.sh <name> <-Dflags...>
-#   e.g. tools/build_variant_lib.sh rmw -DPCS_COMMIT_ATOMIC=0 ; tools/build_variant_lib.sh wait -DPCS_COMMIT_NOWAIT=0
+#   e.g. tools/build_variant_lib.sh nomfma -DPCS_ABLATE5=2
 # -> openpcseg_amd/lib/dbg/<name>.so: every conv*.hip recompiled with the flags (conv_common.h switches reach the launch
 # shape code too), the other objects of the product build linked as they are; select it with PCS_LIB_PATH.
 # Variant builds are never loaded by default and are removed before a round ends (they must not travel as product).
