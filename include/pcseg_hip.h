@@ -34,6 +34,8 @@ extern "C" {
 #define PCS_ELAUNCH (-3)  /* hipLaunch / hipMemsetAsync failed (pcs_last_error has text) */
 #define PCS_EUNSUPPORTED (-4)
 
+/* Still 12 after two additive changes: the `reserved` word of pcs_conv_epilogue became `flags` (PCS_EP_RELU; a zeroed struct
+ * means what it meant) and the prediction-tail export was added. A caller built against the earlier v12 header runs unchanged. */
 #define PCS_ABI_VERSION 12
 
 int pcs_abi_version(void);
@@ -253,13 +255,19 @@ int pcs_conv_gather_gemm_f32(const float *src, int64_t n_src, int32_t cin, const
  *            hands back rides in, instead of a separate elementwise sum of the two gradients (what autograd does around
  *            TS:torchsparse/backend/convolution/convolution_cuda.cu:167-278).
  * Shapes the wave kernels do not serve (pcs_conv_supports_epilogue() == 0) return PCS_EUNSUPPORTED when any extra is set.
- * ABI v12: the struct no longer carries the BatchNorm backward-statistics inputs between addend and act_slope. */
+ * ABI v12: the struct no longer carries the BatchNorm backward-statistics inputs between addend and act_slope.
+ * Still v12 (additive): the former `reserved` word is `flags`, same offset and size; a zero-initialised struct means
+ * what it meant. Order of the write-back: bias, then addend, then the activation. */
+#define PCS_EP_RELU 1   /* flags: the activation is ReLU, whatever act_slope holds */
 typedef struct pcs_conv_epilogue {
   const void *addend;
   float act_slope;   /* LeakyReLU fused into the write-back: dst = v < 0 ? v * act_slope : v, applied before the store and before the
                       * forward BatchNorm statistics (R:pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:88-190: conv -> LeakyReLU
                       * -> BatchNorm1d). 0 is read as 1 (no activation), so a zero-initialised struct is the plain call. */
-  int32_t reserved;
+  int32_t flags;     /* 0 or PCS_EP_RELU; any other bit is PCS_EINVAL. PCS_EP_RELU: the kernels run their LeakyReLU branch with slope
+                      * 0 (inference with BatchNorm folded into the weights: conv + bias + residual + ReLU in one launch). A negative
+                      * pre-activation therefore gives a zero of either sign (v * 0 = -0.0), and non-finite pre-activations are not
+                      * flushed (-inf * 0 = NaN); -0.0 == 0 in every comparison a consumer makes. */
 } pcs_conv_epilogue;
 int pcs_conv_gather_gemm_f32_ex(const float *src, int64_t n_src, int32_t cin, const float *W,
                                 int32_t K, int32_t cout, const int32_t *pairs, int32_t src_col,
@@ -525,6 +533,24 @@ int pcs_voxel_label_vote(const int64_t *inverse, const int64_t *labels, int64_t 
                          void *stream);
 int pcs_rows_argmax_gather_f32(const float *logits, int64_t m, int32_t c, const int64_t *inverse, int64_t n,
                                int64_t *out, void *stream);
+
+/* ---- prediction tail of an evaluation pass (csrc/predict.hip; added under ABI v12, additive) --------------------------
+ * The reference's eval tail (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:436-455, scoring R:infer.py:35-52) for a
+ * whole batch in one launch, no host synchronisation. logits: (m, c) rows of the batch, c <= 64. For point i of scene b
+ * (the b with point_offset[b] <= i < point_offset[b + 1]): row = row_offset[b] + inverse[i], inverse being the per-SCENE
+ * row index of the point. n_scenes = 0 (offsets ignored) = one scene spanning everything: row = inverse ? inverse[i] : i
+ * (inverse NULL needs n == m). A row outside its scene's range -- or a point outside every span -- sets bad_flag[0] |= 1
+ * (1 device int32, zeroed by the caller, never cleared here), gives pred = -1 and is not counted; the range is checked
+ * before any address is formed.
+ *   votes (n, c) or NULL : votes[i] += softmax(logits[row]) in fp32, maximum subtracted (the reference's return_tta
+ *                          output summed over passes); the score vector is then votes[i], else the logits row;
+ *   pred  (n) or NULL    : first arg-max of the score vector (lowest index on ties);
+ *   hist  (c, c) or NULL : hist[labels[i]][pred[i]] += 1 for labels in [0, c) (fast_hist's mask); needs labels (n).
+ *                          Accumulates (the caller zeroes it once): integer sums, exact and run-to-run identical. */
+int pcs_predict_points_f32(const float *logits, int64_t m, int32_t c, const int64_t *inverse, int64_t n,
+                           const int64_t *point_offset, const int64_t *row_offset, int32_t n_scenes,
+                           const int64_t *labels, float *votes, int64_t *pred, int64_t *hist, int32_t *bad_flag,
+                           void *stream);
 
 /* ---- all layers' weight preparation in one launch (ABI v7) ---------------------------------------------------------
  * pcs_transpose_kab_f32 (kind 0: dst (K, B, A) fp32 = per-offset transposed weights for dgrad) and

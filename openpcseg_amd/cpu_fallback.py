@@ -188,7 +188,14 @@ class TorchCpuBackend:
         return 128
 
     # -- convolution (TS:torchsparse/nn/functional/conv.py:67-79 semantics)
-    def conv_gather_gemm(self, src, weight, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True):
+    conv_epilogue_relu = True   # conv_gather_gemm takes the write-back extras of the HIP entry (addend, act_slope, relu)
+
+    def conv_supports_addend(self, cin, cout, k, dtype=0):
+        return dtype == 0
+
+    def conv_gather_gemm(self, src, weight, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True, addend=None,
+                         act_slope=None, relu=False):
+        """Write-back extras in the order of pcs_conv_epilogue: bias, then addend, then the activation (relu wins over act_slope)."""
         src, weight = _cpu(src, "input").float(), _cpu(weight, "weight").float()
         if src.shape[1] != weight.shape[1]:
             raise ValueError("Input feature size and kernel size mismatch")
@@ -198,7 +205,17 @@ class TorchCpuBackend:
             if ko[k + 1] > ko[k]:
                 p = pr[ko[k]:ko[k + 1]]
                 out.index_add_(0, p[:, 1], src[p[:, 0]] @ weight[k])
-        return out + bias if bias is not None else out
+        if bias is not None:
+            out = out + bias
+        if addend is not None:
+            if tuple(addend.shape) != tuple(out.shape):
+                raise ValueError("addend %s does not match the output %s" % (tuple(addend.shape), tuple(out.shape)))
+            out = out + _cpu(addend, "addend").float()
+        if relu:
+            out = torch.relu(out)
+        elif act_slope is not None and act_slope not in (0.0, 1.0):
+            out = torch.where(out < 0, out * float(act_slope), out)
+        return out
 
     def conv_wgrad(self, fa, fb, kmap, a_col, split=False):
         fa, fb = _cpu(fa, "input").float(), _cpu(fb, "grad_output").float()

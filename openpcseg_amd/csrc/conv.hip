@@ -208,6 +208,8 @@ extern "C" int pcs_conv_gather_gemm_f32_ex(const float *src, int64_t n_src, int3
   a.addend = addend;
   if (addend && ((uintptr_t)addend & 15)) { set_error("pcs_conv_gather_gemm_f32_ex: misaligned addend"); return PCS_EINVAL; }
   if (ep && ep->act_slope != 0.f && ep->act_slope != 1.f) a.act_slope = ep->act_slope;
+  if (ep && (ep->flags & ~PCS_EP_RELU)) { set_error("pcs_conv_gather_gemm_f32_ex: unknown pcs_conv_epilogue.flags bits"); return PCS_EINVAL; }
+  if (ep && (ep->flags & PCS_EP_RELU)) a.act_slope = 0.f;   // ReLU = the kernels' LeakyReLU branch with slope 0
   if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, 0)) {
     set_error("pcs_conv_gather_gemm_f32: this shape / tile height does not produce BatchNorm partials (ask pcs_conv_emits_bn_partials)");
     return PCS_EUNSUPPORTED;

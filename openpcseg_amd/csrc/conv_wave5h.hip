@@ -593,6 +593,8 @@ extern "C" int pcs_conv_gather_gemm_h_ex(const void *src, int64_t n_src, int32_t
   a.addend = reinterpret_cast<const uint16_t *>(addend);
   if (addend && ((uintptr_t)addend & 7)) { set_error("pcs_conv_gather_gemm_h_ex: misaligned addend"); return PCS_EINVAL; }
   if (ep && ep->act_slope != 0.f && ep->act_slope != 1.f) a.act_slope = ep->act_slope;
+  if (ep && (ep->flags & ~PCS_EP_RELU)) { set_error("pcs_conv_gather_gemm_h_ex: unknown pcs_conv_epilogue.flags bits"); return PCS_EINVAL; }
+  if (ep && (ep->flags & PCS_EP_RELU)) a.act_slope = 0.f;   // ReLU = the kernels' LeakyReLU branch with slope 0
   if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, dtype)) {
     set_error("pcs_conv_gather_gemm_h: this shape / tile height does not produce BatchNorm partials");
     return PCS_EUNSUPPORTED;

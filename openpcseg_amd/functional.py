@@ -26,7 +26,7 @@ from . import native
 from .sparse import SparseTensor, get_kernel_offsets, make_ntuple
 
 __all__ = ["sphash", "sphashquery", "spcount", "spvoxelize", "spdevoxelize", "calc_ti_weights",
-           "spdownsample", "prebuild_coords", "conv3d", "relu", "leaky_relu"]
+           "spdownsample", "prebuild_coords", "conv3d", "conv3d_inference", "relu", "leaky_relu"]
 
 
 def _be():
@@ -569,28 +569,16 @@ def prebuild_coords(x, steps):
     return x
 
 
-def conv3d(input, weight, kernel_size, bias=None, stride=1, dilation=1, transposed=False, bn_stats=False, with_skip=False,
-           act_slope=None):
-    """bn_stats (not in the reference's signature; used by the fused blocks): ask the convolution for the BatchNorm
-    statistics of its output; they are attached to the returned tensor as `.bn_sums` when the kernel produced them.
-    with_skip (likewise): return (output, skip) where skip is the INPUT tensor again, routed through the convolution's autograd
-    node: a caller that also feeds the input to a residual / skip path uses `skip` there, and the two gradients of the input
-    are summed inside the dgrad kernel's write-back (see _SparseConv)."""
-    skip_feats = None
+def _conv_geometry(input, kernel_size, stride, dilation, transposed):
+    """-> (output stride, output coordinates, KmapEntry or None for a 1x1x1 convolution): the coordinate / kernel-map part of
+    conv3d (TS:torchsparse/nn/functional/conv.py:135-176), shared with conv3d_inference. Fills input.cmaps / input.kmaps."""
     kernel_size = make_ntuple(kernel_size, ndim=3)
     stride = make_ntuple(stride, ndim=3)
     dilation = make_ntuple(dilation, ndim=3)
     ones = (1, 1, 1)
-    bn_sums = None
-
     if kernel_size == ones and stride == ones and dilation == ones:
-        output_stride = input.stride
-        output_coords = input.coords
-        if input.feats.is_cuda and weight.dim() == 2:
-            output_feats = _PointwiseConv.apply(input.feats, weight, input.kmaps)
-        else:
-            output_feats = input.feats.matmul(weight)
-    elif not transposed:
+        return input.stride, input.coords, None
+    if not transposed:
         output_stride = tuple(input.stride[k] * stride[k] for k in range(3))
         if output_stride in input.cmaps:
             output_coords = input.cmaps[output_stride]
@@ -602,18 +590,33 @@ def conv3d(input, weight, kernel_size, bias=None, stride=1, dilation=1, transpos
         if key not in input.kmaps:
             input.kmaps[key] = build_kernel_map(input.coords, output_coords, kernel_size,
                                                 input.stride, dilation)
-        if with_skip:
-            output_feats, bn_sums, skip_feats = _sparse_conv(input.feats, weight, input.kmaps[key], False, bn_stats and bias is None, True, act_slope)
+        return output_stride, output_coords, input.kmaps[key]
+    output_stride = tuple(input.stride[k] // stride[k] for k in range(3))
+    output_coords = input.cmaps[output_stride]
+    key = (output_stride, kernel_size, stride, dilation)
+    return output_stride, output_coords, input.kmaps[key]
+
+
+def conv3d(input, weight, kernel_size, bias=None, stride=1, dilation=1, transposed=False, bn_stats=False, with_skip=False,
+           act_slope=None):
+    """bn_stats (not in the reference's signature; used by the fused blocks): ask the convolution for the BatchNorm
+    statistics of its output; they are attached to the returned tensor as `.bn_sums` when the kernel produced them.
+    with_skip (likewise): return (output, skip) where skip is the INPUT tensor again, routed through the convolution's autograd
+    node: a caller that also feeds the input to a residual / skip path uses `skip` there, and the two gradients of the input
+    are summed inside the dgrad kernel's write-back (see _SparseConv)."""
+    skip_feats = None
+    bn_sums = None
+    output_stride, output_coords, entry = _conv_geometry(input, kernel_size, stride, dilation, transposed)
+
+    if entry is None:
+        if input.feats.is_cuda and weight.dim() == 2:
+            output_feats = _PointwiseConv.apply(input.feats, weight, input.kmaps)
         else:
-            output_feats, bn_sums = _sparse_conv(input.feats, weight, input.kmaps[key], False, bn_stats and bias is None, False, act_slope)
+            output_feats = input.feats.matmul(weight)
+    elif with_skip:
+        output_feats, bn_sums, skip_feats = _sparse_conv(input.feats, weight, entry, bool(transposed), bn_stats and bias is None, True, act_slope)
     else:
-        output_stride = tuple(input.stride[k] // stride[k] for k in range(3))
-        output_coords = input.cmaps[output_stride]
-        key = (output_stride, kernel_size, stride, dilation)
-        if with_skip:
-            output_feats, bn_sums, skip_feats = _sparse_conv(input.feats, weight, input.kmaps[key], True, bn_stats and bias is None, True, act_slope)
-        else:
-            output_feats, bn_sums = _sparse_conv(input.feats, weight, input.kmaps[key], True, bn_stats and bias is None, False, act_slope)
+        output_feats, bn_sums = _sparse_conv(input.feats, weight, entry, bool(transposed), bn_stats and bias is None, False, act_slope)
 
     if bias is not None:
         output_feats += bias
@@ -630,6 +633,93 @@ def conv3d(input, weight, kernel_size, bias=None, stride=1, dilation=1, transpos
             pass
     if with_skip:
         return output, input._like(skip_feats if skip_feats is not None else input.feats)
+    return output
+
+
+def _memo(cache, key, make):
+    if cache is None:
+        return make()
+    if key not in cache:
+        cache[key] = make()
+    return cache[key]
+
+
+def conv3d_inference(input, weight, bias, kernel_size, stride=1, dilation=1, transposed=False, addend=None, relu=False,
+                     prepared=None):
+    """Forward-only convolution of the inference path (openpcseg_amd.inference): act(conv(x, weight) + bias [+ addend]) in ONE
+    launch -- the write-back of the fused gather-GEMM applies bias, addend and ReLU (pcs_conv_epilogue, PCS_EP_RELU). No autograd.
+    weight: fp32 (K, cin, cout) or (cin, cout), typically a convolution's kernel with the BatchNorm that follows folded in; bias
+    fp32 (cout) or None; addend: a tensor / SparseTensor on the output coordinates (the residual), handed over in dst's dtype.
+    The kernel is picked by the rules of _SparseConv.forward: the half kernel under autocast where conv_h_applies, else fp32
+    (rounded to the autocast dtype); a 1x1x1 convolution runs on the gather-GEMM over the identity map like fused._SkinnyLinear.
+    Where the kernel takes no write-back extras (generic shapes, the bf16x3 policy, zero-padded odd widths, a backend without
+    `conv_epilogue_relu`), the kernel adds the bias and torch adds / clamps in place: still no BatchNorm launch.
+    prepared: a dict owned by the caller that keeps the derived weight copies (fragment-ordered half weights per dtype) and the
+    shape queries' answers for as long as `weight` is current; with it a forward after the first prepares nothing."""
+    be = _be()
+    feats = input.feats
+    if isinstance(addend, SparseTensor):
+        addend = addend.feats
+    output_stride, output_coords, entry = _conv_geometry(input, kernel_size, stride, dilation, transposed)
+    w3 = weight if weight.dim() == 3 else weight.unsqueeze(0)
+    k, cin, cout = w3.shape
+    hd = _amp_dtype(feats)
+    if entry is not None:
+        kmap = entry.rev if transposed else entry.fwd
+    elif feats.is_cuda:
+        kmap = _identity_map(feats.shape[0], feats.device, input.kmaps)
+    else:
+        kmap = None   # host backends: a 1x1x1 convolution is a matrix product
+    pin, pout = _channel_padding(feats, w3)
+    epilogue = bool(getattr(be, "conv_epilogue_relu", False)) and hasattr(be, "conv_supports_addend") and not (pin or pout)
+    fused = False
+    if kmap is None:
+        out = feats.float().matmul(w3[0].float())
+        if bias is not None:
+            out = out + bias
+    elif pin or pout:
+        x = torch.nn.functional.pad(feats, (0, pin)) if pin else feats
+        wpad = _memo(prepared, ("pad", pin, pout), lambda: torch.nn.functional.pad(w3.float(), (0, pout, 0, pin)).contiguous())
+        bpad = None if bias is None else _memo(prepared, ("bpad", pout), lambda: torch.nn.functional.pad(bias.float(), (0, pout)))
+        if hd is not None and be.conv_h_applies(cin + pin, cout + pout, k):
+            wp = _memo(prepared, ("padh", hd, pin, pout), lambda: be.prepare_weights_h(wpad, hd, transpose=False))
+            out = be.conv_gather_gemm_h(x.contiguous().to(hd), wp, k, cout + pout, kmap, bias=bpad)
+        else:
+            out = be.conv_gather_gemm(x.contiguous().float(), wpad, kmap, bias=bpad)
+        out = out[:, :cout].contiguous() if pout else out
+    elif hd is not None and feats.is_cuda and _memo(prepared, ("h?", hd), lambda: be.conv_h_applies(cin, cout, k)):
+        wp = _memo(prepared, (hd,), lambda: be.prepare_weights_h(w3.float().contiguous(), hd, transpose=False))
+        kw = {}
+        fused = epilogue and (not (relu or addend is not None) or
+                              _memo(prepared, ("epilogue?", hd), lambda: be.conv_supports_addend(cin, cout, k, be._HALF[hd])))
+        if fused and addend is not None:
+            kw["addend"] = addend.to(hd)
+        if fused and relu:
+            kw["relu"] = True
+        out = be.conv_gather_gemm_h(feats.contiguous().to(hd), wp, k, cout, kmap, bias=bias, **kw)
+    elif hd is None and feats.is_cuda and _CONV_POLICY["mode"] == "bf16x3" and be.conv_x3_applies(cin, cout, k):
+        wp = _memo(prepared, ("x3",), lambda: be.prepare_weights_x3(w3.float().contiguous(), transpose=False))
+        out = be.conv_gather_gemm_x3(feats.contiguous().float(), wp, k, cout, kmap, bias=bias)   # this entry has no epilogue
+    else:
+        kw = {}
+        fused = epilogue and (not (relu or addend is not None) or
+                              _memo(prepared, ("epilogue?", None), lambda: be.conv_supports_addend(cin, cout, k, 0)))
+        if fused and addend is not None:
+            kw["addend"] = addend.float()
+        if fused and relu:
+            kw["relu"] = True
+        out = be.conv_gather_gemm(feats.contiguous().float(), w3.float().contiguous(), kmap, bias=bias, **kw)
+    if not fused:
+        if addend is not None:
+            out = out.add_(addend.to(out.dtype))
+        if relu:
+            out = out.relu_()
+    if hd is not None and out.dtype != hd:
+        out = out.to(hd)
+    output = SparseTensor(coords=output_coords, feats=out, stride=output_stride)
+    output.cmaps = input.cmaps
+    output.cmaps.setdefault(output_stride, output_coords)
+    output.kmaps = input.kmaps
     return output
 
 

@@ -1,0 +1,354 @@
+"""Inference mode: BatchNorm folded into the convolutions, and the prediction tail on the device.
+
+    openpcseg_amd.freeze(model)           # opt-in; model.eval() + torch.no_grad() / inference_mode() then take the folded path
+    ev = SegEvaluator(num_class)
+    for batch in loader:
+        model.predict(batch, evaluator=ev)        # workloads.minkunet.MinkUNet.predict
+    hist, iou, miou = ev.compute()                # the only device-to-host copy
+
+In eval mode a BatchNorm is a per-column affine map, so every `conv -> BatchNorm (-> + residual) (-> ReLU)` chain of the
+package's own blocks becomes ONE launch of the fused gather-GEMM:
+
+    s  = gamma / sqrt(running_var + eps)      (float64, as FusedBatchNorm's eval branch computes its inverse deviation)
+    W' = W * s[None, None, :]  -> fp32        b' = beta - running_mean * s (+ conv.bias * s)  -> fp32
+    y  = act(conv(x, W') + b' [+ residual])   bias, addend and ReLU in the write-back (pcs_conv_epilogue, PCS_EP_RELU)
+
+The fold is plain torch arithmetic on the device, done once per weight version (no host read-back); the folded tensors
+are ordinary attributes of a record beside the module, so `state_dict()` and the parameter lists are what they were. The
+folded path is taken only while the module is frozen, in eval mode and grad mode is off (it has no autograd): `model.train()`
+needs no `unfreeze`. A record remembers the version counters (and storage addresses) of the kernel, the conv bias and the
+BatchNorm's weight / bias / running statistics and re-folds lazily when any of them changed (`load_state_dict`, an optimizer
+step between two evaluations). The half kernels' fragment-ordered copies of W' live in the same record, so a frozen forward
+after the first launches no weight preparation.
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from . import functional as F
+from . import modules as spnn
+from . import native
+from .fused import FusedBatchNorm, FusedLinear
+from .sparse import SparseTensor
+
+__all__ = ["freeze", "unfreeze", "FoldedConv", "SegEvaluator", "point_predict"]
+
+_NORMS = (FusedBatchNorm, nn.BatchNorm1d)   # spnn.BatchNorm and the workloads' _BN / _SyncBN are BatchNorm1d / SyncBatchNorm
+_ATTR = "_pcs_folds"
+
+
+def _is_norm(m):
+    return isinstance(m, _NORMS) or isinstance(m, nn.SyncBatchNorm)
+
+
+def _foldable(conv, bn):
+    return (isinstance(conv, spnn.Conv3d) and _is_norm(bn) and getattr(bn, "running_mean", None) is not None and
+            getattr(bn, "running_var", None) is not None and conv.out_channels == bn.num_features)
+
+
+class FoldedConv:
+    """conv + the BatchNorm that follows it as one convolution with bias; `relu`: the chain ends in a ReLU."""
+
+    def __init__(self, conv, bn, relu):
+        self.conv, self.bn, self.relu = conv, bn, bool(relu)
+        self._stamp = None
+        self.weight = self.bias = None
+        self.prepared = {}   # derived copies of `weight` (functional.conv3d_inference), dropped with it
+        self.folds = 0       # how often the arithmetic ran (tests)
+
+    def _sources(self):
+        c, b = self.conv, self.bn
+        return [c.kernel, c.bias, getattr(b, "weight", None), getattr(b, "bias", None), b.running_mean, b.running_var]
+
+    def _current(self):
+        stamp = []
+        for t in self._sources():
+            if t is None:
+                stamp.append(None)
+                continue
+            try:
+                stamp.append((t._version, t.data_ptr(), t.device, t.dtype))
+            except RuntimeError:   # inference tensors track no version counter: fold on every call
+                return None
+        return tuple(stamp)
+
+    def folded(self):
+        """-> (W' fp32, b' fp32, the dict of derived copies), re-folded when a source tensor changed."""
+        stamp = self._current()
+        if stamp is None or stamp != self._stamp:
+            kernel, cbias, gamma, beta, mean, var = self._sources()
+            with torch.no_grad():
+                s = torch.rsqrt(var.detach().double() + self.bn.eps)
+                if gamma is not None:
+                    s = gamma.detach().double() * s
+                shift = -mean.detach().double() * s
+                if beta is not None:
+                    shift = shift + beta.detach().double()
+                if cbias is not None:
+                    shift = shift + cbias.detach().double() * s
+                self.weight = (kernel.detach().double() * s).float().contiguous()
+                self.bias = shift.float().contiguous()
+            self.prepared = {}
+            self._stamp = stamp
+            self.folds += 1
+        return self.weight, self.bias, self.prepared
+
+    def __call__(self, x, residual=None):
+        w, b, prepared = self.folded()
+        c = self.conv
+        return F.conv3d_inference(x, w, b, c.kernel_size, stride=c.stride, dilation=c.dilation, transposed=c.transposed,
+                                  addend=residual, relu=self.relu, prepared=prepared)
+
+
+class FoldedLinear:
+    """The classifier's column blocks (FusedLinear.devoxelized_part) as (1, cin, cout) gather-GEMM weights, kept -- with their
+    fragment-ordered half copies -- per weight version instead of being transposed and prepared on every forward. Same kernels
+    on the same values as fused._SkinnyLinear.forward: the logits are bit-identical to the unfrozen classifier's."""
+
+    def __init__(self, lin):
+        self.lin, self._stamp, self.parts = lin, None, {}
+
+    def devoxelized_part(self, col, xf, idx, wts, cache=None):
+        lin = self.lin
+        cin, cout = xf.shape[1], lin.out_features
+        ok = (cache is not None and xf.is_cuda and xf.dim() == 2 and xf.dtype in (torch.float32, torch.bfloat16, torch.float16) and
+              xf.shape[0] >= 4096 and cin % 4 == 0 and cout % 4 == 0)
+        if not ok:
+            return lin.devoxelized_part(col, xf, idx, wts, cache=cache)
+        w = lin.weight
+        try:
+            stamp = (w._version, w.data_ptr(), w.device, w.dtype)
+        except RuntimeError:
+            stamp = None
+        if stamp is None or stamp != self._stamp:
+            self.parts, self._stamp = {}, stamp
+        part = self.parts.setdefault((col, cin), {})
+        w1 = F._memo(part, "w", lambda: w.detach()[:, col:col + cin].float().t().contiguous().unsqueeze(0))
+        be = native.backend()
+        km = F._identity_map(xf.shape[0], xf.device, cache)
+        hd = xf.dtype if xf.dtype != torch.float32 else None
+        if hd is not None and be.conv_h_applies(cin, cout, 1):
+            wp = F._memo(part, hd, lambda: be.prepare_weights_h(w1, hd, transpose=False))
+            v = be.conv_gather_gemm_h(xf.contiguous(), wp, 1, cout, km)
+        else:
+            v = be.conv_gather_gemm(xf.contiguous().float(), w1, km)
+            if hd is not None:
+                v = v.to(hd)
+        return F.spdevoxelize(v.float(), idx, wts)
+
+
+def active(module):
+    """The fold records of `module` when the folded path applies to this call (frozen, eval mode, grad mode off), else None."""
+    rec = module.__dict__.get(_ATTR)
+    if rec is None or module.training or torch.is_grad_enabled():
+        return None
+    return rec
+
+
+def _groups(seq):
+    """A Sequential made only of [Conv3d, BatchNorm (, ReLU)] groups -> [(conv, bn, relu)], else None."""
+    mods, out, i = list(seq), [], 0
+    while i < len(mods):
+        if i + 1 >= len(mods) or not _foldable(mods[i], mods[i + 1]):
+            return None
+        relu = i + 2 < len(mods) and isinstance(mods[i + 2], (spnn.ReLU, nn.ReLU)) and not isinstance(mods[i + 2], nn.LeakyReLU)
+        out.append((mods[i], mods[i + 1], relu))
+        i += 3 if relu else 2
+    return out or None
+
+
+class _SequentialForward:
+    """`forward` of a frozen plain Sequential (an instance attribute, so the class and its state_dict stay what they were;
+    a class rather than a closure so that the module still pickles)."""
+
+    def __init__(self, seq):
+        self.seq = seq
+
+    def __call__(self, x):
+        rec = active(self.seq)
+        if rec is None or not isinstance(x, SparseTensor):
+            return type(self.seq).forward(self.seq, x)
+        for f in rec["chain"]:
+            x = f(x)
+        return x
+
+
+def freeze(model):
+    """Fold every BatchNorm of the package's own blocks (workloads.minkunet: the stem, ConvBlock, ResBlock incl. its 1x1x1
+    downsample) and of plain `nn.Sequential(Conv3d, BatchNorm [, ReLU], ...)` chains into its convolution. Anything else is
+    left alone. -> {"folded": number of conv + BatchNorm pairs, "skipped": [names of BatchNorm modules that keep running]}.
+    Changes no parameter, buffer or state_dict entry; takes effect only in eval mode with grad mode off."""
+    from .workloads.minkunet import ConvBlock, MinkUNet, ResBlock
+    unfreeze(model)
+    claimed, folded = set(), 0
+
+    def claim(owner, rec, pairs):
+        nonlocal folded
+        owner.__dict__[_ATTR] = rec
+        for conv, bn in pairs:
+            claimed.add(id(bn))
+            folded += 1
+
+    for m in model.modules():
+        if isinstance(m, ResBlock):
+            ds = m.downsample
+            has_ds = isinstance(ds, nn.Sequential) and len(ds) == 2 and _foldable(ds[0], ds[1])
+            if not (_foldable(m.net[0], m.net[1]) and _foldable(m.net[3], m.net[4]) and (has_ds or isinstance(ds, nn.Identity))):
+                continue
+            rec = {"a": FoldedConv(m.net[0], m.net[1], True), "b": FoldedConv(m.net[3], m.net[4], True),
+                   "ds": FoldedConv(ds[0], ds[1], False) if has_ds else None}
+            claim(m, rec, [(m.net[0], m.net[1]), (m.net[3], m.net[4])] + ([(ds[0], ds[1])] if has_ds else []))
+            claimed.update(id(s) for s in (m.net, ds))
+        elif isinstance(m, ConvBlock):
+            if _foldable(m.net[0], m.net[1]):
+                claim(m, {"net": FoldedConv(m.net[0], m.net[1], True)}, [(m.net[0], m.net[1])])
+                claimed.add(id(m.net))
+        elif isinstance(m, MinkUNet):
+            st = m.stem
+            if _foldable(st[0], st[1]) and _foldable(st[3], st[4]):
+                rec = {"stem": [FoldedConv(st[0], st[1], True), FoldedConv(st[3], st[4], True)],
+                       "classifier": FoldedLinear(m.classifier[0]) if isinstance(m.classifier[0], FusedLinear) else None}
+                claim(m, rec, [(st[0], st[1]), (st[3], st[4])])
+                claimed.add(id(st))
+    for m in model.modules():
+        if isinstance(m, nn.Sequential) and type(m).forward is nn.Sequential.forward and id(m) not in claimed:
+            groups = _groups(m)
+            if groups:
+                claim(m, {"chain": [FoldedConv(c, b, r) for c, b, r in groups]}, [(c, b) for c, b, _ in groups])
+                m.__dict__["forward"] = _SequentialForward(m)
+    skipped = [name for name, m in model.named_modules() if _is_norm(m) and id(m) not in claimed]
+    return {"folded": folded, "skipped": skipped}
+
+
+def unfreeze(model):
+    """Drop every fold record `freeze` attached below `model` (the modules run their BatchNorm layers again). -> how many."""
+    n = 0
+    for m in model.modules():
+        rec = m.__dict__.pop(_ATTR, None)
+        if rec is not None:
+            n += 1
+            if "chain" in rec:
+                m.__dict__.pop("forward", None)
+    return n
+
+
+# ---- prediction tail ------------------------------------------------------------------------------------------------
+def _scene_offsets(batch_col, n_scenes):
+    """(n_scenes + 1) int64 prefix offsets of the rows of each scene, from the batch column; on the device, no read-back."""
+    col = batch_col.long().clamp(0, n_scenes - 1)
+    counts = torch.zeros(n_scenes + 1, dtype=torch.int64, device=col.device)
+    counts.scatter_add_(0, col + 1, torch.ones_like(col))
+    return torch.cumsum(counts, 0)
+
+
+def point_predict(logits, batch, votes=None, hist=None, bad=None):
+    """The reference's eval tail (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:436-455) for the whole batch in one
+    launch: point_predict = logits[rows of scene b][inverse_map of scene b][:num_points[b]].argmax(1), scenes concatenated.
+    batch: "lidar" (SparseTensor, coords (m, 4), batch index last, scenes in order as sparse_collate_fn leaves them),
+    "inverse_map" (SparseTensor: F (n,) per-scene row of every point, C batch index last), optional "targets_mapped" (F (n,)
+    labels), optional "num_points" (host, per scene). The number of scenes comes from the host side of the batch.
+    votes (sum kept points, c) fp32: += softmax of every point's row, then decides (the reference's return_tta, summed);
+    hist (c, c) int64: += confusion counts of labels in [0, c). -> (pred (sum kept points,) int64 on the device, host list of the
+    (n_scenes + 1) offsets into it, bad flag (1,) int32 on the device: an inverse index pointed outside its scene)."""
+    be = native.backend()
+    logits = logits.float().contiguous()
+    dev = logits.device
+    inv = batch["inverse_map"]
+    inverse = inv.F.to(dev).long().reshape(-1)
+    labels = batch["targets_mapped"].F.to(dev).long().reshape(-1) if batch.get("targets_mapped") is not None else None
+    n = inverse.numel()
+    num_points = batch.get("num_points")
+    if num_points is not None:
+        if isinstance(num_points, torch.Tensor):
+            num_points = num_points.cpu()   # host data in every loader of the reference; a device tensor costs a read-back
+        num_points = [int(v) for v in np.asarray(num_points).reshape(-1)]
+        ns = len(num_points)
+    elif batch.get("offset") is not None:
+        ns, num_points = len(batch["offset"]), None
+    else:
+        raise ValueError("openpcseg_amd: the batch needs `num_points` or `offset` (the number of scenes, known on the host)")
+    row_offset = _scene_offsets(batch["lidar"].C.to(dev)[:, -1], ns)
+    if num_points is None or sum(num_points) == n:
+        # every scene keeps all its points (`[:num_points[idx]]` cuts nothing)
+        if num_points is None:
+            point_offset = _scene_offsets(inv.C.to(dev)[:, -1], ns)
+            kept = None
+        else:
+            kept = [0] + np.cumsum(num_points).tolist()
+            point_offset = native._h2d(kept, torch.int64, dev) if dev.type == "cuda" else torch.tensor(kept, dtype=torch.int64)
+    else:
+        # shortened spans: point j of scene b's kept prefix is point start[b] + j of the batch; all sizes known on the host
+        kept = [0] + np.cumsum(num_points).tolist()
+        start = _scene_offsets(inv.C.to(dev)[:, -1], ns)
+        scene = torch.repeat_interleave(torch.arange(ns), torch.tensor(num_points)).to(dev)
+        kept_dev = torch.tensor(kept, dtype=torch.int64).to(dev)
+        src = torch.arange(kept[-1], device=dev) - kept_dev[scene] + start[scene]
+        inside = src < start[scene + 1]           # a scene with fewer points than num_points says: refused, not read
+        src = src.clamp(max=max(n - 1, 0))
+        inverse = torch.where(inside, inverse[src], torch.full_like(src, -1))
+        labels = labels[src] if labels is not None else None
+        point_offset = kept_dev
+    pred, bad = be.predict_points(logits, inverse=inverse, point_offset=point_offset, row_offset=row_offset,
+                                  labels=labels if hist is not None else None, votes=votes, hist=hist, bad=bad)
+    return pred, kept, bad
+
+
+class SegEvaluator:
+    """Confusion matrix of an evaluation run, kept on the device: `update` per batch (no host synchronisation), `compute` once.
+    num_class = the width of the logits; unique_label as in the reference's trainer (R:train.py:226-230: class 0 is `ignore`,
+    label k + 1 is evaluated class k), default range(num_class - 1)."""
+
+    def __init__(self, num_class, unique_label=None):
+        self.num_class = int(num_class)
+        self.unique_label = np.asarray(list(range(self.num_class - 1)) if unique_label is None else unique_label, dtype=np.int64)
+        if self.unique_label.size == 0 or self.unique_label.min() < 0 or int(self.unique_label.max()) + 2 > self.num_class:
+            raise ValueError("openpcseg_amd: unique_label + 1 must index classes of the (num_class, num_class) histogram")
+        self.hist = None   # (num_class, num_class) int64 on the device of the first update
+        self.bad = None    # (1,) int32: some inverse index pointed outside its scene (that point was not counted)
+
+    def _ensure(self, device):
+        if self.hist is None:
+            with torch.inference_mode(False):   # ordinary tensors also when first used inside MinkUNet.predict (merge adds in place)
+                self.hist = torch.zeros((self.num_class, self.num_class), dtype=torch.int64, device=device)
+                self.bad = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def update(self, logits, batch, votes=None):
+        """hist[label][pred] += 1 over the batch's points (labels: batch["targets_mapped"]). -> pred (flat, on the device)."""
+        if logits.shape[1] != self.num_class:
+            raise ValueError("openpcseg_amd: %d logit columns for a %d-class evaluator" % (logits.shape[1], self.num_class))
+        if batch.get("targets_mapped") is None:
+            raise ValueError("openpcseg_amd: SegEvaluator.update needs batch['targets_mapped']")
+        self._ensure(logits.device)
+        pred, self.last_offsets, _ = point_predict(logits, batch, votes=votes, hist=self.hist, bad=self.bad)
+        return pred
+
+    def merge(self, other):
+        """Add another evaluator's counts (what a multi-rank evaluation would all-reduce)."""
+        if other.hist is not None:
+            self._ensure(other.hist.device)
+            self.hist += other.hist.to(self.hist.device)
+            self.bad |= other.bad.to(self.bad.device)
+        return self
+
+    @staticmethod
+    def metrics(hist, unique_label):
+        """(cropped histogram, per-class IoU, mIoU) from a full (c, c) histogram: fast_hist_crop + per_class_iu + nanmean
+        (R:infer.py:43-52, R:train.py:459-465), in NumPy on the host."""
+        hist = np.asarray(hist)
+        n = int(np.max(unique_label)) + 2
+        h = hist[:n, :n]
+        h = h[unique_label + 1, :]
+        h = h[:, unique_label + 1]
+        iou = np.diag(h) / (h.sum(1) + h.sum(0) - np.diag(h) + 1e-9)
+        return h, iou, float(np.nanmean(iou))
+
+    def compute(self):
+        """-> (cropped histogram (int64), per-class IoU, mIoU as a fraction): the one device-to-host copy of the run."""
+        if self.hist is None:
+            raise RuntimeError("openpcseg_amd: SegEvaluator.compute before any update")
+        host = torch.cat([self.hist.reshape(-1), self.bad.long()]).cpu().numpy()
+        self.saw_bad = bool(host[-1])
+        if self.saw_bad:
+            import warnings
+            warnings.warn("openpcseg_amd: inverse_map entries pointed outside their scene's rows; those points were not counted")
+        return self.metrics(host[:-1].reshape(self.num_class, self.num_class), self.unique_label)

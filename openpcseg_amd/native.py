@@ -112,6 +112,7 @@ SIGNATURES = {
     "pcs_cylinder_partition_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "pcs_voxel_label_vote": (c_int32, [_P, _P, c_int64, c_int64, c_int32, c_int64, _P, _P, _P, _P]),
     "pcs_rows_argmax_gather_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P]),
+    "pcs_predict_points_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
     "pcs_weights_multi_plan": (c_int64, [_P, c_int32]),
     "pcs_weights_multi": (c_int32, [_P, c_int32, c_int64, _P]),
     "pcs_lovasz_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int64]),
@@ -125,7 +126,7 @@ class _WeightJob(ctypes.Structure):   # pcs_weight_job of include/pcseg_hip.h
                 ("transpose", c_int32), ("nctt", c_int32), ("nt16", c_int32), ("ns", c_int32), ("first_block", c_int64)]
 
 
-ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
+ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
 _lib = None
 
 
@@ -637,13 +638,16 @@ class HipBackend:
         return bool(self.lib.pcs_conv_emits_bn_partials(cin, cout, k, self.tile_rows(cin, cout, kmap, code), code))
 
     class _Epilogue(ctypes.Structure):   # include/pcseg_hip.h: pcs_conv_epilogue
-        _fields_ = [("addend", ctypes.c_void_p), ("act_slope", ctypes.c_float), ("reserved", ctypes.c_int32)]
+        _fields_ = [("addend", ctypes.c_void_p), ("act_slope", ctypes.c_float), ("flags", ctypes.c_int32)]
 
-    def _epilogue(self, addend, kmap, cout, dtype, act_slope=None):
+    EP_RELU = 1                 # include/pcseg_hip.h: PCS_EP_RELU
+    conv_epilogue_relu = True   # the conv entries take relu=True (ReLU in the write-back); the inference path asks for it
+
+    def _epilogue(self, addend, kmap, cout, dtype, act_slope=None, relu=False):
         """-> (ctypes pointer or None, keep-alive tuple) for the _ex entries."""
-        if addend is None and act_slope is None:
+        if addend is None and act_slope is None and not relu:
             return None, None
-        ep = self._Epilogue(None, float(act_slope) if act_slope is not None else 0.0, 0)
+        ep = self._Epilogue(None, float(act_slope) if act_slope is not None else 0.0, self.EP_RELU if relu else 0)
         if addend is not None:
             addend = _dev(addend, "addend", dtype)
             if tuple(addend.shape) != (kmap.n_dst, cout):
@@ -652,7 +656,7 @@ class HipBackend:
         return ctypes.byref(ep), (ep, addend)
 
     def conv_gather_gemm(self, src, weight, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True, bn_raw=False, addend=None,
-                         act_slope=None):
+                         act_slope=None, relu=False):
         """dst[d] = sum_{(s,d) in offset k} src[s] @ weight[k] (+bias); kmap dst-sorted. bn_sums: a list; when the
         kernel can, the [sum x | sum x^2 | n] vector of dst (what bn_stats(dst) returns) is appended to it, computed in
         the convolution's write-back instead of by a pass over dst. ordered: True = heaviest-first tile order where it
@@ -671,8 +675,8 @@ class HipBackend:
         dst = torch.empty((kmap.n_dst, cout), dtype=torch.float32, device=src.device)
         part = self._bn_partial(kmap, t, cin, cout, k, 0, bn_sums, src.device)
         order = self._tile_order(kmap, t) if (ordered == "force" or (ordered and self._wants_order(kmap))) and kmap.n_dst > 0 and self.lib.pcs_conv_uses_tile_order(cin, cout, k, 0) else None
-        # write-back extras: addend (dgrad + skip gradient), LeakyReLU slope
-        ep, keep = self._epilogue(addend, kmap, cout, torch.float32, act_slope)
+        # write-back extras: addend (dgrad + skip gradient, inference residual), LeakyReLU slope, ReLU
+        ep, keep = self._epilogue(addend, kmap, cout, torch.float32, act_slope, relu)
         _check(self.lib.pcs_conv_gather_gemm_f32_ex(_ptr(src), src.shape[0], cin, _ptr(weight), k, cout,
                                                     _ptr(kmap._pairs_raw), 0, _ptr(seg), t, kmap.n_dst,
                                                     _ptr(bias) if bias is not None else None, ep, _ptr(dst),
@@ -705,7 +709,7 @@ class HipBackend:
         return wp
 
     def conv_gather_gemm_h(self, src, wp, k, cout, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True, bn_raw=False,
-                           addend=None, act_slope=None):
+                           addend=None, act_slope=None, relu=False):
         """Half-precision fused conv: src (n, cin) bf16 / fp16, wp = prepare_weights_h(...) of the same dtype."""
         if src.dtype not in self._HALF:
             raise TypeError("openpcseg_amd: conv_gather_gemm_h wants bfloat16 / float16 features, got %s" % src.dtype)
@@ -723,7 +727,7 @@ class HipBackend:
         dst = torch.empty((kmap.n_dst, cout), dtype=src.dtype, device=src.device)
         part = self._bn_partial(kmap, t, cin, cout, k, self._HALF[src.dtype], bn_sums, src.device)
         order = self._tile_order(kmap, t) if (ordered == "force" or (ordered and self._wants_order(kmap))) and kmap.n_dst > 0 else None
-        ep, keep = self._epilogue(addend, kmap, cout, src.dtype, act_slope)
+        ep, keep = self._epilogue(addend, kmap, cout, src.dtype, act_slope, relu)
         _check(self.lib.pcs_conv_gather_gemm_h_ex(_ptr(src), src.shape[0], cin, _ptr(wp), k, cout, _ptr(kmap._pairs_raw), 0,
                                                   _ptr(seg), t, kmap.n_dst, _ptr(bias) if bias is not None else None, ep,
                                                   _ptr(dst), self._HALF[src.dtype], _ptr(part) if part is not None else None,
@@ -1257,6 +1261,52 @@ class HipBackend:
                                                    n, _ptr(out), _stream()), "pcs_rows_argmax_gather_f32")
         return out
 
+    def predict_points(self, logits, inverse=None, point_offset=None, row_offset=None, labels=None, votes=None, want_pred=True,
+                       hist=None, bad=None):
+        """Prediction tail of an eval pass in one launch (csrc/predict.hip, pcs_predict_points_f32): logits (m, c) fp32;
+        inverse (n) int64 per-scene row index of every point, with point_offset / row_offset (n_scenes + 1) int64 device
+        tensors (both or neither; neither = one scene); labels (n) int64 for hist (c, c) int64, which accumulates; votes
+        (n, c) fp32 += softmax(row) and then decides. bad: (1,) int32 device flag, OR-ed (made and zeroed here when None).
+        -> (pred (n,) int64 or None, bad)."""
+        logits = _dev(logits, "logits", torch.float32)
+        m, c = logits.shape
+        dev = logits.device
+        if inverse is not None:
+            inverse = _dev(inverse, "inverse_map", torch.int64)
+        n = inverse.numel() if inverse is not None else m
+        if (point_offset is None) != (row_offset is None):
+            raise ValueError("openpcseg_amd: predict_points wants point_offset and row_offset together")
+        ns = 0
+        if point_offset is not None:
+            point_offset = _dev(point_offset, "point_offset", torch.int64)
+            row_offset = _dev(row_offset, "row_offset", torch.int64)
+            ns = point_offset.numel() - 1
+            if ns < 1 or row_offset.numel() != ns + 1:
+                raise ValueError("openpcseg_amd: point_offset / row_offset must both hold n_scenes + 1 entries")
+        if labels is not None:
+            labels = _dev(labels, "labels", torch.int64)
+            if labels.numel() != n:
+                raise ValueError("openpcseg_amd: %d labels for %d points" % (labels.numel(), n))
+        if votes is not None:
+            if votes.dtype != torch.float32 or not votes.is_cuda or not votes.is_contiguous() or tuple(votes.shape) != (n, c):
+                raise ValueError("openpcseg_amd: votes must be a contiguous (%d, %d) float32 device tensor (updated in place)" % (n, c))
+        if hist is not None:
+            if hist.dtype != torch.int64 or not hist.is_cuda or not hist.is_contiguous() or tuple(hist.shape) != (c, c):
+                raise ValueError("openpcseg_amd: hist must be a contiguous (%d, %d) int64 device tensor (updated in place)" % (c, c))
+            if labels is None:
+                raise ValueError("openpcseg_amd: hist needs labels")
+        if bad is None:
+            bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        pred = torch.empty(n, dtype=torch.int64, device=dev) if want_pred else None
+        _check(self.lib.pcs_predict_points_f32(_ptr(logits), m, c, _ptr(inverse) if inverse is not None else None, n,
+                                               _ptr(point_offset) if ns else None, _ptr(row_offset) if ns else None, ns,
+                                               _ptr(labels) if labels is not None else None,
+                                               _ptr(votes) if votes is not None else None,
+                                               _ptr(pred) if pred is not None else None,
+                                               _ptr(hist) if hist is not None else None, _ptr(bad), _stream()),
+               "pcs_predict_points_f32")
+        return pred, bad
+
     # -- criterion tail ---------------------------------------------------------------------------
     def lovasz_softmax(self, probas, labels, ignore=None, need_grad=True):
         """-> (loss 0-dim float32, d loss / d probas (n, C) float32 or None); csrc/lovasz.hip."""
@@ -1287,3 +1337,8 @@ def backend():
     if _BACKEND is None:
         _BACKEND = HipBackend()
     return _BACKEND
+
+
+def predict_points(logits, **kw):
+    """backend().predict_points: the device prediction tail (see HipBackend.predict_points)."""
+    return backend().predict_points(logits, **kw)

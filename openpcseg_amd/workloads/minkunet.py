@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from .. import functional as F
+from .. import inference
 from .. import modules as spnn
 from ..fused import FusedBatchNorm, FusedLinear
 from ..sparse import PointTensor, cat, fapply
@@ -77,6 +78,10 @@ class ConvBlock(nn.Module):
         _link(self.net[0], self.net[1])
 
     def forward(self, x, cat_with=None):
+        folds = inference.active(self)
+        if folds is not None:   # openpcseg_amd.freeze: conv + bias + ReLU in one launch; the decoder concat is torch.cat
+            y = folds["net"](x)
+            return y if cat_with is None else cat([y, cat_with])
         return _bn_act(self.net[1], self.net[0](x), act=self.net[2], cat_with=cat_with)
 
 
@@ -94,6 +99,10 @@ class ResBlock(nn.Module):
         _link(self.net[3], self.net[4])
 
     def forward(self, x):
+        folds = inference.active(self)
+        if folds is not None:   # openpcseg_amd.freeze: three (two) launches, the residual and the ReLU in the last write-back
+            r = x if folds["ds"] is None else folds["ds"](x)
+            return folds["b"](folds["a"](x), residual=r)
         if SKIP_FUSED and torch.is_grad_enabled() and x.feats.requires_grad:
             # x feeds the first convolution AND the skip path: both through the convolution's autograd node, whose dgrad kernel
             # adds the skip gradient in its write-back (no elementwise sum of two gradient tensors per block)
@@ -143,6 +152,9 @@ class MinkUNet(nn.Module):
             m.counted_by_parent = True
 
     def _stem(self, x):
+        folds = inference.active(self)
+        if folds is not None:
+            return folds["stem"][1](folds["stem"][0](x))
         h = _bn_act(self.stem[1], self.stem[0](x), act=self.stem[2])
         return _bn_act(self.stem[4], self.stem[3](h), act=self.stem[5])
 
@@ -168,31 +180,53 @@ class MinkUNet(nn.Module):
         # order. The voxel features are taken where the reference devoxelises them: BEFORE the dropout that follows (which
         # then runs out of place: the product keeps its input for the weight gradient).
         commute = isinstance(lin, FusedLinear) and os.environ.get("PCS_CLASSIFIER_COMMUTE", "1") != "0"
+        folds = inference.active(self)
+        if commute and folds is not None and folds["classifier"] is not None:
+            lin_part = folds["classifier"].devoxelized_part   # openpcseg_amd.freeze: the weight blocks are prepared once
+        else:
+            lin_part = lin.devoxelized_part
         x1 = self.stage1(x0)
         x2 = self.stage2(x1)
         x3 = self.stage3(x2)
         x4 = self.stage4(x3)
         if commute:
-            t1 = lin.devoxelized_part(0, x4.F, *point_maps(x4, z0), cache=x4.kmaps)
+            t1 = lin_part(0, x4.F, *point_maps(x4, z0), cache=x4.kmaps)
         else:
             z1 = voxel_to_point(x4, z0)
         x4.F = self._dropout(x4.F, commute)
         y1 = self.up1[1](self.up1[0](x4, cat_with=x3))  # torchsparse.cat([up(x4), x3]) fused into the BN apply pass
         y2 = self.up2[1](self.up2[0](y1, cat_with=x2))
         if commute:
-            t2 = lin.devoxelized_part(x4.F.shape[1], y2.F, *point_maps(y2, z0), cache=y2.kmaps)
+            t2 = lin_part(x4.F.shape[1], y2.F, *point_maps(y2, z0), cache=y2.kmaps)
         else:
             z2 = voxel_to_point(y2, z1)
         y2.F = self._dropout(y2.F, commute)
         y3 = self.up3[1](self.up3[0](y2, cat_with=x1))
         y4 = self.up4[1](self.up4[0](y3, cat_with=x0))
         if commute:
-            t3 = lin.devoxelized_part(x4.F.shape[1] + y2.F.shape[1], y4.F, *point_maps(y4, z0), cache=y4.kmaps)
+            t3 = lin_part(x4.F.shape[1] + y2.F.shape[1], y4.F, *point_maps(y4, z0), cache=y4.kmaps)
             return lin.sum_devoxelized([t1, t2, t3])
         z3 = voxel_to_point(y4, z2)
         if isinstance(lin, FusedLinear) and os.environ.get("PCS_CLASSIFIER_PARTS", "1") != "0":
             return lin.forward_parts([z1.F, z2.F, z3.F])  # Linear over [z1 | z2 | z3] without the (N, 480) concat
         return self.classifier(torch.cat([z1.F, z2.F, z3.F], dim=1))
+
+    def predict(self, batch, evaluator=None, votes=None):
+        """Evaluation forward + the prediction tail on the device (openpcseg_amd.inference.point_predict), no host
+        synchronisation: -> {"logits" (points of batch["lidar"], num_class) fp32, "point_predict": flat int64 device tensor over
+        the points of batch["inverse_map"] (scene after scene, each cut to num_points), "point_offset": its host offsets}.
+        evaluator: a SegEvaluator that also counts the confusion matrix against batch["targets_mapped"]; votes: a
+        (points, num_class) fp32 tensor that accumulates softmax votes over several passes and then decides."""
+        if self.training:
+            raise RuntimeError("MinkUNet.predict is an evaluation pass: call model.eval() first")
+        with torch.inference_mode():
+            logits = self.point_logits(batch["lidar"]).float()
+            if evaluator is not None:
+                pred = evaluator.update(logits, batch, votes=votes)
+                offsets = evaluator.last_offsets
+            else:
+                pred, offsets, _ = inference.point_predict(logits, batch, votes=votes)
+        return {"logits": logits, "point_predict": pred, "point_offset": offsets}
 
     def forward(self, batch):
         logits = self.point_logits(batch["lidar"])
