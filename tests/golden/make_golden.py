@@ -11,7 +11,7 @@ Known reference CPU-twin defects are worked around WITHOUT changing semantics:
   - kernel_hash_cpu uses row 0's batch index for every row (hash_cpu.cpp:29): called per batch;
   - devoxelize_backward_cpu is wrong (devoxelize_cpu.cpp:51-53): replaced by the restatement of
     devoxelize_cuda.cu:37-57 where a golden needs a backward pass (main_full).
-Usage: python tests/golden/make_golden.py [models | quantize | lovasz | config2 | config3 | config4 | config5 | cylinder]
+Usage: python tests/golden/make_golden.py [models | quantize | lovasz | config2 | config3 | config4 | config5 | cylinder | geometry]
 """
 import os
 import sys
@@ -45,6 +45,23 @@ def import_reference_torchsparse():
     torchsparse.backend = backend
     assert torchsparse.__version__ == "1.4.0"
     return torchsparse
+
+
+def per_batch_kmap(inc, outc, ks, in_stride, dilation=1):
+    """reference conv.py:156-176, with kernel_hash called per batch (CPU twin bug)."""
+    import torchsparse.nn.functional as F
+    from torchsparse.nn.utils import get_kernel_offsets
+    offsets = get_kernel_offsets(ks, stride=in_stride, dilation=dilation)
+    references = F.sphash(inc)
+    queries = torch.zeros(offsets.shape[0], outc.shape[0], dtype=torch.long)
+    for b in outc[:, 3].unique().tolist():
+        sel = (outc[:, 3] == b).nonzero().squeeze(1)
+        queries[:, sel] = F.sphash(outc[sel].contiguous(), offsets)
+    results = F.sphashquery(queries, references)
+    nbsizes = torch.sum(results != -1, dim=1)
+    nbmaps = torch.nonzero(results != -1)
+    nbmaps[:, 0] = results.view(-1)[nbmaps[:, 0] * results.size(1) + nbmaps[:, 1]]
+    return nbmaps, nbsizes
 
 
 def main():
@@ -92,20 +109,6 @@ def main():
     g["query_q"], g["query_out"] = q.numpy(), F.sphashquery(q, ref_h).numpy()
 
     # ---- spdownsample (fast + general branches) and kernel maps -------------------------------------
-    def per_batch_kmap(inc, outc, ks, in_stride):
-        """reference conv.py:156-176, with kernel_hash called per batch (CPU twin bug)."""
-        offsets = get_kernel_offsets(ks, stride=in_stride)
-        references = F.sphash(inc)
-        queries = torch.zeros(offsets.shape[0], outc.shape[0], dtype=torch.long)
-        for b in outc[:, 3].unique().tolist():
-            sel = (outc[:, 3] == b).nonzero().squeeze(1)
-            queries[:, sel] = F.sphash(outc[sel].contiguous(), offsets)
-        results = F.sphashquery(queries, references)
-        nbsizes = torch.sum(results != -1, dim=1)
-        nbmaps = torch.nonzero(results != -1)
-        nbmaps[:, 0] = results.view(-1)[nbmaps[:, 0] * results.size(1) + nbmaps[:, 1]]
-        return nbmaps, nbsizes
-
     cases = [("k3s1", 3, 1, 1), ("k2s2", 2, 2, 1), ("k133", (1, 3, 3), 1, 1), ("k313", (3, 1, 3), 1, 1),
              ("k3s2", 3, 2, 1), ("k3s221", 3, (2, 2, 1), 1)]
     cur = {1: coords}
@@ -728,8 +731,75 @@ def main_cylinder():
     print("wrote cylinder_golden.npz:", {k: v.shape for k, v in g.items() if k.endswith("voxel_coord")})
 
 
+def save_npz_stable(path, arrays):
+    """np.savez_compressed without the wall-clock time stamps (the same arrays give the same bytes) and with LZMA entries;
+    np.load reads it like any other .npz."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_LZMA) as zf:   # LZMA: the int32 pair lists shrink to half of what deflate leaves
+        for key, val in arrays.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_LZMA
+            info.external_attr = 0o644 << 16
+            with zf.open(info, "w") as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(val), allow_pickle=False)
+
+
+def main_geometry():
+    """Coordinates, kernel maps and convolution vectors of the reference for geometries no shipped model uses
+    (tests/geometry_cases.py: kernel volumes 2 .. 125, even kernels at stride 1, dilation, strides 3 and (2, 1, 2), the
+    tensor-stride-2 level, the scene shifted to negative coordinates) -> geometry_golden.npz. Same scene and the same
+    per-batch kernel_hash workaround as main(); data only."""
+    import_reference_torchsparse()
+    import torchsparse.nn.functional as F
+    from torchsparse.nn.functional.conv import ConvolutionFunction
+    import geometry_cases as gc
+    torch.set_num_threads(1)
+    ops = np.load(os.path.join(OUT, "ops_golden.npz"))
+    g = {}
+
+    def run(table, coords_of, prefix):
+        for name, ks, st, ts_, dil in table:
+            inc = torch.from_numpy(coords_of(ts_))
+            if gc.is_strided(st):
+                outc = F.spdownsample(inc, st, ks, ts_)
+                g["%sds_%s" % (prefix, name)] = outc.numpy().astype(np.int32)
+            else:
+                outc = inc
+            nbmaps, nbsizes = per_batch_kmap(inc, outc, ks, ts_, dil)
+            assert nbsizes.shape[0] == gc.volume(ks) and int(nbmaps.max()) < 2 ** 31
+            g["%skmap_%s_nbmaps" % (prefix, name)] = nbmaps.numpy().astype(np.int32)
+            g["%skmap_%s_nbsizes" % (prefix, name)] = nbsizes.numpy()
+
+    run(gc.CASES, lambda ts_: gc.input_coords(ops, ts_), "")
+    neg = gc.negative_scene(ops)
+    assert (neg[:, :3].min(0) < 0).all() and (neg[:, :3].max(0) > 0).all()
+    g["neg_coords"] = neg
+    run(gc.NEG_CASES, lambda ts_: neg, "neg_")
+
+    tg = torch.Generator().manual_seed(5)
+    n_in = ops["scene_coords"].shape[0]
+    for name, transposed, cin, cout in gc.CONV_CASES:
+        nbmaps = torch.from_numpy(g["kmap_%s_nbmaps" % name]).long()
+        nbsizes = torch.from_numpy(g["kmap_%s_nbsizes" % name])
+        n_out = g["ds_%s" % name].shape[0] if ("ds_%s" % name) in g else n_in
+        # operands on a coarse binary grid (features in halves, weights in sixteenths): the vectors stay small once
+        # compressed (the k4 s2 level has 16 523 rows), and every sum of products is exact in fp32
+        x = (torch.randn(n_out if transposed else n_in, cin, generator=tg) * 2).round().div(2).requires_grad_(True)
+        w = (torch.randn(nbsizes.shape[0], cin, cout, generator=tg) * 0.2 * 16).round().div(16).requires_grad_(True)
+        y = ConvolutionFunction.apply(x, w, nbmaps, nbsizes, (n_in, n_out), transposed)
+        gy = (torch.randn(y.shape, generator=tg) * 2).round().div(2)
+        y.backward(gy)
+        tag = "conv_%s_%s" % (name, "T" if transposed else "N")
+        for key, val in [("x", x), ("w", w), ("y", y), ("gy", gy), ("gx", x.grad), ("gw", w.grad)]:
+            g["%s_%s" % (tag, key)] = val.detach().numpy()
+    path = os.path.join(OUT, "geometry_golden.npz")
+    save_npz_stable(path, g)
+    print("wrote geometry_golden.npz with", len(g), "arrays,", os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "cylinder":
+    if len(sys.argv) > 1 and sys.argv[1] == "geometry":
+        main_geometry()
+    elif len(sys.argv) > 1 and sys.argv[1] == "cylinder":
         main_cylinder()
     elif len(sys.argv) > 1 and sys.argv[1] in ("config2", "config3", "config4", "config5", "config2x2", "config_mk34"):
         main_full(sys.argv[1])

@@ -9,6 +9,10 @@ from openpcseg_amd import cpu_fallback, native
 from openpcseg_amd import functional as F
 from openpcseg_amd.sparse import SparseTensor
 
+import geometry_cases as gc
+
+OPS, GEO = gc.load()   # ops_golden.npz, geometry_golden.npz (tests/geometry_cases.py)
+
 
 @pytest.fixture()
 def be():
@@ -77,6 +81,51 @@ def test_conv_forward_backward_vs_reference(golden, be, tag, ks, stride, transpo
     out.F.backward(t(golden[tag + "_gy"]))
     assert np.allclose(x.grad.numpy(), golden[tag + "_gx"], rtol=1e-4, atol=1e-5)
     assert np.allclose(w.grad.numpy(), golden[tag + "_gw"], rtol=1e-4, atol=1e-4)
+
+
+def _geo_conv_entry(coords, ts_, ks, st, dil, w=None):
+    """conv3d with an all-zero (or the given) kernel on `coords` at tensor stride ts_ -> (input, output, kmap entry)."""
+    ks3, st3, dil3, ts3 = gc.tup3(ks), gc.tup3(st), gc.tup3(dil), gc.tup3(ts_)
+    inp = SparseTensor(torch.zeros(coords.shape[0], 4), coords, ts_)
+    out = F.conv3d(inp, torch.zeros(gc.volume(ks), 4, 4), ks3, stride=st3, dilation=dil3)
+    return inp, out, inp.kmaps[(ts3, ks3, st3, dil3)]
+
+
+@pytest.mark.parametrize("prefix,table", [("", gc.CASES), ("neg_", gc.NEG_CASES)], ids=["scene", "negative"])
+def test_geometry_rulebooks_vs_reference(be, prefix, table):
+    """functional.conv3d on the CPU path: output coordinates and kernel maps of K = 2 .. 125, even kernels at stride 1,
+    dilation, strides 3 / (2, 1, 2), the tensor-stride-2 level and negative coordinates are the reference's, in order."""
+    for name, ks, st, ts_, dil in table:
+        coords = t(gc.negative_scene(OPS) if prefix else gc.input_coords(OPS, ts_))
+        inp, out, entry = _geo_conv_entry(coords, ts_, ks, st, dil)
+        assert (entry[0].long().numpy() == GEO["%skmap_%s_nbmaps" % (prefix, name)]).all(), name
+        assert (entry[1].numpy() == GEO["%skmap_%s_nbsizes" % (prefix, name)]).all(), name
+        if gc.is_strided(st):
+            assert out.C.dtype == torch.int32 and (out.C.numpy() == GEO["%sds_%s" % (prefix, name)]).all(), name
+            assert out.s == tuple(a * b for a, b in zip(gc.tup3(ts_), gc.tup3(st)))
+        else:
+            assert out.C is inp.C
+
+
+@pytest.mark.parametrize("name,transposed,cin,cout", gc.CONV_CASES, ids=["%s_%s" % (c[0], "T" if c[1] else "N") for c in gc.CONV_CASES])
+def test_geometry_conv_forward_backward_vs_reference(be, name, transposed, cin, cout):
+    _, ks, st, ts_, dil = gc.case(name)
+    tag = "conv_%s_%s" % (name, "T" if transposed else "N")
+    coords = t(OPS["scene_coords"])
+    x = t(GEO[tag + "_x"]).requires_grad_(True)
+    w = t(GEO[tag + "_w"]).requires_grad_(True)
+    if not transposed:
+        out = F.conv3d(SparseTensor(x, coords, 1), w, ks, stride=st, dilation=dil)
+    else:
+        _, down, _ = _geo_conv_entry(coords, ts_, ks, st, dil)
+        inp = SparseTensor(x, down.C, down.s)
+        inp.cmaps, inp.kmaps = down.cmaps, down.kmaps
+        inp.cmaps[(1, 1, 1)] = coords
+        out = F.conv3d(inp, w, ks, stride=st, dilation=dil, transposed=True)
+    assert np.allclose(out.F.detach().numpy(), GEO[tag + "_y"], rtol=1e-4, atol=1e-5)
+    out.F.backward(t(GEO[tag + "_gy"]))
+    assert np.allclose(x.grad.numpy(), GEO[tag + "_gx"], rtol=1e-4, atol=1e-5)
+    assert np.allclose(w.grad.numpy(), GEO[tag + "_gw"], rtol=1e-4, atol=1e-4)
 
 
 def test_point_voxel_ops_vs_reference(golden, be):

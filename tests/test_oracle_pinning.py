@@ -14,6 +14,10 @@ import torch
 
 from oracle import oracle as orc
 
+import geometry_cases as gc
+
+OPS, GEO = gc.load()   # ops_golden.npz, geometry_golden.npz (tests/geometry_cases.py)
+
 RTOL = 1e-5
 
 
@@ -108,6 +112,95 @@ def test_devoxelize_bwd_is_adjoint_of_fwd(golden):
     lhs = (orc.devoxelize_fwd(f, idx8, w8).astype(np.float64) * g).sum()
     rhs = (f.astype(np.float64) * orc.devoxelize_bwd(g, idx8, w8, 300)).sum()
     assert abs(lhs - rhs) <= 1e-4 * max(abs(lhs), 1.0)
+
+
+# ---- geometries no shipped model uses (tests/geometry_cases.py, geometry_golden.npz) --------------------------------
+def _geo_check_case(prefix, inc, name, ks, st, ts_, dil):
+    if gc.is_strided(st):
+        outc = orc.spdownsample(inc, st, ks, ts_)
+        want = GEO["%sds_%s" % (prefix, name)]
+        assert outc.dtype == np.int32 and outc.shape == want.shape and (outc == want).all()
+    else:
+        outc = inc
+        assert ("%sds_%s" % (prefix, name)) not in GEO.files
+    nbmaps, nbsizes = orc.build_kmap(inc, outc, ks, ts_, dil)
+    assert nbsizes.shape == (gc.volume(ks),) and (nbsizes == GEO["%skmap_%s_nbsizes" % (prefix, name)]).all()
+    want = GEO["%skmap_%s_nbmaps" % (prefix, name)]
+    assert want.dtype == np.int32 and nbmaps.shape == want.shape and (nbmaps == want).all()
+
+
+@pytest.mark.parametrize("name,ks,st,ts_,dil", gc.CASES, ids=[c[0] for c in gc.CASES])
+def test_geometry_downsample_and_kmap(name, ks, st, ts_, dil):
+    """K = 2 .. 125, even kernels at stride 1, dilation 2 / 3, strides 3 and (2, 1, 2), the tensor-stride-2 level: output
+    coordinates and kernel maps of the oracle are the reference's, bit for bit and in order."""
+    _geo_check_case("", gc.input_coords(OPS, ts_), name, ks, st, ts_, dil)
+
+
+@pytest.mark.parametrize("name,ks,st,ts_,dil", gc.NEG_CASES, ids=[c[0] for c in gc.NEG_CASES])
+def test_geometry_negative_coordinates(name, ks, st, ts_, dil):
+    """The scene shifted to negative coordinates: the fast spdownsample branch truncates toward zero (so k2 s2 loses most
+    negative voxels in the reference, too), the general one compares with the coordinate minimum."""
+    neg = gc.negative_scene(OPS)
+    assert (neg == GEO["neg_coords"]).all() and (neg[:, :3].min(0) < 0).all()
+    _geo_check_case("neg_", neg, name, ks, st, ts_, dil)
+
+
+def test_geometry_fixture_facts():
+    """What the GPU tests lean on: empty offsets (k5 s1: 84 of 125, k4 s1: 43 of 64) and output rows that no pair reaches
+    (k4 s2: 9 686 of 16 523, k3 s3: 1 022 of 2 372), where the reference returns exact zeros."""
+    assert int((GEO["kmap_k5s1_nbsizes"] == 0).sum()) == 84 and int((GEO["kmap_k4s1_nbsizes"] == 0).sum()) == 43
+    for name, rows, empty in (("k4s2", 16523, 9686), ("k3s3", 2372, 1022)):
+        n_out = GEO["ds_" + name].shape[0]
+        hit = np.zeros(n_out, bool)
+        hit[GEO["kmap_%s_nbmaps" % name][:, 1]] = True
+        assert (n_out, int((~hit).sum())) == (rows, empty)
+        y = GEO["conv_%s_N_y" % name]
+        assert not y[~hit].any() and y[hit].any(axis=1).mean() > 0.95
+    assert os.path.getsize(os.path.join(gc.GOLDEN_DIR, "geometry_golden.npz")) < os.path.getsize(os.path.join(gc.GOLDEN_DIR, "ops_golden.npz"))
+
+
+@pytest.mark.parametrize("name,transposed,cin,cout", gc.CONV_CASES, ids=["%s_%s" % (c[0], "T" if c[1] else "N") for c in gc.CONV_CASES])
+def test_geometry_conv_fwd_bwd(name, transposed, cin, cout):
+    tag = "conv_%s_%s" % (name, "T" if transposed else "N")
+    nbmaps, nbsizes = GEO["kmap_%s_nbmaps" % name], GEO["kmap_%s_nbsizes" % name]
+    n_in = OPS["scene_coords"].shape[0]
+    n_out = GEO["ds_" + name].shape[0] if ("ds_" + name) in GEO.files else n_in
+    x, w, gy = GEO[tag + "_x"], GEO[tag + "_w"], GEO[tag + "_gy"]
+    assert w.shape == (nbsizes.shape[0], cin, cout)
+    close(orc.conv_fwd(x, w, nbmaps, nbsizes, (n_in, n_out), transposed), GEO[tag + "_y"])
+    gx, gw = orc.conv_bwd(x, gy, w, nbmaps, nbsizes, transposed)
+    close(gx, GEO[tag + "_gx"])
+    close(gw, GEO[tag + "_gw"])
+
+
+def test_geometry_live_reference_backend(ref_backend):
+    """K = 125 and dilated K = 27 on one frame of the scene (the CPU twin's kernel_hash reads one batch index): hashes of
+    the offset grid, the map the reference's own hash / query give, and its convolution forward / backward."""
+    inc = np.ascontiguousarray(OPS["scene_coords"][OPS["scene_coords"][:, 3] == 0])
+    tc = torch.from_numpy(inc)
+    n = inc.shape[0]
+    rng = np.random.default_rng(12)
+    for ks, dil in ((5, 1), (3, 2), (4, 1)):
+        off = orc.get_kernel_offsets(ks, 1, dil)
+        kh = ref_backend.ref.kernel_hash_cpu(tc, torch.from_numpy(off))
+        assert (kh.numpy() == orc.sphash(inc, off)).all()
+        res = ref_backend.hash_query(kh.reshape(-1), ref_backend.hash(tc)).reshape(off.shape[0], n).numpy()
+        nbmaps, nbsizes = orc.build_kmap(inc, inc, ks, 1, dil)
+        kk, jj = np.nonzero(res != -1)
+        assert ((res != -1).sum(1) == nbsizes).all() and (np.stack([res[kk, jj], jj], 1) == nbmaps).all()
+        k = off.shape[0]
+        x = rng.normal(size=(n, 6)).astype(np.float32)
+        w = (rng.normal(size=(k, 6, 10)) * 0.1).astype(np.float32)
+        gy = rng.normal(size=(n, 10)).astype(np.float32)
+        tm, tsz = torch.from_numpy(nbmaps.astype(np.int32)), torch.from_numpy(nbsizes.astype(np.int32))
+        out = torch.zeros(n, 10)
+        ref_backend.ref.convolution_forward_cpu(torch.from_numpy(x), out, torch.from_numpy(w), tm, tsz, False)
+        close(orc.conv_fwd(x, w, nbmaps, nbsizes, (n, n)), out.numpy())
+        gin, gw = torch.zeros(n, 6), torch.zeros(k, 6, 10)
+        ref_backend.ref.convolution_backward_cpu(torch.from_numpy(x), gin, torch.from_numpy(gy), torch.from_numpy(w), gw, tm, tsz, False)
+        ogx, ogw = orc.conv_bwd(x, gy, w, nbmaps, nbsizes)
+        close(ogx, gin.numpy())
+        close(ogw, gw.numpy())
 
 
 # ---- live against the reference's compiled backend (in-container only) -----------------------------
