@@ -103,6 +103,16 @@ int pcs_voxelize_fwd_csr_f32(const float *feats, const int64_t *order, const int
                              const int32_t *counts, int64_t m, int32_t c, float *out, void *stream);
 int pcs_voxelize_bwd_f32(const float *gout, const int32_t *idx, const int32_t *counts,
                          int64_t n, int32_t c, float *gin, void *stream);
+/* K7 (CSR form) / K8 with 16-bit feature storage, as the reference's AT_DISPATCH_FLOATING_TYPES_AND_HALF instances serve under
+ * --amp: feats / out / gout / gin are bf16 (dtype 1) or fp16 (dtype 2) rows, any other dtype is PCS_EINVAL; order, rowptr, idx and
+ * counts as in the _f32 entries. Every sum is accumulated in fp32 registers in `order` order (divide, then add) and rounded to
+ * storage once (nearest even); every output row is written exactly once, zeros for a voxel without points (fwd) and for a point
+ * without a voxel or with a zero count (bwd). 16-byte accesses where c % 8 == 0 and the rows are 16-byte aligned, 8-byte where
+ * c % 4 == 0, scalar otherwise. The atomic form pcs_voxelize_fwd_f32 has no 16-bit twin. */
+int pcs_voxelize_fwd_csr_h(const void *feats, const int64_t *order, const int64_t *rowptr, const int32_t *counts,
+                           int64_t m, int32_t c, int32_t dtype, void *out, void *stream);
+int pcs_voxelize_bwd_h(const void *gout, const int32_t *idx, const int32_t *counts, int64_t n, int32_t c,
+                       int32_t dtype, void *gin, void *stream);
 
 /* K9/K10  devoxelize_forward_cuda / devoxelize_backward_cuda
  *         TS:torchsparse/backend/devoxelize/devoxelize_cuda.cu:11-98
@@ -115,6 +125,10 @@ int pcs_devoxelize_fwd_f32(const float *feat, const int32_t *idx8, const float *
                            int32_t c, float *out, void *stream);
 int pcs_devoxelize_bwd_f32(const float *gout, const int32_t *idx8, const float *w8, int64_t n,
                            int64_t m, int32_t c, float *gfeat, void *stream);
+/* K9 with 16-bit feature storage: feat / out bf16 (dtype 1) or fp16 (dtype 2), any other dtype is PCS_EINVAL; w8 stays fp32.
+ * The 8 corners are accumulated in fp32 registers in k = 0..7 order and rounded to storage once. */
+int pcs_devoxelize_fwd_h(const void *feat, const int32_t *idx8, const float *w8, int64_t n, int32_t c,
+                         int32_t dtype, void *out, void *stream);
 
 /* voxel_to_point map in one pass (R:pcseg/model/segmentor/voxel/minkunet/utils.py:69-105: floor, cat, kernel_hash
  * over the 8 cell corners, hashquery, calc_ti_weights, two transposes): coords (n, coord_ld >= 4) float = x,y,z,..,batch
@@ -131,6 +145,16 @@ int pcs_corner_map_f32(const float *coords, int32_t coord_ld, int64_t n, int32_t
  * idx8 (one sort) and reuses them for every backward through the same map. */
 int pcs_devoxelize_bwd_csr_f32(const float *gout, const int64_t *order, const int64_t *rowptr,
                                const float *w8, int64_t m, int32_t c, float *gfeat, void *stream);
+/* The same with 16-bit feature storage: gout / gfeat bf16 (dtype 1) or fp16 (dtype 2), any other dtype is PCS_EINVAL; w8 fp32.
+ * fp32 accumulation in a fixed order (run-to-run identical), one rounding on the store, rows without entries written as zeros.
+ * Narrow rows (at most 8 vectors of 8 or 4 halfs) on levels of at most 400 000 voxels take a wave-per-voxel form, everything
+ * else one lane row per voxel. The atomic form pcs_devoxelize_bwd_f32 has no 16-bit twin. */
+int pcs_devoxelize_bwd_csr_h(const void *gout, const int64_t *order, const int64_t *rowptr, const float *w8,
+                             int64_t m, int32_t c, int32_t dtype, void *gfeat, void *stream);
+/* Measurement switch (tools/pointvoxel_bench.py), not part of the contract: independent row loads in flight per lane in the
+ * segmented lane-row kernels of pcs_voxelize_fwd_csr_h and pcs_devoxelize_bwd_csr_h: 2 or 4 forces that form, any other value
+ * restores the default (4 on levels of at most 400 000 voxels, else 2). Same summation order, same bits. */
+void pcs_debug_pointvoxel_h_inflight(int32_t loads);
 
 /* calc_ti_weights  TS:torchsparse/nn/functional/devoxelize.py:10-48  (about 25 small torch
  * kernels in the reference, one kernel here). coords (n, coord_ld) fp32 (first 3 columns

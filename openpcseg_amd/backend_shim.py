@@ -35,6 +35,8 @@ def count_cuda(idx, s):
     return native.backend().count(idx, s)
 
 
+# K7-K10 take Float, Half and BFloat16 features like the reference's AT_DISPATCH_FLOATING_TYPES_AND_HALF instances (under
+# autocast its nn/functional hands them half tensors, the trilinear weight included: that one is computed with in fp32 here)
 def voxelize_forward_cuda(inputs, idx, counts):
     return native.backend().voxelize_fwd(inputs, idx, counts)
 
@@ -44,11 +46,11 @@ def voxelize_backward_cuda(top_grad, idx, counts, n):
 
 
 def devoxelize_forward_cuda(feat, indices, weight):
-    return native.backend().devoxelize_fwd(feat, indices, weight)
+    return native.backend().devoxelize_fwd(feat, indices, weight.float())
 
 
 def devoxelize_backward_cuda(top_grad, indices, weight, n):
-    return native.backend().devoxelize_bwd(top_grad, indices, weight, n)
+    return native.backend().devoxelize_bwd(top_grad, indices, weight.float().contiguous(), n)
 
 
 def _as_kmap(neighbor_map, neighbor_offset, n_src, n_dst, dst_col):

@@ -13,8 +13,9 @@ built by a fused probe/compaction pass instead of kernel_hash -> hashquery -> su
 and the convolution is an output-stationary fused gather-GEMM (no per-offset launches, no
 `nbsizes.cpu()` per call).
 Autocast: the reference casts op inputs to fp16 under AMP (`custom_fwd(cast_inputs=torch.half)`). Here conv3d follows
-the autocast dtype (bf16 or fp16) on the 16-bit MFMA kernels (`_SparseConv`); voxelize / devoxelize keep fp32 (at
-least the reference's precision).
+the autocast dtype (bf16 or fp16) on the 16-bit MFMA kernels (`_SparseConv`); voxelize / devoxelize cast to fp32 by
+default (at least the reference's precision) and keep 16-bit features on the 16-bit kernels under
+`set_pointvoxel_policy("keep")`; outside autocast they run in the dtype that arrives.
 """
 import os
 
@@ -57,16 +58,49 @@ def spcount(coords, num):
 
 
 # ---------------------------------------------------------------------------------------------
+# voxelize / devoxelize under autocast. "fp32" (library default): the feature tensor is cast to fp32 and the fp32 kernels run, fp32
+# out -- every point <-> voxel hop of a bf16 model then converts in front and the consumer converts back. "keep": no cast; a
+# bf16 / fp16 tensor runs on the 16-bit kernels (csrc/pointvoxel_half.hip: fp32 accumulation, one rounding on the store) and
+# leaves in its own dtype, an fp32 tensor stays on the fp32 kernels. "keep" never casts fp32 DOWN: initial_voxelize averages
+# voxel COORDINATES through spvoxelize, and the reference's `custom_fwd(cast_inputs=torch.half)`
+# (TS:torchsparse/nn/functional/voxelize.py) rounds those to fp16 under --amp, where coordinates above 2048 lose their low
+# bits. Outside autocast the policy plays no part: the op takes what arrives, 16 bits in give 16 bits out.
+_POINTVOXEL_POLICY = {"mode": "fp32"}
+
+
+def set_pointvoxel_policy(mode):
+    if mode not in ("fp32", "keep"):
+        raise ValueError("pointvoxel policy must be 'fp32' or 'keep'")
+    _POINTVOXEL_POLICY["mode"] = mode
+
+
+def get_pointvoxel_policy():
+    return _POINTVOXEL_POLICY["mode"]
+
+
+def _voxelize_forward(ctx, feats, coords, counts):
+    feats = feats.contiguous()
+    holder = coords  # the caller's tensor outlives this call (idx_query cache of point_to_voxel)
+    coords = coords.contiguous().int()
+    out = _be().voxelize_fwd(feats, coords, counts, cache_on=holder)
+    ctx.for_backwards = (coords, counts, feats.shape[0])
+    return out
+
+
+def _devoxelize_forward(ctx, feats, coords, weights):
+    feats = feats.contiguous()
+    coords = coords.contiguous().int()
+    weights = weights.contiguous().float()   # the trilinear weights stay fp32 whatever the features are stored in
+    out = _be().devoxelize_fwd(feats, coords, weights)
+    ctx.for_backwards = (coords, weights, feats.shape[0])
+    return out
+
+
 class _Voxelize(Function):
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, feats, coords, counts):
-        feats = feats.contiguous()
-        holder = coords  # the caller's tensor outlives this call (idx_query cache of point_to_voxel)
-        coords = coords.contiguous().int()
-        out = _be().voxelize_fwd(feats, coords, counts, cache_on=holder)
-        ctx.for_backwards = (coords, counts, feats.shape[0])
-        return out
+        return _voxelize_forward(ctx, feats, coords, counts)
 
     @staticmethod
     @custom_bwd(device_type="cuda")
@@ -75,20 +109,25 @@ class _Voxelize(Function):
         return _be().voxelize_bwd(grad_output.contiguous(), coords, counts, n), None, None
 
 
+class _VoxelizeKeep(_Voxelize):
+    """The "keep" policy: no cast under autocast, the gradient leaves in the dtype the output was handed on in."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda")
+    def forward(ctx, feats, coords, counts):
+        return _voxelize_forward(ctx, feats, coords, counts)
+
+
 def spvoxelize(feats, coords, counts):
-    return _Voxelize.apply(feats, coords, counts)
+    fn = _VoxelizeKeep if _POINTVOXEL_POLICY["mode"] == "keep" else _Voxelize
+    return fn.apply(feats, coords, counts)
 
 
 class _Devoxelize(Function):
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, feats, coords, weights):
-        feats = feats.contiguous()
-        coords = coords.contiguous().int()
-        weights = weights.contiguous()
-        out = _be().devoxelize_fwd(feats, coords, weights)
-        ctx.for_backwards = (coords, weights, feats.shape[0])
-        return out
+        return _devoxelize_forward(ctx, feats, coords, weights)
 
     @staticmethod
     @custom_bwd(device_type="cuda")
@@ -97,8 +136,16 @@ class _Devoxelize(Function):
         return _be().devoxelize_bwd(grad_output.contiguous(), coords, weights, m), None, None
 
 
+class _DevoxelizeKeep(_Devoxelize):
+    @staticmethod
+    @custom_fwd(device_type="cuda")
+    def forward(ctx, feats, coords, weights):
+        return _devoxelize_forward(ctx, feats, coords, weights)
+
+
 def spdevoxelize(feats, coords, weights):
-    return _Devoxelize.apply(feats, coords, weights)
+    fn = _DevoxelizeKeep if _POINTVOXEL_POLICY["mode"] == "keep" else _Devoxelize
+    return fn.apply(feats, coords, weights)
 
 
 def calc_ti_weights(coords, idx_query, scale=1):

@@ -32,6 +32,10 @@ SIGNATURES = {
     "pcs_devoxelize_fwd_f32": (c_int32, [_P, _P, _P, c_int64, c_int32, _P, _P]),
     "pcs_devoxelize_bwd_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int32, _P, _P]),
     "pcs_devoxelize_bwd_csr_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, _P]),
+    "pcs_voxelize_fwd_csr_h": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
+    "pcs_voxelize_bwd_h": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
+    "pcs_devoxelize_fwd_h": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
+    "pcs_devoxelize_bwd_csr_h": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
     "pcs_corner_map_f32": (c_int32, [_P, c_int32, c_int64, c_int32, _P, c_int64, _P, _P, _P]),
     "pcs_ti_weights_f32": (c_int32, [_P, c_int32, _P, c_int64, c_float, _P, _P]),
     "pcs_downsample_pack": (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, _P, _P, _P, _P]),
@@ -119,6 +123,7 @@ SIGNATURES = {
     "pcs_lovasz_softmax_f32": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int64, _P, _P, _P, c_int64, _P]),
     "pcs_debug_convh_ws": (None, [c_int32, c_int32, c_int32]),       # measurement switches (A/B tools), not part of the contract
     "pcs_debug_wgrad_interleave": (None, [c_int32]),
+    "pcs_debug_pointvoxel_h_inflight": (None, [c_int32]),
 }
 
 class _WeightJob(ctypes.Structure):   # pcs_weight_job of include/pcseg_hip.h
@@ -376,24 +381,40 @@ class HipBackend:
         return out
 
     # -- K7-K10 ---------------------------------------------------------------------------------
+    def _pv_feats(self, t, name):
+        """A feature tensor of the point <-> voxel operators: fp32, bf16 or fp16 -> (tensor, dtype code of the _h entries or 0)."""
+        t = _dev(t, name)
+        if t.dtype == torch.float32:
+            return t, 0
+        if t.dtype not in self._HALF:
+            raise TypeError("openpcseg_amd: `%s` must be float32, bfloat16 or float16, got %s" % (name, t.dtype))
+        return t, self._HALF[t.dtype]
+
     def voxelize_fwd(self, feats, idx, counts, cache_on=None):
         """out[v] = sum over the points i of voxel v of feats[i] / counts[v]: segmented over the points sorted by
         voxel (no atomics, deterministic). The sorted order is cached on `cache_on` (the caller's index tensor,
-        which point_to_voxel reuses at every stage) or on idx."""
-        feats = _dev(feats, "feats", torch.float32)
+        which point_to_voxel reuses at every stage) or on idx. feats fp32, bf16 or fp16; out in the same dtype (16-bit rows:
+        fp32 accumulation, one rounding on the store); the cached order serves every dtype."""
+        feats, code = self._pv_feats(feats, "feats")
         idx = _dev(idx, "coords", torch.int32)
         counts = _dev(counts, "counts", torch.int32)
         c = feats.shape[1]
         m = counts.shape[0]
         holder = cache_on if cache_on is not None else idx
         csr = _cached(holder, "_pcs_vox_csr", _cache_key(holder) + (m, idx.shape[0]), lambda: self._csr(idx, m))
-        out = torch.empty((m, c), dtype=torch.float32, device=feats.device)
-        _check(self.lib.pcs_voxelize_fwd_csr_f32(_ptr(feats), _ptr(csr[0]), _ptr(csr[1]), _ptr(counts), m, c,
-                                                 _ptr(out), _stream()), "pcs_voxelize_fwd_csr_f32")
+        out = torch.empty((m, c), dtype=feats.dtype, device=feats.device)
+        if code:
+            _check(self.lib.pcs_voxelize_fwd_csr_h(_ptr(feats), _ptr(csr[0]), _ptr(csr[1]), _ptr(counts), m, c, code,
+                                                   _ptr(out), _stream()), "pcs_voxelize_fwd_csr_h")
+        else:
+            _check(self.lib.pcs_voxelize_fwd_csr_f32(_ptr(feats), _ptr(csr[0]), _ptr(csr[1]), _ptr(counts), m, c,
+                                                     _ptr(out), _stream()), "pcs_voxelize_fwd_csr_f32")
         return out
 
     def voxelize_fwd_atomic(self, feats, idx, counts):
-        """The reference's literal K7 dataflow (fp32 atomics); kept for A/B measurements."""
+        """The reference's literal K7 dataflow (fp32 atomics); kept for A/B measurements. fp32 only."""
+        if isinstance(feats, torch.Tensor) and feats.dtype in self._HALF:
+            raise TypeError("openpcseg_amd: voxelize_fwd_atomic is fp32 only (got %s); 16-bit rows take voxelize_fwd" % feats.dtype)
         feats = _dev(feats, "feats", torch.float32)
         idx = _dev(idx, "coords", torch.int32)
         counts = _dev(counts, "counts", torch.int32)
@@ -405,37 +426,54 @@ class HipBackend:
         return out
 
     def voxelize_bwd(self, gout, idx, counts, n):
-        gout = _dev(gout, "grad_output", torch.float32)
+        gout, code = self._pv_feats(gout, "grad_output")
         c = gout.shape[1]
-        gin = torch.empty((n, c), dtype=torch.float32, device=gout.device)
-        _check(self.lib.pcs_voxelize_bwd_f32(_ptr(gout), _ptr(idx), _ptr(counts), n, c, _ptr(gin),
-                                             _stream()), "pcs_voxelize_bwd_f32")
+        gin = torch.empty((n, c), dtype=gout.dtype, device=gout.device)
+        if code:
+            _check(self.lib.pcs_voxelize_bwd_h(_ptr(gout), _ptr(idx), _ptr(counts), n, c, code, _ptr(gin),
+                                               _stream()), "pcs_voxelize_bwd_h")
+        else:
+            _check(self.lib.pcs_voxelize_bwd_f32(_ptr(gout), _ptr(idx), _ptr(counts), n, c, _ptr(gin),
+                                                 _stream()), "pcs_voxelize_bwd_f32")
         return gin
 
     def devoxelize_fwd(self, feats, idx8, w8):
-        feats = _dev(feats, "feats", torch.float32)
+        """feats fp32, bf16 or fp16, out in the same dtype; the weights w8 are always fp32."""
+        feats, code = self._pv_feats(feats, "feats")
         idx8 = _dev(idx8, "coords", torch.int32)
         w8 = _dev(w8, "weights", torch.float32)
         n, c = idx8.shape[0], feats.shape[1]
-        out = torch.empty((n, c), dtype=torch.float32, device=feats.device)
-        _check(self.lib.pcs_devoxelize_fwd_f32(_ptr(feats), _ptr(idx8), _ptr(w8), n, c, _ptr(out),
-                                               _stream()), "pcs_devoxelize_fwd_f32")
+        out = torch.empty((n, c), dtype=feats.dtype, device=feats.device)
+        if code:
+            _check(self.lib.pcs_devoxelize_fwd_h(_ptr(feats), _ptr(idx8), _ptr(w8), n, c, code, _ptr(out),
+                                                 _stream()), "pcs_devoxelize_fwd_h")
+        else:
+            _check(self.lib.pcs_devoxelize_fwd_f32(_ptr(feats), _ptr(idx8), _ptr(w8), n, c, _ptr(out),
+                                                   _stream()), "pcs_devoxelize_fwd_f32")
         return out
 
     def devoxelize_bwd(self, gout, idx8, w8, m):
         """gfeat[v] = sum over (point i, corner k) with idx8[i,k] == v of w8[i,k] * gout[i].
         Contention-free: entries sorted by voxel once per idx8 tensor (cached on the tensor; the
-        same map serves every backward of one forward), then a segmented reduction."""
-        gout = _dev(gout, "grad_output", torch.float32)
+        same map serves every backward of one forward, in every dtype), then a segmented reduction.
+        gout fp32, bf16 or fp16, gfeat in the same dtype; w8 fp32."""
+        gout, code = self._pv_feats(gout, "grad_output")
         n, c = gout.shape
         csr = _cached(idx8, "_pcs_csr", _cache_key(idx8) + (m,), lambda: self._csr(idx8, m))
-        gfeat = torch.empty((m, c), dtype=torch.float32, device=gout.device)
-        _check(self.lib.pcs_devoxelize_bwd_csr_f32(_ptr(gout), _ptr(csr[0]), _ptr(csr[1]), _ptr(w8), m, c,
-                                                   _ptr(gfeat), _stream()), "pcs_devoxelize_bwd_csr_f32")
+        gfeat = torch.empty((m, c), dtype=gout.dtype, device=gout.device)
+        if code:
+            w8 = _dev(w8, "weights", torch.float32)
+            _check(self.lib.pcs_devoxelize_bwd_csr_h(_ptr(gout), _ptr(csr[0]), _ptr(csr[1]), _ptr(w8), m, c, code,
+                                                     _ptr(gfeat), _stream()), "pcs_devoxelize_bwd_csr_h")
+        else:
+            _check(self.lib.pcs_devoxelize_bwd_csr_f32(_ptr(gout), _ptr(csr[0]), _ptr(csr[1]), _ptr(w8), m, c,
+                                                       _ptr(gfeat), _stream()), "pcs_devoxelize_bwd_csr_f32")
         return gfeat
 
     def devoxelize_bwd_atomic(self, gout, idx8, w8, m):
-        """The reference's literal K10 dataflow (fp32 atomics); kept for A/B measurements."""
+        """The reference's literal K10 dataflow (fp32 atomics); kept for A/B measurements. fp32 only."""
+        if isinstance(gout, torch.Tensor) and gout.dtype in self._HALF:
+            raise TypeError("openpcseg_amd: devoxelize_bwd_atomic is fp32 only (got %s); 16-bit rows take devoxelize_bwd" % gout.dtype)
         gout = _dev(gout, "grad_output", torch.float32)
         n, c = gout.shape
         gfeat = torch.empty((m, c), dtype=torch.float32, device=gout.device)
