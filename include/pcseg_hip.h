@@ -129,6 +129,25 @@ int pcs_devoxelize_bwd_f32(const float *gout, const int32_t *idx8, const float *
  * The 8 corners are accumulated in fp32 registers in k = 0..7 order and rounded to storage once. */
 int pcs_devoxelize_fwd_h(const void *feat, const int32_t *idx8, const float *w8, int64_t n, int32_t c,
                          int32_t dtype, void *out, void *stream);
+/* K9 merged with the point branch of SPVCNN (additive, still ABI v12):
+ *   R:pcseg/model/segmentor/fusion/spvcnn/spvcnn.py:417-418, 430-431, 443-444
+ *   `z_next.F = voxel_to_point(x, z).F + ReLU(BatchNorm(Linear(z.F)))` with the Linear output `lin` (n, c) given:
+ *     out[i,j]       = ( sum_{k<8, idx8[i,k] >= 0} w8[i,k] * vox[idx8[i,k], j] ) + max(0, bn(lin[i,j]))
+ *     mask bit (i,j) = [ bn(lin[i,j]) > 0 ]      word i * (c / 32) + j / 32, bit j % 32: what pcs_bn_apply_* writes and
+ *                                                pcs_bn_bwd_stats_* / pcs_bn_bwd_apply_* read (relu = 1, y = NULL)
+ *   stat = mean | invstd (2c doubles), gamma / beta (c floats or NULL) as pcs_bn_apply_* takes them, bn(x) by the same
+ *   expression. The corners are accumulated in fp32 registers from zero in k = 0..7 order as pcs_devoxelize_fwd_* does,
+ *   the BatchNorm term is added last, one rounding on the store: the fp32 result equals pcs_devoxelize_fwd_f32 +
+ *   pcs_bn_apply_f32 + an fp32 add bit for bit. No backward entry: the gradient of `out` is the dy of the BatchNorm
+ *   backward passes and the gout of pcs_devoxelize_bwd_csr_*.
+ *   c % 32 == 0 and 16-byte-aligned vox / lin / out, else PCS_EUNSUPPORTED; n == 0 is a no-op. _h: vox, lin, out in
+ *   bf16 (dtype 1) or fp16 (dtype 2), any other dtype is PCS_EINVAL. */
+int pcs_point_merge_f32(const float *vox, const int32_t *idx8, const float *w8, const float *lin, const double *stat,
+                        const float *gamma, const float *beta, int64_t n, int32_t c, float *out, uint32_t *mask,
+                        void *stream);
+int pcs_point_merge_h(const void *vox, const int32_t *idx8, const float *w8, const void *lin, const double *stat,
+                      const float *gamma, const float *beta, int64_t n, int32_t c, int32_t dtype, void *out,
+                      uint32_t *mask, void *stream);
 
 /* voxel_to_point map in one pass (R:pcseg/model/segmentor/voxel/minkunet/utils.py:69-105: floor, cat, kernel_hash
  * over the 8 cell corners, hashquery, calc_ti_weights, two transposes): coords (n, coord_ld >= 4) float = x,y,z,..,batch

@@ -341,6 +341,11 @@ class TorchCpuBackend:
             y = torch.cat([y, tail], dim=1)
         return (y, mask) if want_mask else y
 
+    def point_merge(self, vox, idx8, w8, lin, stat, gamma, beta):
+        """devoxelize(vox) + relu(bn(lin)) and the ReLU gate of the BatchNorm term as bit-mask words (csrc/pointmerge.hip)."""
+        y, mask = self.bn_apply(_cpu(lin, "input").float(), None, stat, gamma, beta, True, want_mask=True)
+        return self.devoxelize_fwd(vox, idx8, w8) + y, mask
+
     def bn_bwd_stats(self, dy, x, gate, stat, relu):
         c = x.shape[1]
         g = dy * self._gate(gate, c) if relu else dy

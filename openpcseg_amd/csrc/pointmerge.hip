@@ -1,0 +1,168 @@
+// Point-branch merge of SPVCNN -- gfx950, HBM-bound. The reference computes, three times per forward
+// (R:pcseg/model/segmentor/fusion/spvcnn/spvcnn.py:417-418, 430-431, 443-444),
+//     z_next.F = voxel_to_point(x, z).F + ReLU(BatchNorm(Linear(z.F)))
+// as a devoxelize write (K9), a BatchNorm apply pass and an elementwise add: four passes over an (N, C) point tensor.
+// Here the Linear output is read once and the merged rows are written once; the voxel rows are gathered as K9 gathers them.
+//     out[i, j]       = ( sum over k = 0..7 with idx8[i, k] >= 0 of w8[i, k] * vox[idx8[i, k], j] ) + max(0, bn(lin[i, j]))
+//     mask bit (i, j) = [ bn(lin[i, j]) > 0 ]          word i * (c / 32) + j / 32, bit j % 32 (bn_apply_kernel's layout)
+// Order of the arithmetic: the corners in fp32 registers from zero in k = 0..7 order (devoxelize_fwd_kernel), bn(x) with
+// the expression of bn_apply_kernel (norm.hip), the BatchNorm term added last, ONE rounding on the store. In fp32 that is
+// bit for bit what the three separate kernels give; in 16 bits it is one rounding where they have three.
+// Launch shape of the K9 kernels: a 256-thread workgroup covers 256/TX points, TX lanes x 16 bytes per row, grid-stride
+// over the points; the corner indices and weights of a point are loaded once per pass of the lane row (one pass up to
+// c = 256 in fp32, 512 in 16 bits). No LDS, no atomics; every output row and mask word is written exactly once.
+#include "pcs_common.h"
+
+using namespace pcs;
+
+namespace {
+
+struct F32 {};
+struct B16 {};
+struct H16 {};
+__device__ __forceinline__ float h2f(B16, uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
+__device__ __forceinline__ float h2f(H16, uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+__device__ __forceinline__ uint16_t f2h(B16, float f) {  // round to nearest even; NaN stays NaN
+  uint32_t u = __float_as_uint(f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+__device__ __forceinline__ uint16_t f2h(H16, float f) { const _Float16 h = (_Float16)f; return __builtin_bit_cast(uint16_t, h); }
+
+// one 16-byte piece of a row: 4 floats or 8 halfs, widened to fp32 registers
+template <typename ET> struct Piece;
+template <> struct Piece<F32> { static constexpr int V = 4; };
+template <> struct Piece<B16> { static constexpr int V = 8; };
+template <> struct Piece<H16> { static constexpr int V = 8; };
+
+template <int V> struct Acc { float f[V]; };
+
+__device__ __forceinline__ Acc<4> widen(F32, const uint4 &r) {
+  Acc<4> a;
+  a.f[0] = __uint_as_float(r.x); a.f[1] = __uint_as_float(r.y); a.f[2] = __uint_as_float(r.z); a.f[3] = __uint_as_float(r.w);
+  return a;
+}
+template <typename HT> __device__ __forceinline__ Acc<8> widen(HT, const uint4 &r) {
+  Acc<8> a;
+  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    a.f[2 * q] = h2f(HT{}, (uint16_t)(w[q] & 0xFFFFu));
+    a.f[2 * q + 1] = h2f(HT{}, (uint16_t)(w[q] >> 16));
+  }
+  return a;
+}
+__device__ __forceinline__ uint4 narrow(F32, const Acc<4> &a) {
+  return make_uint4(__float_as_uint(a.f[0]), __float_as_uint(a.f[1]), __float_as_uint(a.f[2]), __float_as_uint(a.f[3]));
+}
+template <typename HT> __device__ __forceinline__ uint4 narrow(HT, const Acc<8> &a) {  // the one rounding of an output element
+  uint32_t w[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) w[q] = (uint32_t)f2h(HT{}, a.f[2 * q]) | ((uint32_t)f2h(HT{}, a.f[2 * q + 1]) << 16);
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// rows are addressed in 16-byte pieces: piece j of row r of a (rows, c) tensor sits at uint4 index r * cv + j
+template <typename ET>
+__global__ void __launch_bounds__(256) point_merge_kernel(const uint4 *__restrict__ vox, const int32_t *__restrict__ idx8,
+                                                          const float *__restrict__ w8, const uint4 *__restrict__ lin,
+                                                          const double *__restrict__ stat, const float *__restrict__ gamma,
+                                                          const float *__restrict__ beta, int64_t n, int c, int cv,
+                                                          uint4 *__restrict__ out, uint32_t *__restrict__ mask) {
+  constexpr int V = Piece<ET>::V;
+  constexpr int LPW = 32 / V;  // lanes per mask word: 8 (fp32) or 4 (16 bits); cv % LPW == 0 because c % 32 == 0
+  for (int j = threadIdx.x; j < cv; j += blockDim.x) {
+    float sc[V], sh[V];  // bn(x) = fma(x, sc, sh), as bn_apply_kernel forms it
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+      const int ch = j * V + q;
+      const float invstd = (float)stat[c + ch], mean = (float)stat[ch];
+      sc[q] = invstd * (gamma ? gamma[ch] : 1.f);
+      sh[q] = (beta ? beta[ch] : 0.f) - mean * sc[q];
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.y + threadIdx.y; i < n; i += (int64_t)gridDim.x * blockDim.y) {
+      const uint4 lr = lin[i * cv + j];  // streamed row first: in flight while the corners are gathered
+      int32_t id[8];
+      float w[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { id[k] = idx8[i * 8 + k]; w[k] = w8[i * 8 + k]; }
+      Acc<V> acc;
+#pragma unroll
+      for (int q = 0; q < V; ++q) acc.f[q] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (id[k] >= 0) {
+          const Acc<V> f = widen(ET{}, vox[(int64_t)id[k] * cv + j]);
+#pragma unroll
+          for (int q = 0; q < V; ++q) acc.f[q] = fmaf(w[k], f.f[q], acc.f[q]);
+        }
+      }
+      const Acc<V> x = widen(ET{}, lr);
+      unsigned bits = 0;
+#pragma unroll
+      for (int q = 0; q < V; ++q) {
+        float t = fmaf(x.f[q], sc[q], sh[q]);
+        if (t < 0.f) t = 0.f;
+        bits |= (t > 0.f ? 1u : 0u) << q;
+        acc.f[q] += t;
+      }
+      out[i * cv + j] = narrow(ET{}, acc);
+      // LPW consecutive lanes of one row make one mask word. The groups are aligned in the wave (blockDim.x is a power
+      // of two >= LPW) and all their lanes take the same trips of both loops (cv % LPW == 0).
+      unsigned m = bits << (V * (j & (LPW - 1)));
+#pragma unroll
+      for (int o = 1; o < LPW; o <<= 1) m |= __shfl_xor(m, o, 64);
+      if ((j & (LPW - 1)) == 0) mask[i * (c >> 5) + j / LPW] = m;
+    }
+  }
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// dtype 0 fp32, 1 bf16, 2 fp16
+int point_merge_any(const char *what, int dtype, const void *vox, const int32_t *idx8, const float *w8, const void *lin,
+                    const double *stat, const float *gamma, const float *beta, int64_t n, int32_t c, void *out,
+                    uint32_t *mask, void *stream) {
+  if (n < 0 || c <= 0) { set_error("%s: bad sizes", what); return PCS_EINVAL; }
+  if (c & 31) { set_error("%s: c = %d is not a multiple of 32 (the ReLU bit mask is made of whole words)", what, (int)c); return PCS_EUNSUPPORTED; }
+  if (n == 0) return PCS_OK;
+  if (!idx8 || !w8 || !lin || !stat || !out || !mask) { set_error("%s: null pointer", what); return PCS_EINVAL; }
+  if (!aligned16(vox) || !aligned16(lin) || !aligned16(out)) {
+    set_error("%s: vox, lin and out rows must be 16-byte aligned", what);
+    return PCS_EUNSUPPORTED;
+  }
+  if (((uintptr_t)mask & 3) || ((uintptr_t)idx8 & 3) || ((uintptr_t)w8 & 3) || ((uintptr_t)stat & 7)) {
+    set_error("%s: misaligned mask / idx8 / w8 / stat", what);
+    return PCS_EINVAL;
+  }
+  const int cv = c / (dtype == 0 ? 4 : 8);
+  int tx = 1;
+  while (tx < cv && tx < 64) tx <<= 1;   // >= 4: c >= 32
+  const int ty = 256 / tx;
+  int64_t g = ceil_div(n, ty);
+  if (g > 256 * 16) g = 256 * 16;
+  const dim3 grid((unsigned)g), block(tx, ty);
+  hipStream_t st = as_stream(stream);
+  const uint4 *v = reinterpret_cast<const uint4 *>(vox), *l = reinterpret_cast<const uint4 *>(lin);
+  uint4 *o = reinterpret_cast<uint4 *>(out);
+  if (dtype == 0) hipLaunchKernelGGL(point_merge_kernel<F32>, grid, block, 0, st, v, idx8, w8, l, stat, gamma, beta, n, c, cv, o, mask);
+  else if (dtype == 1) hipLaunchKernelGGL(point_merge_kernel<B16>, grid, block, 0, st, v, idx8, w8, l, stat, gamma, beta, n, c, cv, o, mask);
+  else hipLaunchKernelGGL(point_merge_kernel<H16>, grid, block, 0, st, v, idx8, w8, l, stat, gamma, beta, n, c, cv, o, mask);
+  return check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int pcs_point_merge_f32(const float *vox, const int32_t *idx8, const float *w8, const float *lin, const double *stat,
+                                   const float *gamma, const float *beta, int64_t n, int32_t c, float *out, uint32_t *mask,
+                                   void *stream) {
+  return point_merge_any("pcs_point_merge_f32", 0, vox, idx8, w8, lin, stat, gamma, beta, n, c, out, mask, stream);
+}
+
+extern "C" int pcs_point_merge_h(const void *vox, const int32_t *idx8, const float *w8, const void *lin, const double *stat,
+                                 const float *gamma, const float *beta, int64_t n, int32_t c, int32_t dtype, void *out,
+                                 uint32_t *mask, void *stream) {
+  if (dtype != 1 && dtype != 2) { set_error("pcs_point_merge_h: dtype must be 1 (bf16) or 2 (fp16), got %d", (int)dtype); return PCS_EINVAL; }
+  return point_merge_any("pcs_point_merge_h", dtype, vox, idx8, w8, lin, stat, gamma, beta, n, c, out, mask, stream);
+}

@@ -366,3 +366,101 @@ class FusedLinear(nn.Linear):
         elif torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") in (torch.bfloat16, torch.float16):
             hd = torch.get_autocast_dtype("cuda")
         return _SkinnyLinearParts.apply(self.weight, self.bias, self._maps, hd, *parts)
+
+
+# ---- SPVCNN's point-branch merge -----------------------------------------------------------------------------------------
+def _merge_enabled():
+    import os
+    return os.environ.get("PCS_POINT_MERGE", "1") != "0"   # A/B switch: 0 = the literal three-op sequence
+
+
+def _bn_backward(ctx_cfg, saved, dy):
+    """The two backward passes of a BatchNorm + ReLU whose gate is the bit mask (no residual): -> (dx, dweight, dbias)."""
+    be = native.backend()
+    x, gate, stat, weight, count_dev = saved
+    count, sync = ctx_cfg
+    c = x.shape[1]
+    local = be.bn_bwd_stats(dy, x, gate, stat, True)
+    sums2 = local
+    if _syncing(sync):
+        sums2 = local.clone()
+        dist.all_reduce(sums2, group=_stats_group())
+    dx, _ = be.bn_bwd_apply(dy, x, gate, stat, sums2, count, weight, True, False, count_dev=count_dev)
+    dw = db = None
+    if weight is not None:  # local sums: DDP averages parameter grads
+        lw = getattr(local, "_pcs_f32", None)
+        if lw is None or lw.dtype != weight.dtype:
+            lw = local.to(weight.dtype)
+        dw, db = lw[c:], lw[:c]
+    return dx, dw, db
+
+
+class _PointMerge(Function):
+    """out = devoxelize(vox) + relu(bn(lin)) with training-mode statistics (R:pcseg/model/segmentor/fusion/spvcnn/spvcnn.py:417-418,
+    430-431, 443-444), the apply pass, the gather and the add in ONE kernel (csrc/pointmerge.hip). Statistics, all-reduce and
+    running statistics as `_FusedBN`. The gradient of `out` is both the dy of the BatchNorm backward passes (gate = the bit
+    mask the kernel wrote) and the gout of the devoxelize backward, through the CSR cached on the corner map."""
+
+    @staticmethod
+    def forward(ctx, lin, vox, idx8, w8, weight, bias, running_mean, running_var, eps, momentum, sync):
+        be = native.backend()
+        lin, vox = lin.contiguous(), vox.contiguous()
+        idx8, w8 = idx8.contiguous().int(), w8.contiguous().float()
+        n, c = lin.shape
+        sums = be.bn_stats(lin)
+        count_dev = None
+        if _syncing(sync):
+            dist.all_reduce(sums, group=_stats_group())
+            count_dev = sums[2 * c:]
+        stat = be.bn_finalize(sums, float(n), eps, momentum, running_mean, running_var, count_dev=count_dev)
+        out, mask = be.point_merge(vox, idx8, w8, lin, stat, weight, bias)
+        ctx.save_for_backward(lin, mask, stat, weight, count_dev)
+        ctx.cfg = (float(n), sync)
+        ctx.maps = (idx8, w8, vox.shape[0], vox.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        be = native.backend()
+        g = g.contiguous()
+        idx8, w8, m, vox_dtype = ctx.maps
+        dlin = dvox = dw = db = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
+            dlin, dw, db = _bn_backward(ctx.cfg, ctx.saved_tensors, g)
+        if ctx.needs_input_grad[1]:
+            dvox = be.devoxelize_bwd(g, idx8, w8, m)
+            if dvox.dtype != vox_dtype:
+                dvox = dvox.to(vox_dtype)
+        return dlin, dvox, None, None, dw, db, None, None, None, None, None
+
+
+def point_merge(bn, lin_out, vox_feats, idx8, w8):
+    """`spdevoxelize(vox_feats, idx8, w8) + relu(bn(lin_out))`: SPVCNN's point-branch merge. bn: a FusedBatchNorm (or any
+    BatchNorm1d-shaped module: weight, bias, running statistics, eps, momentum); lin_out (N, C) the point Linear's output;
+    vox_feats (M, C); idx8 / w8 (N, 8) the points' corner map. One kernel when the backend has `point_merge`, C % 32 == 0 and
+    the tensors are on the device (PCS_POINT_MERGE=0 switches it off); otherwise the literal sequence through the existing
+    fused passes -- same function, and in fp32 the same bits. Eval mode: the running statistics."""
+    from . import functional as F_
+    be = native.backend()
+    c = lin_out.shape[1]
+    sync = bool(getattr(bn, "sync", isinstance(bn, nn.SyncBatchNorm)))
+    fused = (_merge_enabled() and hasattr(be, "point_merge") and c % 32 == 0 and lin_out.dim() == 2 and
+             vox_feats.dim() == 2 and vox_feats.shape[1] == c and
+             (lin_out.is_cuda and vox_feats.is_cuda and idx8.is_cuda and w8.is_cuda or getattr(be, "name", "") == "torch-cpu") and
+             lin_out.dtype in (torch.float32, torch.bfloat16, torch.float16) and
+             vox_feats.dtype in (torch.float32, torch.bfloat16, torch.float16))
+    if bn.training:
+        if not getattr(bn, "counted_by_parent", False):
+            bn.num_batches_tracked += 1
+        if fused:
+            return _PointMerge.apply(lin_out, vox_feats, idx8, w8, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                     bn.eps, bn.momentum, sync)
+        y = _FusedBN.apply(lin_out, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, True,
+                           sync, None, None, None, None)
+        return F_.spdevoxelize(vox_feats, idx8, w8) + y
+    inv = torch.rsqrt(bn.running_var.double() + bn.eps)
+    stat = torch.cat([bn.running_mean.double(), inv]).contiguous()
+    if fused:
+        return be.point_merge(vox_feats.contiguous(), idx8.contiguous().int(), w8.contiguous().float(), lin_out.contiguous(),
+                              stat, bn.weight, bn.bias)[0]
+    return F_.spdevoxelize(vox_feats, idx8, w8) + be.bn_apply(lin_out.contiguous(), None, stat, bn.weight, bn.bias, True)

@@ -36,6 +36,8 @@ SIGNATURES = {
     "pcs_voxelize_bwd_h": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
     "pcs_devoxelize_fwd_h": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
     "pcs_devoxelize_bwd_csr_h": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
+    "pcs_point_merge_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P]),
+    "pcs_point_merge_h": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P]),
     "pcs_corner_map_f32": (c_int32, [_P, c_int32, c_int64, c_int32, _P, c_int64, _P, _P, _P]),
     "pcs_ti_weights_f32": (c_int32, [_P, c_int32, _P, c_int64, c_float, _P, _P]),
     "pcs_downsample_pack": (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, _P, _P, _P, _P]),
@@ -451,6 +453,31 @@ class HipBackend:
             _check(self.lib.pcs_devoxelize_fwd_f32(_ptr(feats), _ptr(idx8), _ptr(w8), n, c, _ptr(out),
                                                    _stream()), "pcs_devoxelize_fwd_f32")
         return out
+
+    def point_merge(self, vox, idx8, w8, lin, stat, gamma, beta):
+        """SPVCNN's point-branch merge in one pass (csrc/pointmerge.hip): out = devoxelize(vox) + relu(bn(lin)) and the ReLU
+        gate of the BatchNorm term as bn_apply's bit mask -> (out (n, c), mask (n, c / 32) int32). vox and lin both bf16 or
+        both fp16: the 16-bit entry, out in that dtype; otherwise fp32 (a 16-bit operand beside an fp32 one is cast up).
+        c % 32 == 0; stat / gamma / beta as bn_apply takes them."""
+        vox, vcode = self._pv_feats(vox, "feats")
+        lin, lcode = self._pv_feats(lin, "input")
+        if vcode != lcode:
+            vox, lin, vcode = vox.float(), lin.float(), 0
+        idx8 = _dev(idx8, "coords", torch.int32)
+        w8 = _dev(w8, "weights", torch.float32)
+        n, c = lin.shape
+        if vox.dim() != 2 or vox.shape[1] != c or idx8.shape != (n, 8) or w8.shape != (n, 8):
+            raise ValueError("openpcseg_amd: point_merge takes vox (m, c), lin (n, c), idx8 / w8 (n, 8); got %s %s %s %s"
+                             % (tuple(vox.shape), tuple(lin.shape), tuple(idx8.shape), tuple(w8.shape)))
+        out = torch.empty((n, c), dtype=lin.dtype, device=lin.device)
+        mask = torch.empty((n, c // 32), dtype=torch.int32, device=lin.device)
+        args = [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(lin), _ptr(stat), _ptr(gamma) if gamma is not None else None,
+                _ptr(beta) if beta is not None else None, n, c]
+        if vcode:
+            _check(self.lib.pcs_point_merge_h(*args, vcode, _ptr(out), _ptr(mask), _stream()), "pcs_point_merge_h")
+        else:
+            _check(self.lib.pcs_point_merge_f32(*args, _ptr(out), _ptr(mask), _stream()), "pcs_point_merge_f32")
+        return out, mask
 
     def devoxelize_bwd(self, gout, idx8, w8, m):
         """gfeat[v] = sum over (point i, corner k) with idx8[i,k] == v of w8[i,k] * gout[i].
