@@ -133,7 +133,8 @@ int pcs_devoxelize_fwd_h(const void *feat, const int32_t *idx8, const float *w8,
  *   R:pcseg/model/segmentor/fusion/spvcnn/spvcnn.py:417-418, 430-431, 443-444
  *   `z_next.F = voxel_to_point(x, z).F + ReLU(BatchNorm(Linear(z.F)))` with the Linear output `lin` (n, c) given:
  *     out[i,j]       = ( sum_{k<8, idx8[i,k] >= 0} w8[i,k] * vox[idx8[i,k], j] ) + max(0, bn(lin[i,j]))
- *     mask bit (i,j) = [ bn(lin[i,j]) > 0 ]      word i * (c / 32) + j / 32, bit j % 32: what pcs_bn_apply_* writes and
+ *     mask bit (i,j) = [ bn(lin[i,j]) rounded to the storage type > 0 ]      word i * (c / 32) + j / 32, bit j % 32:
+ *                                                what pcs_bn_apply_* writes (the gate of its STORED y) and
  *                                                pcs_bn_bwd_stats_* / pcs_bn_bwd_apply_* read (relu = 1, y = NULL)
  *   stat = mean | invstd (2c doubles), gamma / beta (c floats or NULL) as pcs_bn_apply_* takes them, bn(x) by the same
  *   expression. The corners are accumulated in fp32 registers from zero in k = 0..7 order as pcs_devoxelize_fwd_* does,
@@ -418,8 +419,16 @@ int pcs_range_sample_bwd_csr_f32(const float *gout, const int64_t *order, const 
  *   single process, statistics from the convolution's write-back: pcs_bn_reduce_partials_finalize = pcs_bn_reduce_partials +
  *             pcs_bn_finalize_f32 (count = n) in one launch (ABI v7; `sums` may be NULL there).
  * partial_ws: pcs_bn_num_partials() * 2 * c floats.
- * mask (optional, c % 32 == 0): n * c/32 words written by the apply pass, bit = [y > 0]; handed to the two backward
+ * mask (optional, c % 32 == 0): n * c/32 words written by the apply pass, bit = [y > 0] of y AS STORED (in fp16 a
+ *   pre-activation in (0, 2^-25] stores as 0 and its bit is clear: the mask and the y form of backward always agree, so
+ *   a layer's gradient does not depend on whether its width is a multiple of 32); handed to the two backward
  *   passes instead of y (then y may be NULL) -- the ReLU gate costs 1/32 of a tensor read instead of a whole one.
+ * n == 0 (an empty tensor; under SyncBN a rank without rows still takes part in the all-reduce): every entry that
+ *   takes n returns PCS_OK and the tensor pointers may be NULL -- the stats entries leave sums = 0 with count 0
+ *   (sums2 = 0); pcs_bn_reduce_partials(_finalize) accept nrows == 0 with a NULL `partial` (zero sums) and _finalize
+ *   reads n == 0 as count 1; the apply entries launch nothing, and pcs_bn_bwd_apply_* return before they look at
+ *   `count`. With n > 0 a NULL tensor is PCS_EINVAL, and so is a host `count` that is not positive without a count_dev.
+ *   pcs_bn_finalize_f32 takes no n: it wants a positive host `count` or a count_dev, and reads a DEVICE count of 0 as 1.
  */
 int32_t pcs_bn_num_partials(void);
 int pcs_bn_stats_f32(const float *x, int64_t n, int32_t c, float *partial_ws, double *sums, void *stream);

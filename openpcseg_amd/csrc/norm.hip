@@ -55,6 +55,10 @@ template <typename HT> __device__ __forceinline__ void stv(HT, void *p, int64_t 
   reinterpret_cast<uint16_t *>(p)[e] = f2h(HT{}, v);
 }
 
+// the value a store leaves in memory, read back: what a later `y > 0` sees (fp16 rounds (0, 2^-25] to 0)
+__device__ __forceinline__ float stored(F32, float f) { return f; }
+template <typename HT> __device__ __forceinline__ float stored(HT, float f) { return h2f(HT{}, f2h(HT{}, f)); }
+
 template <int V> struct NV;
 template <> struct NV<4> { using T = float4; };
 template <> struct NV<1> { using T = float; };
@@ -266,17 +270,18 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const void *__restrict__ 
       const VT xv = ldv<V>(ET{}, x, i * c + (int64_t)j * V);
       VT rv; if (res) rv = ldv<V>(ET{}, res, i * c + (int64_t)j * V);
       VT o;
-      unsigned bits = 0;
 #pragma unroll
       for (int q = 0; q < V; ++q) {
         float t = fmaf(comp(xv, q), sc[q], sh[q]);
         if (res) t += comp(rv, q);
         if (relu && t < 0.f) t = 0.f;
-        bits |= (t > 0.f ? 1u : 0u) << q;
         setc(o, q, t);
       }
       stv(ET{}, y, i * ldy + (int64_t)j * V, o);
       if (V == 4 && mask) {  // c % 32 == 0: 8 consecutive lanes (4 channels each) of one row make one word
+        unsigned bits = 0;   // the gate of the STORED y: the mask and y forms of backward agree
+#pragma unroll
+        for (int q = 0; q < V; ++q) bits |= (stored(ET{}, comp(o, q)) > 0.f ? 1u : 0u) << q;
         unsigned m = bits << (4 * (j & 7));
         m |= __shfl_xor(m, 1, 64); m |= __shfl_xor(m, 2, 64); m |= __shfl_xor(m, 4, 64);
         if ((j & 7) == 0) mask[i * (c >> 5) + (j >> 3)] = m;
@@ -416,10 +421,11 @@ static int bn_bwd_apply_any(int dtype, const void *dy, const void *x, const void
                             const double *stat, const double *sums2, double count, const double *count_dev,
                             const float *w, int64_t n, int32_t c, int32_t relu, void *dx, void *dres, int64_t lddy,
                             void *stream, float in_slope = 1.f) {
-  if (n < 0 || c <= 0 || (!count_dev && !(count > 0))) { set_error("pcs_bn_bwd_apply: bad sizes"); return PCS_EINVAL; }
+  if (n < 0 || c <= 0) { set_error("pcs_bn_bwd_apply: bad sizes"); return PCS_EINVAL; }
+  if (n == 0) return PCS_OK;   // before the count: an empty tensor has none
+  if (!count_dev && !(count > 0)) { set_error("pcs_bn_bwd_apply: count must be positive"); return PCS_EINVAL; }
   if (lddy == 0) lddy = c;
   if (lddy < c) { set_error("pcs_bn_bwd_apply: row stride of dy smaller than c"); return PCS_EINVAL; }
-  if (n == 0) return PCS_OK;
   if (!dy || !x || !stat || !sums2 || !dx || (relu && !y && !mask)) { set_error("pcs_bn_bwd_apply: null pointer"); return PCS_EINVAL; }
   hipStream_t st = as_stream(stream);
   const bool vec = (c & 3) == 0 && (lddy & 3) == 0 && al_v4(dtype, dy) && al_v4(dtype, x) && al_v4(dtype, y) && al_v4(dtype, dx) && al_v4(dtype, dres);
@@ -436,19 +442,20 @@ static int bn_bwd_apply_any(int dtype, const void *dy, const void *x, const void
 
 static bool bad_half(int32_t dtype) { return dtype != 1 && dtype != 2; }
 
+// n == 0 (a rank with an empty shard under SyncBN): the tensors may be NULL, the sums are zero with count 0
 extern "C" int pcs_bn_stats_f32(const float *x, int64_t n, int32_t c, float *partial_ws, double *sums, void *stream) {
-  if (n < 0 || c <= 0 || !x || !partial_ws || !sums) { set_error("pcs_bn_stats: bad args"); return PCS_EINVAL; }
+  if (n < 0 || c <= 0 || (n > 0 && !x) || !partial_ws || !sums) { set_error("pcs_bn_stats: bad args"); return PCS_EINVAL; }
   return bn_partial(false, 0, x, nullptr, nullptr, nullptr, nullptr, n, c, 0, partial_ws, sums, as_stream(stream));
 }
 extern "C" int pcs_bn_stats_h(const void *x, int64_t n, int32_t c, int32_t dtype, float *partial_ws, double *sums, void *stream) {
-  if (n < 0 || c <= 0 || !x || !partial_ws || !sums || bad_half(dtype)) { set_error("pcs_bn_stats_h: bad args"); return PCS_EINVAL; }
+  if (n < 0 || c <= 0 || (n > 0 && !x) || !partial_ws || !sums || bad_half(dtype)) { set_error("pcs_bn_stats_h: bad args"); return PCS_EINVAL; }
   return bn_partial(false, dtype, x, nullptr, nullptr, nullptr, nullptr, n, c, 0, partial_ws, sums, as_stream(stream));
 }
 
 // sums (2c + 1) from the per-tile double partials a fused convolution left in its write-back
 // (pcs_conv_gather_gemm_*'s bn_partial: [nrows][2][c] raw sums) -- replaces the pcs_bn_stats_* pass over the tensor
 extern "C" int pcs_bn_reduce_partials(const double *partial, int64_t nrows, int32_t c, int64_t n, double *sums, void *stream) {
-  if (nrows < 0 || nrows > 0x7FFFFFFF || c <= 0 || n < 0 || !partial || !sums) { set_error("pcs_bn_reduce_partials: bad args"); return PCS_EINVAL; }
+  if (nrows < 0 || nrows > 0x7FFFFFFF || c <= 0 || n < 0 || (nrows > 0 && !partial) || !sums) { set_error("pcs_bn_reduce_partials: bad args"); return PCS_EINVAL; }
   hipLaunchKernelGGL(bn_reduce_kernel<double>, dim3((unsigned)ceil_div(c, kRedCh)), dim3(kRedCh, kRedLanes), 0, as_stream(stream), partial,
                      (int)nrows, c, (const float *)nullptr, n, sums, 1, (float *)nullptr, (double *)nullptr, 0.0, 0.0,
                      (float *)nullptr, (float *)nullptr);
@@ -456,11 +463,11 @@ extern "C" int pcs_bn_reduce_partials(const double *partial, int64_t nrows, int3
 }
 
 // the same reduction with pcs_bn_finalize_f32 (count = n) in its tail: stat (2c) from the convolution's partials in ONE launch.
-// sums (2c + 1) may be NULL. Not for SyncBN (the sums of all ranks must be added between the two steps).
+// sums (2c + 1) may be NULL. No partial rows (nrows == 0, then `partial` may be NULL) give zero sums; n == 0 is read as count 1. Not for SyncBN (the sums of all ranks must be added between the two steps).
 extern "C" int pcs_bn_reduce_partials_finalize(const double *partial, int64_t nrows, int32_t c, int64_t n, double eps,
                                                double momentum, float *running_mean, float *running_var, double *sums,
                                                double *stat, void *stream) {
-  if (nrows < 0 || nrows > 0x7FFFFFFF || c <= 0 || n <= 0 || !partial || !stat || (!running_mean) != (!running_var)) {
+  if (nrows < 0 || nrows > 0x7FFFFFFF || c <= 0 || n < 0 || (nrows > 0 && !partial) || !stat || (!running_mean) != (!running_var)) {
     set_error("pcs_bn_reduce_partials_finalize: bad args");
     return PCS_EINVAL;
   }
@@ -493,14 +500,14 @@ extern "C" int pcs_bn_apply_h(const void *x, const void *res, const double *stat
 extern "C" int pcs_bn_bwd_stats_f32(const float *dy, const float *x, const float *y, const uint32_t *mask,
                                     const double *stat, int64_t n, int32_t c, int32_t relu, float *partial_ws,
                                     double *sums2, int64_t sums2_doubles, int64_t lddy, void *stream) {
-  if (n < 0 || c <= 0 || !dy || !x || !stat || !partial_ws || !sums2 || (relu && !y && !mask)) { set_error("pcs_bn_bwd_stats: bad args"); return PCS_EINVAL; }
+  if (n < 0 || c <= 0 || (n > 0 && (!dy || !x || (relu && !y && !mask))) || !stat || !partial_ws || !sums2) { set_error("pcs_bn_bwd_stats: bad args"); return PCS_EINVAL; }
   if (sums2_doubles < 3 * (int64_t)c) { set_error("pcs_bn_bwd_stats: sums2 must hold 3c doubles (2c sums + the same 2c values as floats)"); return PCS_EWORKSPACE; }
   return bn_partial(true, 0, x, dy, y, mask, stat, n, c, relu, partial_ws, sums2, as_stream(stream), lddy);
 }
 extern "C" int pcs_bn_bwd_stats_h(const void *dy, const void *x, const void *y, const uint32_t *mask,
                                   const double *stat, int64_t n, int32_t c, int32_t relu, int32_t dtype, float *partial_ws,
                                   double *sums2, int64_t sums2_doubles, int64_t lddy, void *stream) {
-  if (n < 0 || c <= 0 || !dy || !x || !stat || !partial_ws || !sums2 || (relu && !y && !mask) || bad_half(dtype)) { set_error("pcs_bn_bwd_stats_h: bad args"); return PCS_EINVAL; }
+  if (n < 0 || c <= 0 || (n > 0 && (!dy || !x || (relu && !y && !mask))) || !stat || !partial_ws || !sums2 || bad_half(dtype)) { set_error("pcs_bn_bwd_stats_h: bad args"); return PCS_EINVAL; }
   if (sums2_doubles < 3 * (int64_t)c) { set_error("pcs_bn_bwd_stats_h: sums2 must hold 3c doubles (2c sums + the same 2c values as floats)"); return PCS_EWORKSPACE; }
   return bn_partial(true, dtype, x, dy, y, mask, stat, n, c, relu, partial_ws, sums2, as_stream(stream), lddy);
 }

@@ -4,7 +4,7 @@
 // as a devoxelize write (K9), a BatchNorm apply pass and an elementwise add: four passes over an (N, C) point tensor.
 // Here the Linear output is read once and the merged rows are written once; the voxel rows are gathered as K9 gathers them.
 //     out[i, j]       = ( sum over k = 0..7 with idx8[i, k] >= 0 of w8[i, k] * vox[idx8[i, k], j] ) + max(0, bn(lin[i, j]))
-//     mask bit (i, j) = [ bn(lin[i, j]) > 0 ]          word i * (c / 32) + j / 32, bit j % 32 (bn_apply_kernel's layout)
+//     mask bit (i, j) = [ bn(lin[i, j]) rounded to the storage type > 0 ]          word i * (c / 32) + j / 32, bit j % 32 (bn_apply_kernel's layout)
 // Order of the arithmetic: the corners in fp32 registers from zero in k = 0..7 order (devoxelize_fwd_kernel), bn(x) with
 // the expression of bn_apply_kernel (norm.hip), the BatchNorm term added last, ONE rounding on the store. In fp32 that is
 // bit for bit what the three separate kernels give; in 16 bits it is one rounding where they have three.
@@ -29,6 +29,10 @@ __device__ __forceinline__ uint16_t f2h(B16, float f) {  // round to nearest eve
   return (uint16_t)(u >> 16);
 }
 __device__ __forceinline__ uint16_t f2h(H16, float f) { const _Float16 h = (_Float16)f; return __builtin_bit_cast(uint16_t, h); }
+
+// bn(x) as pcs_bn_apply_* would store it, read back: the ReLU gate of the mask is that of the stored value
+__device__ __forceinline__ float stored(F32, float f) { return f; }
+template <typename HT> __device__ __forceinline__ float stored(HT, float f) { return h2f(HT{}, f2h(HT{}, f)); }
 
 // one 16-byte piece of a row: 4 floats or 8 halfs, widened to fp32 registers
 template <typename ET> struct Piece;
@@ -104,7 +108,7 @@ __global__ void __launch_bounds__(256) point_merge_kernel(const uint4 *__restric
       for (int q = 0; q < V; ++q) {
         float t = fmaf(x.f[q], sc[q], sh[q]);
         if (t < 0.f) t = 0.f;
-        bits |= (t > 0.f ? 1u : 0u) << q;
+        bits |= (stored(ET{}, t) > 0.f ? 1u : 0u) << q;  // pcs_bn_apply_*'s bit; the sum below keeps its one rounding
         acc.f[q] += t;
       }
       out[i * cv + j] = narrow(ET{}, acc);

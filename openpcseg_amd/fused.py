@@ -85,7 +85,8 @@ class _FusedBN(Function):
         n, c = x.shape
         # [sum x | sum x^2 | n]: handed over by the producing convolution (its write-back computed them), else one pass
         syncing = _syncing(sync)
-        count, count_dev, stat = float(n), None, None
+        # an empty tensor (a rank without voxels): count read as 1, as the kernels read a zero device count
+        count, count_dev, stat = float(max(n, 1)), None, None
         raw = pre is not None and pre.numel() != 2 * c + 1 and pre.numel() > 0 and pre.numel() % (2 * c) == 0
         if raw and not syncing and n > 0:
             # the producing convolution's per-tile partials: reduction and finalize in one launch (nothing to all-reduce)

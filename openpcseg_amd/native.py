@@ -1101,7 +1101,8 @@ class HipBackend:
 
     def bn_apply(self, x, res, stat, w, b, relu, want_mask=False, tail=None):
         """y = act((x - mean) * invstd * w + b [+ res]) in x's dtype (fp32 / bf16 / fp16). want_mask (c % 32 == 0): also
-        the ReLU gate as n x c/32 int32 words (bit ch % 32 of word ch / 32 = [y > 0]) -- what the backward passes read
+        the ReLU gate as n x c/32 int32 words (bit ch % 32 of word ch / 32 = [y > 0] of y as stored, so that the mask
+        and y itself always give the same gate) -- what the backward passes read
         instead of y. tail (n, ct): concat fusion -- the result is the (n, c + ct) tensor cat([y, tail], 1), y written
         straight into its left columns and `tail` copied to the right ones by the same launch."""
         x = self._feat(x, "input")

@@ -13,7 +13,9 @@ A = sum_k |w_k vox_k| + (|lin| + |mean|) |invstd gamma| + |beta|:
              lower figures are reached only at the top of a binade, and a correctly rounded store exceeds them by up to 2x
              (measured on MI355X: worst error 1.62x of 16 * 2^-24 * A + 2^-9 |y64| at the first bf16 case, the stored value being
              the nearest bf16 number), so the bound is the exact half ulp, not a fixed fraction of |y64|
-    mask:    equals [bn64 > 0] wherever |bn64| exceeds the fp32 bound; at most 0.1 % of the elements may be excluded that way
+    mask:    the bit is the gate of the BatchNorm term AS pcs_bn_apply_* WOULD STORE IT, [round_storage(bn) > 0] (fp16 rounds a
+             term in (0, 2^-25] to 0: bit clear), so the backward passes see the gate they see after the literal sequence;
+             equals [bn64 > 0] wherever |bn64| exceeds the fp32 bound; at most 0.1 % of the elements may be excluded that way
 
 In fp32 the kernel must also reproduce the three operations it replaces bit for bit (same summation order)."""
 import ctypes
@@ -369,3 +371,30 @@ def test_mixed_dtypes_and_eval_mode(hip):
     y64, bn64, A = oracle(idx8, w8, vox.astype(np.float64), lin.astype(np.float64), np.concatenate([rm, 1 / np.sqrt(rv + bn.eps)]), gamma, beta)
     assert (np.abs(got.cpu().numpy() - y64) <= 16 * U24 * A).all()
     assert int(bn.num_batches_tracked) == 0
+
+
+@pytest.mark.gpu
+def test_mask_bit_is_the_gate_of_the_stored_batchnorm_term(hip):
+    """One fp16 element whose BatchNorm term is positive in fp32 and would store as 0 (lin = mean = 0, beta = 2^-26): its mask
+    bit is clear, as in the mask pcs_bn_apply_h writes for the same input; the merged output still adds the unrounded term
+    (one rounding). In fp32 and bf16 the term survives the store and the bit is set."""
+    n, m, c = 4, 3, 32
+    idx8 = np.full((n, 8), -1, dtype=np.int32)
+    idx8[:, 0] = [0, 1, 2, 0]
+    w8 = np.full((n, 8), 0.5, dtype=np.float32)
+    vox = np.arange(m * c, dtype=np.float32).reshape(m, c) / 8
+    lin = np.zeros((n, c), dtype=np.float32)
+    stat = np.concatenate([np.zeros(c), np.ones(c)])
+    beta = np.ones(c, dtype=np.float32)
+    beta[:4] = [2.0 ** -26, 2.0 ** -25, 2.0 ** -24, 1.5 * 2.0 ** -25]   # fp16: 0, 0 (tie to even), 2^-24, 2^-24
+    for dtype, on in [(torch.float16, [False, False, True, True]), (torch.float32, [True] * 4), (torch.bfloat16, [True] * 4)]:
+        vt, v64 = stored(vox, dtype)
+        lt, l64 = stored(lin, dtype)
+        out, mask = hip.point_merge(dev(vt), dev(idx8), dev(w8), dev(lt), dev(stat), None, dev(beta))
+        y, ymask = hip.bn_apply(dev(lt), None, dev(stat), None, dev(beta), True, want_mask=True)
+        assert torch.equal(mask, ymask), dtype
+        bits = mask_bits(mask, c)
+        assert np.array_equal(bits, y.float().cpu().numpy() > 0), dtype
+        assert bits[:, :4].tolist() == [on] * n and bits[:, 4:].all(), dtype
+        y64, bn64, A = oracle(idx8, w8, v64, l64, stat, np.ones(c, dtype=np.float32), beta)
+        assert (np.abs(out.float().cpu().numpy() - y64) <= 16 * U24 * A + half_ulp(y64, dtype)).all(), dtype
