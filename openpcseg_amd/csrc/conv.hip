@@ -134,7 +134,7 @@ extern "C" int32_t pcs_conv_pick_tile_rows_dt(int64_t n_dst, int64_t n_pairs, in
   double best_cost = launch_cost(n_dst, 128, ncol, ppr, K) * 0.97;
   for (int T = 80; T <= 192; T += 16) {
     if (T == 128) continue;
-    if (2 * conv5_lds_est(T, nctt) > 160 * 1024) continue;  // keep two workgroups per CU
+    if (conv_nw8(T, nctt)) continue;  // keep two workgroups per CU
     const double c = launch_cost(n_dst, T, ncol, ppr, K);
     if (c < best_cost) { best = T; best_cost = c; }
   }
@@ -153,13 +153,13 @@ extern "C" int32_t pcs_conv_emits_bn_partials(int32_t cin, int32_t cout, int32_t
   if (dtype == 0) {
     if (conv5_applies(cin, cout, K)) {
       nctt = conv5_nctt(cout, tile_rows);
-      nt = 2 * conv5_lds_est(tile_rows, nctt) > 160 * 1024 ? 512 : 256;
+      nt = conv_nw8(tile_rows, nctt) ? 512 : 256;
     } else if (tile_rows != 64 && tile_rows != 128) {
       return 0;
     }
   } else {
     if (!convh_applies(cin, cout, K)) return 0;
-    nt = 2 * conv5_lds_est(tile_rows, nctt) > 160 * 1024 ? 512 : 256;
+    nt = conv_nw8(tile_rows, nctt) ? 512 : 256;
   }
   return conv_stats_fit(tile_rows, 16 * nctt, nt) ? 1 : 0;
 }
@@ -192,7 +192,6 @@ extern "C" int pcs_conv_gather_gemm_f32_ex(const float *src, int64_t n_src, int3
                                            const int32_t *seg, int32_t tile_rows, int64_t n_dst,
                                            const float *bias, const pcs_conv_epilogue *ep, float *dst, double *bn_partial,
                                            const int32_t *tile_order, void *stream) {
-  const float *addend = ep ? reinterpret_cast<const float *>(ep->addend) : nullptr;
   if (cin <= 0 || cout <= 0 || K <= 0 || n_dst < 0 || n_src < 0 || (src_col != 0 && src_col != 1)) {
     set_error("pcs_conv_gather_gemm_f32: bad sizes");
     return PCS_EINVAL;
@@ -205,11 +204,9 @@ extern "C" int pcs_conv_gather_gemm_f32_ex(const float *src, int64_t n_src, int3
   a.n_dst = n_dst; a.ntiles = ceil_div(n_dst, tile_rows); a.tile_rows = tile_rows;
   a.cin = cin; a.cout = cout; a.K = K; a.src_col = src_col; a.ncoltiles = 1; a.stats = bn_partial;
   a.order = tile_order;
-  a.addend = addend;
-  if (addend && ((uintptr_t)addend & 15)) { set_error("pcs_conv_gather_gemm_f32_ex: misaligned addend"); return PCS_EINVAL; }
-  if (ep && ep->act_slope != 0.f && ep->act_slope != 1.f) a.act_slope = ep->act_slope;
-  if (ep && (ep->flags & ~PCS_EP_RELU)) { set_error("pcs_conv_gather_gemm_f32_ex: unknown pcs_conv_epilogue.flags bits"); return PCS_EINVAL; }
-  if (ep && (ep->flags & PCS_EP_RELU)) a.act_slope = 0.f;   // ReLU = the kernels' LeakyReLU branch with slope 0
+  const void *addend = nullptr;
+  if (conv_decode_epilogue(ep, "pcs_conv_gather_gemm_f32_ex", 16, addend, a.act_slope) != PCS_OK) return PCS_EINVAL;
+  a.addend = reinterpret_cast<const float *>(addend);
   if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, 0)) {
     set_error("pcs_conv_gather_gemm_f32: this shape / tile height does not produce BatchNorm partials (ask pcs_conv_emits_bn_partials)");
     return PCS_EUNSUPPORTED;

@@ -1,5 +1,6 @@
 // Shared by the fused-convolution translation units (conv.hip = picker + C entry point, conv_block.hip = generic
-// block-synchronous kernel, conv_wave4.hip / conv_wave5.hip = wave-autonomous kernels, conv_wgrad.hip = weight gradient).
+// block-synchronous kernel, conv_wave*.hip = wave-autonomous kernels, conv_wgrad.hip = weight gradient). The skeleton the wave
+// kernels share (tile mapping, offset lists, commit, launch) is conv_wave_common.h.
 #pragma once
 #include <stdlib.h>
 
@@ -66,15 +67,11 @@ __device__ __forceinline__ uint16_t f2h(Fp16, float f) {
 }
 
 constexpr size_t kMaxDynLds = 160 * 1024 - 256;  // per-workgroup LDS ceiling of a gfx950 CU, minus the static part
-// the sink row below the accumulator tile of the wave kernels (the padding rows of a row block commit into it) and the
-// LDS estimate every launch-shape decision shares (tile + offset lists + slack)
-constexpr int kConvSinkRows = 1;
-inline size_t conv5_lds_est(int tile_rows, int nctt) { return (size_t)((tile_rows + kConvSinkRows) * (16 * nctt + 4)) * 4 + 1024; }
 
 // 16-column MFMA tiles per column tile of the wave kernels: 1, 2, 3, 4, 6 or 8. Up to 128 output columns are one
 // column tile; wider outputs take the width in {8, 6, 4} that pads the fewest columns (ties: the widest) -- 256 -> 8,
 // 192 -> 6, and the cr 1.75 widths 168 -> 6 (192), 224 -> 8 (256), 336 -> 8 (384), 448 -> 4 (448), 672 -> 6 (672).
-// The fragment order of the prepared half weights is defined by this function (conv_wave5h.hip).
+// The fragment order of the prepared half weights is defined by this function (conv_wfrag_values, conv_wave_common.h).
 inline int conv_nctt(int cout) {
   int nctt = (cout + 15) / 16;
   if (nctt <= 8) {

@@ -1,7 +1,7 @@
 // Shared by the 16-bit-MFMA fused-convolution code: conv_wave5h.hip (wave-autonomous row-block groups, ticket commit),
 // conv_wave6h.hip (weight-stationary ranges) and weights_multi.hip. They read the same prepared weights (MFMA fragment order, pcs_conv_prepare_weights_h) and share the tile epilogue of conv_common.h.
 #pragma once
-#include "conv_common.h"
+#include "conv_wave_common.h"
 
 namespace pcs {
 
@@ -13,15 +13,6 @@ __device__ __forceinline__ f32x4 mfma_h(Bf16, const uint4 &a, const uint4 &b, f3
 }
 __device__ __forceinline__ f32x4 mfma_h(Fp16, const uint4 &a, const uint4 &b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-// local column (inside a CT-wide column tile) that lane n of 16-column tile tl feeds -- the interleave the commit and
-// the epilogue of the wave kernels assume (quads of 4 tiles: 64 q + 4 n + f; a pair: + 2 n + f; a single: + n)
-__host__ __device__ inline int h_local_col(int nctt, int tl, int n) {
-  const int n4 = nctt / 4, n2 = (nctt % 4) / 2;
-  if (tl < 4 * n4) return 64 * (tl / 4) + 4 * n + (tl % 4);
-  if (tl < 4 * n4 + 2 * n2) return 64 * n4 + 2 * n + (tl - 4 * n4);
-  return 64 * n4 + 32 * n2 + n;
 }
 
 struct ConvArgsH {

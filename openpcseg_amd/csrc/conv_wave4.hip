@@ -1,6 +1,6 @@
 // Wave-autonomous fused convolution, one row block per wave step ("wave4"): serves the 16-byte-granular shapes the
 // wave5 kernel does not take (cin < 64 or cin % 32 != 0, odd column-tile counts).
-#include "conv_common.h"
+#include "conv_wave_common.h"
 
 using namespace pcs;
 
@@ -48,16 +48,10 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os4_kernel(ConvArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // a scalar: wave-level loops and branches stay uniform
   const int g = lane >> 4, l15 = lane & 15;
-  // XCD-aware tile mapping: workgroup b runs on XCD b % 8 (observed dispatch order, speed only).
-  // Give every XCD one CONTIGUOUS range of tiles so that neighbouring tiles -- which gather
-  // overlapping src rows -- share that XCD's L2 (bijective remap for any grid size).
-  unsigned bid = blockIdx.x;
-  {
-    const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int64_t tile = bid / a.ncoltiles;
-  const int ctile = bid % a.ncoltiles;
+  // every XCD takes one contiguous range of tiles (conv_wave_common.h); a.order is not read: row order, unpadded grid
+  int64_t tile;
+  int ctile;
+  conv_block_slot<true, false>(a, tile, ctile);
   const int n0 = ctile * C::CT;
   const int64_t row0 = tile * T;
   const int64_t nt1 = a.ntiles + 1;
@@ -275,37 +269,15 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os4_kernel(ConvArgs a) {
   float *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
-                                   [&](int r, int cq, const float4 &v0) {
-                                     float4 v = v0;
-                                     if (a.addend) {  // kernel argument: uniform
-                                       const float4 ad = *reinterpret_cast<const float4 *>(a.addend + (row0 + r) * (int64_t)ldd + n0 + cq);
-                                       v.x += ad.x; v.y += ad.y; v.z += ad.z; v.w += ad.w;
-                                     }
-                                     if (a.act_slope != 1.f) {
-                                       v.x = v.x < 0.f ? v.x * a.act_slope : v.x; v.y = v.y < 0.f ? v.y * a.act_slope : v.y;
-                                       v.z = v.z < 0.f ? v.z * a.act_slope : v.z; v.w = v.w < 0.f ? v.w * a.act_slope : v.w;
-                                     }
-                                     *reinterpret_cast<float4 *>(drow + (int64_t)r * ldd + cq) = v;
-                                     return v;
-                                   });
+                                   ConvStoreF32{drow, a.addend, row0, n0, ldd, a.act_slope});
 }
 
 template <int NCTT, int T, int NW, int MINW>
 int launch_conv4_cfg(const ConvArgs &a, hipStream_t st) {
   using C = Conv4Cfg<NCTT, T, NW>;
-  const int64_t nblocks = a.ntiles * a.ncoltiles;
-  if (nblocks <= 0) return PCS_OK;
-  if (nblocks > 0x7FFFFFFF) { set_error("pcs_conv: grid too large"); return PCS_EUNSUPPORTED; }
-  const bool e32 = (a.cin % 32) == 0;
-  auto kern = e32 ? conv_os4_kernel<NCTT, T, true, NW, MINW> : conv_os4_kernel<NCTT, T, false, NW, MINW>;
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[e32]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::lds_bytes);
-    attr_set[e32] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(C::NT), C::lds_bytes, st, a);
-  return check_launch("pcs_conv_gather_gemm_f32(wave4)");
+  constexpr const char *who = "pcs_conv", *label = "pcs_conv_gather_gemm_f32(wave4)";
+  if (a.cin % 32 == 0) return conv_wave_launch<conv_os4_kernel<NCTT, T, true, NW, MINW>>(a, false, C::NT, C::lds_bytes, st, who, label);
+  return conv_wave_launch<conv_os4_kernel<NCTT, T, false, NW, MINW>>(a, false, C::NT, C::lds_bytes, st, who, label);
 }
 
 

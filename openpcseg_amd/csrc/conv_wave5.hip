@@ -1,5 +1,5 @@
 // Wave-autonomous fused convolution with row-block groups ("wave5"): the kernel behind every >= 64-channel layer.
-#include "conv_common.h"
+#include "conv_wave_common.h"
 
 using namespace pcs;
 
@@ -23,97 +23,29 @@ constexpr int kTraceBlocks = 8192;
 // and an odd number of blocks ends the group one pipeline stage early (the next group's first block lands in the
 // other register set and is moved over).
 // ================================================================================================
-template <int NCTT, int NW_, int R_>
-struct Conv5Cfg {
-  static constexpr int NW = NW_;
-  static constexpr int R = R_;
-  static constexpr int NT = 64 * NW;
-  static constexpr int CT = 16 * NCTT;
-  static constexpr int ACS = CT + 4;
-  static constexpr int N4 = NCTT / 4;
-  static constexpr int N2 = (NCTT % 4) / 2;
-  static constexpr int N1 = NCTT % 2;
-  static constexpr int NWL = N4 + N2 + N1;  // W loads per contraction step
-  static constexpr int SINK = kConvSinkRows;
-  static constexpr size_t lds_bytes(int T) { return (size_t)((T + SINK) * ACS) * 4 + 5 * 33 * 4 + 16; }
-};
-
 template <int NCTT, int NW, int MINW, int R, bool TAIL>
 __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
-  using C = Conv5Cfg<NCTT, NW, R>;
+  using C = ConvWaveCfg<NCTT, NW, R>;
   const int T = a.tile_rows;  // any multiple of 16: the host picks it per layer (pcs_conv_pick_tile_rows)
   PCS_T(const long long tr_entry = wall_clock64(); long long tr_loop = 0, tr_ticket = 0, tr_commit = 0; int tr_groups = 0;)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *acc_l = reinterpret_cast<float *>(smem);            // [T+SINK][ACS], rows >= T = sink for padding rows
-  int *kl_k = reinterpret_cast<int *>(acc_l + (T + C::SINK) * C::ACS);  // [32] offset id
-  int *kl_s = kl_k + 32;                                     // [32] first pair
-  int *kl_m = kl_s + 32;                                     // [32] #pairs
-  int *kl_g = kl_m + 32;                                     // [33] first FULL group (prefix over the offsets)
-  int *kl_h = kl_g + 33;                                     // [33] first partial group (prefix)
-  int *commit = kl_h + 33;
-  const unsigned commit_lds = (unsigned)(size_t)(__attribute__((address_space(3))) int *)commit;  // LDS byte address
-  const unsigned acc_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float *)acc_l;
-  __shared__ int nk_s;
+  const ConvTileLds tl = conv_tile_lds<C, true>(smem, T);
+  float *acc_l = tl.acc;
+  int *commit = tl.commit;
+  const unsigned commit_lds = tl.commit_lds, acc_lds = tl.acc_lds;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // a scalar: wave-level loops and branches stay uniform
   const int g = lane >> 4, l15 = lane & 15;
-  unsigned bid = blockIdx.x;
-  if (!a.order) {  // row order: one contiguous tile range per XCD; heaviest-first order: dealt round-robin
-    const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int64_t slot = bid / a.ncoltiles;
-  int ctile = bid % a.ncoltiles;
-  if (a.order) {  // the column tiles of one row tile on ONE XCD, back to back (they gather the same A rows)
-    const unsigned xcd = bid & 7, idx = bid >> 3;
-    slot = (int64_t)(idx / a.ncoltiles) * 8 + xcd;
-    ctile = idx % a.ncoltiles;
-    if (slot >= a.ntiles) return;  // the grid is padded to 8 * ncoltiles
-  }
+  int64_t slot;
+  int ctile;
+  conv_block_slot<true>(a, slot, ctile);
+  if (a.order && slot >= a.ntiles) return;  // the grid of an ordered launch is padded to 8 * ncoltiles
   const int64_t tile = a.order ? (int64_t)a.order[slot] : slot;
   const int n0 = ctile * C::CT;
   const int64_t row0 = tile * T;
-  const int64_t nt1 = a.ntiles + 1;
-
-  if (wid == 0) {  // non-empty offsets of this tile + prefix of their row-block groups
-    const int k = lane;
-    int s0 = 0, m = 0;
-    if (k < a.K) {
-      s0 = a.seg[(int64_t)k * nt1 + tile];
-      m = a.seg[(int64_t)k * nt1 + tile + 1] - s0;
-    }
-    const unsigned long long mask = __ballot(m > 0);
-    const int nrb = (m + 15) >> 4;
-    const int nfull = nrb / R, npart = (nrb % R) ? 1 : 0;  // groups of R row blocks + at most one shorter group
-    int incl = nfull | (npart << 16);                       // both prefixes in one scan
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (m > 0) {
-      const int pos = __popcll(mask & ((1ULL << lane) - 1ULL));
-      kl_k[pos] = k; kl_s[pos] = s0; kl_m[pos] = m;
-      kl_g[pos] = (incl & 0xFFFF) - nfull; kl_h[pos] = (incl >> 16) - npart;
-    }
-    const int total = __shfl(incl, 63, 64);
-    if (lane == 0) {
-      const int nkk = __popcll(mask);
-      nk_s = nkk; kl_g[nkk] = total & 0xFFFF; kl_h[nkk] = total >> 16; *commit = 0;
-    }
-  }
-  {  // zero the tile: (T + SINK) * ACS floats, a multiple of four
-    float4 *z = reinterpret_cast<float4 *>(acc_l);
-    const int n4 = (T + C::SINK) * (C::ACS / 4);
-    for (int i = tid; i < n4; i += C::NT) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
-  const int nk = __builtin_amdgcn_readfirstlane(nk_s);  // scalars: the group loop and its branches are wave-uniform
-  // group order = commit order: all full groups (R row blocks, equal duration) in ascending offset order, then the
-  // partial groups. Waves take groups round-robin and commit in order, so neighbours of equal length never wait
-  // for each other (with offset-major numbering a short group queued behind a long one idled its wave: 9-12 % of
-  // the wave time in the ticket wait, tools/conv_trace.py). The order depends on the map only: deterministic.
-  const int total_full = nk > 0 ? __builtin_amdgcn_readfirstlane(kl_g[nk]) : 0;
-  const int total_grp = nk > 0 ? total_full + __builtin_amdgcn_readfirstlane(kl_h[nk]) : 0;
+  __shared__ int nk_s;
+  int nk, total_full, total_grp;  // wave-uniform scalars
+  conv_offset_prologue<C>(tl, a, tile, T, tid, lane, wid, &nk_s, nk, total_full, total_grp);
 
   const int cin4 = a.cin - 4;
   const int nb16 = TAIL ? (a.cin + 15) >> 4 : a.cin >> 4;  // 16-channel contraction blocks
@@ -168,34 +100,8 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
       if (C::N1) f.b1[e] = wp[col1];
     }
   };
-  // group grp -> its offset entry (the hint only moves forward inside a phase; bit 5 = partial-group phase),
-  // pair index of this lane per row block
   auto locate = [&](int grp, int &i_hint, int *pidx, unsigned &vmask, int &nr) {
-    int rb0, e;
-    if (grp < total_full) {
-      e = i_hint;
-      while (kl_g[e + 1] <= grp) ++e;
-      i_hint = e;
-      rb0 = (grp - kl_g[e]) * R;
-      nr = R;
-    } else {
-      const int q = grp - total_full;
-      e = (i_hint & 32) ? (i_hint & 31) : 0;
-      while (kl_h[e + 1] <= q) ++e;
-      i_hint = e | 32;
-      const int nrb = (kl_m[e] + 15) >> 4;
-      rb0 = (nrb / R) * R;
-      nr = nrb - rb0;
-    }
-    const int m = kl_m[e];
-    vmask = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int rk = (rb0 + r) * 16 + l15;
-      const bool v = rk < m;
-      vmask |= v ? (1u << r) : 0u;
-      pidx[r] = kl_s[e] + (v ? rk : m - 1);  // padding rows re-read the slice's last pair
-    }
+    conv_locate<R>(tl, total_full, l15, grp, i_hint, pidx, vmask, nr);
   };
   auto make_ctx = [&](Ctx &cx, const int2 *pr, unsigned vmask, int nr, int i_k) {
 #pragma unroll
@@ -212,7 +118,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
 #if PCS_ALIAS == 1   /* debug build: every offset reads W[0] (W operand always L1/L2-hot) */
     cx.Wk = a.W + n0;
 #else
-    cx.Wk = a.W + (int64_t)kl_k[i_k & 31] * a.cin * a.cout + n0;
+    cx.Wk = a.W + (int64_t)tl.kl_k[i_k & 31] * a.cin * a.cout + n0;
 #endif
   };
 
@@ -329,6 +235,8 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
     // bounds the tile. So the row addresses are formed BEFORE the ticket wait, and the wave raises its priority while
     // it holds the ticket (its VALU / LDS instructions otherwise queue behind the MFMA streams of the waves sharing
     // its SIMD): +8 % and +3 % at stride 1. A second ticket for half of the columns bought nothing on top.
+    // (inline here, not conv_commit_* of conv_wave_common.h -- the reference definition, where the LDS ordering assumption is
+    // stated: shared, this kernel's register allocation moved and instances gained spills; profiles/conv_skeleton_refactor.md)
     PCS_T(const long long tr_b = wall_clock64();)
     int doff[R][4];
 #pragma unroll
@@ -413,7 +321,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
     }
     // the ticket store stays behind the tile writes in program order and the LDS keeps a wave's instructions in order; a
     // bare ds_write_b32 because the compiler puts the completion wait (s_waitcnt lgkmcnt(0)) in front of its own store
-    // (the hardware assumption is stated once)
+    // (the hardware assumption is stated once, at conv_commit_rows in conv_wave_common.h)
     if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(grp + 1) : "memory");
     __builtin_amdgcn_s_setprio(0);
     PCS_T(const long long tr_d = wall_clock64(); tr_loop += tr_b - tr_a; tr_ticket += tr_c - tr_b; tr_commit += tr_d - tr_c; ++tr_groups;)
@@ -431,19 +339,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
   float *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
-                                   [&](int r, int cq, const float4 &v0) {
-                                     float4 v = v0;
-                                     if (a.addend) {  // kernel argument: uniform
-                                       const float4 ad = *reinterpret_cast<const float4 *>(a.addend + (row0 + r) * (int64_t)ldd + n0 + cq);
-                                       v.x += ad.x; v.y += ad.y; v.z += ad.z; v.w += ad.w;
-                                     }
-                                     if (a.act_slope != 1.f) {
-                                       v.x = v.x < 0.f ? v.x * a.act_slope : v.x; v.y = v.y < 0.f ? v.y * a.act_slope : v.y;
-                                       v.z = v.z < 0.f ? v.z * a.act_slope : v.z; v.w = v.w < 0.f ? v.w * a.act_slope : v.w;
-                                     }
-                                     *reinterpret_cast<float4 *>(drow + (int64_t)r * ldd + cq) = v;
-                                     return v;
-                                   });
+                                   ConvStoreF32{drow, a.addend, row0, n0, ldd, a.act_slope});
 #if PCS_TRACE
   if (lane == 0 && blockIdx.x < kTraceBlocks && g_conv_trace) {
     long long *t = g_conv_trace + ((int64_t)blockIdx.x * 8 + wid) * 8;
@@ -466,32 +362,22 @@ void trace_prepare(hipStream_t st) {
 
 template <int NCTT, int NW, int MINW, int R, bool TAIL>
 int launch_conv5(const ConvArgs &a, hipStream_t st) {
-  using C = Conv5Cfg<NCTT, NW, R>;
-  const int64_t nblocks = a.order ? ceil_div(a.ntiles, 8) * 8 * a.ncoltiles : a.ntiles * a.ncoltiles;
-  if (nblocks <= 0) return PCS_OK;
-  if (nblocks > 0x7FFFFFFF) { set_error("pcs_conv: grid too large"); return PCS_EUNSUPPORTED; }
-  auto kern = conv_os5_kernel<NCTT, NW, MINW, R, TAIL>;
+  using C = ConvWaveCfg<NCTT, NW, R>;
+  constexpr auto kern = conv_os5_kernel<NCTT, NW, MINW, R, TAIL>;
   const size_t lds = C::lds_bytes(a.tile_rows);
-  if (lds > kMaxDynLds) { set_error("pcs_conv: tile_rows too large for this column tile"); return PCS_EUNSUPPORTED; }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
-    attr_set = true;
-  }
-  PCS_T(trace_prepare(st);)
-  static const int dbg = getenv("PCS_CONV_DEBUG") ? atoi(getenv("PCS_CONV_DEBUG")) : 0;  // debug: launch shape + residency
-  static long long dbg_last = -1;
-  const long long dbg_key = ((long long)a.tile_rows << 32) ^ ((long long)a.cin << 16) ^ a.cout;
-  if (dbg && dbg_key != dbg_last) {
-    dbg_last = dbg_key;
-    int nb = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern), C::NT, lds);
-    fprintf(stderr, "[pcs_conv] wave5<%d,%d,%d,%d%s> T=%d cin=%d cout=%d grid=%lld lds=%zu resident WG/CU=%d (waves/SIMD=%d)\n", NCTT, NW,
-            MINW, R, TAIL ? ",tail" : "", a.tile_rows, a.cin, a.cout, (long long)nblocks, lds, nb, nb * NW / 4);
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(C::NT), lds, st, a);
-  return check_launch("pcs_conv_gather_gemm_f32(wave5)");
+  return conv_wave_launch<kern>(a, a.order != nullptr, C::NT, lds, st, "pcs_conv", "pcs_conv_gather_gemm_f32(wave5)", [&](int64_t nblocks) {
+    PCS_T(trace_prepare(st);)
+    static const int dbg = getenv("PCS_CONV_DEBUG") ? atoi(getenv("PCS_CONV_DEBUG")) : 0;  // debug: launch shape + residency
+    static long long dbg_last = -1;
+    const long long dbg_key = ((long long)a.tile_rows << 32) ^ ((long long)a.cin << 16) ^ a.cout;
+    if (dbg && dbg_key != dbg_last) {
+      dbg_last = dbg_key;
+      int nb = 0;
+      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern), C::NT, lds);
+      fprintf(stderr, "[pcs_conv] wave5<%d,%d,%d,%d%s> T=%d cin=%d cout=%d grid=%lld lds=%zu resident WG/CU=%d (waves/SIMD=%d)\n", NCTT, NW,
+              MINW, R, TAIL ? ",tail" : "", a.tile_rows, a.cin, a.cout, (long long)nblocks, lds, nb, nb * NW / 4);
+    }
+  });
 }
 
 }  // namespace
@@ -511,8 +397,7 @@ int pcs::launch_conv_wave5(ConvArgs a, hipStream_t st) {
   static const int force_nw = getenv("PCS_CONV_NW") ? atoi(getenv("PCS_CONV_NW")) : 0;        // debug: 4 / 8
   if (force_nctt && nctt > force_nctt) nctt = force_nctt;
   a.ncoltiles = (int)ceil_div(a.cout, 16 * nctt);
-  // 4-wave workgroups while two of them fit a CU's LDS, else one 8-wave workgroup
-  const bool nw8 = force_nw ? force_nw == 8 : 2 * conv5_lds_est(a.tile_rows, nctt) > 160 * 1024;
+  const bool nw8 = force_nw ? force_nw == 8 : conv_nw8(a.tile_rows, nctt);
   // groups of 2 row blocks (groups of 3 / 4 were instantiated and measured through round 2: within +-1 % where they fit
   // the registers -- the W stream they save is not what bounds the kernel -- and spilling at 6 / 8 column tiles)
   const bool tail = (a.cin % 32) != 0;

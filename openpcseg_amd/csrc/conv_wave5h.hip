@@ -3,7 +3,8 @@
 // half; TS:torchsparse/backend/convolution/convolution_cuda.cu:61,120-127 runs gather / mm / scatter in half).
 //
 // Same output-stationary structure as conv_wave5.hip -- wave-autonomous row-block groups, fp32 accumulator tile in
-// LDS, ticket-ordered commit, every dst row written once -- with the operand side rebuilt for 16-bit MFMAs, whose
+// LDS, ticket-ordered commit, every dst row written once: the skeleton of conv_wave_common.h -- with the operand side rebuilt
+// for 16-bit MFMAs, whose
 // 16x-higher rate turns the kernel from MFMA-bound into L2/gather-bound:
 //   * one contraction step = 32 channels = ONE 16-byte load per lane and operand: lane (n = lane & 15, g = lane >> 4)
 //     reads the 8 halfs src[row_n][32 s + 8 g .. +7] (A) and the 8 halfs of column n of the weights (B);
@@ -34,35 +35,21 @@ namespace {
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // native vector: loads from LDS address-space pointers
 
 #if PCS_TRACE
-__device__ long long *g_convh_trace;   // [block][wave][8], as conv_wave5.hip: t_entry, t_start, t_end, loop, ticket, commit, groups, t_exit
+__device__ long long *g_convh_trace;   // [block][wave][8], the layout of conv_wave5.hip's g_conv_trace: t_entry, t_start, t_end, loop, ticket, commit, groups, t_exit
 constexpr int kTraceBlocksH = 8192;
 #endif
 
-// Wp block (k, global 16-column tile gt, step s) = 64 lanes x 8 halfs; lane 16 g + n, element j =
-//   Wmath[k][32 s + 8 g + j][column(gt, n)],  Wmath[k][c][col] = transpose ? W[k][col][c] : W[k][c][col]
-// (W is (K, A, B) fp32: forward contracts over A = cin, dgrad over B = cout). Columns >= ccols are zero.
+// prepared weights in the storage format HT: fragment order and values of conv_wfrag_values (conv_wave_common.h), rounded
 template <typename HT>
 __global__ void __launch_bounds__(256) prepare_weights_kernel(const float *__restrict__ W, int K, int A, int B, int transpose,
                                                               int nctt, int nt16, int ns, uint4 *__restrict__ Wp) {
-  const int ccon = transpose ? B : A, ccols = transpose ? A : B;
   const int64_t total = (int64_t)K * nt16 * ns * 64;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int lane = (int)(i & 63);
-    int64_t b = i >> 6;
-    const int s = (int)(b % ns); b /= ns;
-    const int gt = (int)(b % nt16);
-    const int k = (int)(b / nt16);
-    const int n = lane & 15, g = lane >> 4;
-    const int col = (gt / nctt) * 16 * nctt + h_local_col(nctt, gt % nctt, n);
+    float v[8];
+    conv_wfrag_values(W, i, A, B, transpose, nctt, nt16, ns, v);
     uint16_t h[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = 32 * s + 8 * g + j;
-      float v = 0.f;
-      if (col < ccols && c < ccon)
-        v = transpose ? W[((int64_t)k * A + col) * B + c] : W[((int64_t)k * A + c) * B + col];
-      h[j] = f2h(HT{}, v);
-    }
+    for (int j = 0; j < 8; ++j) h[j] = f2h(HT{}, v[j]);
     uint4 o;
     o.x = h[0] | ((uint32_t)h[1] << 16); o.y = h[2] | ((uint32_t)h[3] << 16);
     o.z = h[4] | ((uint32_t)h[5] << 16); o.w = h[6] | ((uint32_t)h[7] << 16);
@@ -70,92 +57,29 @@ __global__ void __launch_bounds__(256) prepare_weights_kernel(const float *__res
   }
 }
 
-template <int NCTT, int NW_, int R_>
-struct Conv5hCfg {
-  static constexpr int NW = NW_;
-  static constexpr int R = R_;
-  static constexpr int NT = 64 * NW;
-  static constexpr int CT = 16 * NCTT;
-  static constexpr int ACS = CT + 4;
-  static constexpr int N4 = NCTT / 4;
-  static constexpr int N2 = (NCTT % 4) / 2;
-  static constexpr int N1 = NCTT % 2;
-  static constexpr int SINK = kConvSinkRows;
-  static constexpr size_t lds_bytes(int T) { return (size_t)((T + SINK) * ACS) * 4 + 5 * 33 * 4 + 16; }
-};
-
 template <typename HT, int NCTT, int NW, int MINW, int R, bool TAIL>
 __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
-  using C = Conv5hCfg<NCTT, NW, R>;
+  using C = ConvWaveCfg<NCTT, NW, R>;
   const int T = a.tile_rows;
   PCS_T(const long long tr_entry = wall_clock64(); long long tr_loop = 0, tr_ticket = 0, tr_commit = 0; int tr_groups = 0;)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *acc_l = reinterpret_cast<float *>(smem);            // [T+SINK][ACS], rows >= T = sink for padding rows
-  int *kl_k = reinterpret_cast<int *>(acc_l + (T + C::SINK) * C::ACS);  // [32] offset id
-  int *kl_s = kl_k + 32;                                     // [32] first pair
-  int *kl_m = kl_s + 32;                                     // [32] #pairs
-  int *kl_g = kl_m + 32;                                     // [33] first FULL group (prefix over the offsets)
-  int *kl_h = kl_g + 33;                                     // [33] first partial group (prefix)
-  int *commit = kl_h + 33;
-  const unsigned commit_lds = (unsigned)(size_t)(__attribute__((address_space(3))) int *)commit;  // LDS byte address
-  const unsigned acc_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float *)acc_l;
-  __shared__ int nk_s;
+  const ConvTileLds tl = conv_tile_lds<C, true>(smem, T);
+  float *acc_l = tl.acc;
+  int *kl_s = tl.kl_s, *kl_m = tl.kl_m, *kl_g = tl.kl_g, *kl_h = tl.kl_h, *commit = tl.commit;
+  const unsigned commit_lds = tl.commit_lds, acc_lds = tl.acc_lds;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // a scalar: wave-level loops and branches stay uniform
   const int g = lane >> 4, l15 = lane & 15;
-  unsigned bid = blockIdx.x;
-  if (!a.order) {
-    const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int64_t slot = bid / a.ncoltiles;
-  int ctile = bid % a.ncoltiles;
-  if (a.order) {  // tiles dealt round-robin over the XCDs, the column tiles of one row tile back to back on one XCD
-    const unsigned xcd = bid & 7, idx = bid >> 3;
-    slot = (int64_t)(idx / a.ncoltiles) * 8 + xcd;
-    ctile = idx % a.ncoltiles;
-    if (slot >= a.ntiles) return;  // the grid is padded to 8 * ncoltiles
-  }
+  int64_t slot;
+  int ctile;
+  conv_block_slot<true>(a, slot, ctile);
+  if (a.order && slot >= a.ntiles) return;  // the grid of an ordered launch is padded to 8 * ncoltiles
   const int64_t tile = a.order ? (int64_t)a.order[slot] : slot;
   const int n0 = ctile * C::CT;
   const int64_t row0 = tile * T;
-  const int64_t nt1 = a.ntiles + 1;
-
-  if (wid == 0) {  // non-empty offsets of this tile + prefix of their row-block groups (as conv_wave5.hip)
-    const int k = lane;
-    int s0 = 0, m = 0;
-    if (k < a.K) {
-      s0 = a.seg[(int64_t)k * nt1 + tile];
-      m = a.seg[(int64_t)k * nt1 + tile + 1] - s0;
-    }
-    const unsigned long long mask = __ballot(m > 0);
-    const int nrb = (m + 15) >> 4;
-    const int nfull = nrb / R, npart = (nrb % R) ? 1 : 0;
-    int incl = nfull | (npart << 16);
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (m > 0) {
-      const int pos = __popcll(mask & ((1ULL << lane) - 1ULL));
-      kl_k[pos] = k; kl_s[pos] = s0; kl_m[pos] = m;
-      kl_g[pos] = (incl & 0xFFFF) - nfull; kl_h[pos] = (incl >> 16) - npart;
-    }
-    const int total = __shfl(incl, 63, 64);
-    if (lane == 0) {
-      const int nkk = __popcll(mask);
-      nk_s = nkk; kl_g[nkk] = total & 0xFFFF; kl_h[nkk] = total >> 16; *commit = 0;
-    }
-  }
-  {  // zero the tile: (T + SINK) * ACS floats, a multiple of four
-    float4 *z = reinterpret_cast<float4 *>(acc_l);
-    const int n4 = (T + C::SINK) * (C::ACS / 4);
-    for (int i = tid; i < n4; i += C::NT) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
-  const int nk = __builtin_amdgcn_readfirstlane(nk_s);  // scalars: the group loop and its branches are wave-uniform
-  const int total_full = nk > 0 ? __builtin_amdgcn_readfirstlane(kl_g[nk]) : 0;
-  const int total_grp = nk > 0 ? total_full + __builtin_amdgcn_readfirstlane(kl_h[nk]) : 0;
+  __shared__ int nk_s;
+  int nk, total_full, total_grp;  // wave-uniform scalars
+  conv_offset_prologue<C>(tl, a, tile, T, tid, lane, wid, &nk_s, nk, total_full, total_grp);
 
   // B fragments of this column tile: 16-column tiles that do not exist (beyond cout) read tile 0, results dropped
   const int gt0 = ctile * NCTT;
@@ -207,6 +131,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
 #endif
     (void)ldb;
   };
+  // conv_locate of conv_wave_common.h, inline here and in the commit and the write-back below for this kernel's register allocation
   auto locate = [&](int grp, int &i_hint, int *pidx, unsigned &vmask, int &nr) {
     int rb0, e;
     if (grp < total_full) {
@@ -242,7 +167,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
     }
     cx.vmask = vmask;
     cx.nr = nr;
-    cx.Wk = a.Wp + (((int64_t)kl_k[i_k & 31] * a.nt16 + gt0) * NS) * 1024 + lane * 16;
+    cx.Wk = a.Wp + (((int64_t)tl.kl_k[i_k & 31] * a.nt16 + gt0) * NS) * 1024 + lane * 16;
   };
 
   int i = 0;
@@ -262,7 +187,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
     load_frag(f0, cur, 0);
   }
   PCS_T(const long long tr_start = wall_clock64();)
-  // one straight-line body per group loop (full groups: R row blocks, partial groups: one), see conv_wave5.hip
+  // one straight-line body per group loop (full groups: R row blocks, partial groups: 1 .. R - 1), see conv_wave5.hip's run_group
   static_assert(R >= 2 && R <= 4, "partial groups hold 1 .. R - 1 row blocks");
   auto run_group = [&](const int grp, auto nrc_tag) {
     constexpr int NRC = decltype(nrc_tag)::value;
@@ -317,8 +242,10 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
       f0 = f1;
     }
     PCS_T(const long long tr_b = wall_clock64();)
-    // ---- in-order commit of the group's row blocks (as conv_wave5.hip: row addresses formed before the ticket wait,
-    // raised wave priority while the ticket is held -- the commits of a workgroup are one serial chain) -----------
+    // ---- in-order commit of the group's row blocks: row addresses formed before the ticket wait, raised wave priority
+    // while the ticket is held -- the commits of a workgroup are one serial chain -----------------------------------
+    // (inline here, not conv_commit_* of conv_wave_common.h -- the reference definition, where the LDS ordering assumption is
+    // stated: shared, this kernel's register allocation moved and instances gained spills; profiles/conv_skeleton_refactor.md)
     int doff[R][4];
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -409,6 +336,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
     }
     // the ticket store stays behind the tile writes in program order and the LDS keeps a wave's instructions in order; a
     // bare ds_write_b32 because the compiler puts the completion wait (s_waitcnt lgkmcnt(0)) in front of its own store
+    // (the hardware assumption is stated once, at conv_commit_rows in conv_wave_common.h)
     if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(grp + 1) : "memory");
     __builtin_amdgcn_s_setprio(0);
 #endif  // PCS_ABLATEH 3 / 4
@@ -473,21 +401,9 @@ void traceh_prepare(hipStream_t st) {
 
 template <typename HT, int NCTT, int NW, int MINW, int R, bool TAIL>
 int launch_conv5h(const ConvArgsH &a, hipStream_t st) {
-  using C = Conv5hCfg<NCTT, NW, R>;
-  const int64_t nblocks = a.order ? ceil_div(a.ntiles, 8) * 8 * a.ncoltiles : a.ntiles * a.ncoltiles;
-  if (nblocks <= 0) return PCS_OK;
-  if (nblocks > 0x7FFFFFFF) { set_error("pcs_conv_h: grid too large"); return PCS_EUNSUPPORTED; }
-  auto kern = conv_os5h_kernel<HT, NCTT, NW, MINW, R, TAIL>;
-  const size_t lds = C::lds_bytes(a.tile_rows);
-  if (lds > kMaxDynLds) { set_error("pcs_conv_h: tile_rows too large for this column tile"); return PCS_EUNSUPPORTED; }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
-    attr_set = true;
-  }
-  PCS_T(traceh_prepare(st);)
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(C::NT), lds, st, a);
-  return check_launch("pcs_conv_gather_gemm_h(wave5h)");
+  using C = ConvWaveCfg<NCTT, NW, R>;
+  return conv_wave_launch<conv_os5h_kernel<HT, NCTT, NW, MINW, R, TAIL>>(a, a.order != nullptr, C::NT, C::lds_bytes(a.tile_rows), st, "pcs_conv_h",
+                                                                          "pcs_conv_gather_gemm_h(wave5h)", [&](int64_t) { PCS_T(traceh_prepare(st);) });
 }
 
 // row blocks per group of the half kernel per column-tile width (picked from profiles/round3_convh_group_rows.txt)
@@ -502,7 +418,7 @@ int launch_h(ConvArgsH a, hipStream_t st) {
   static const int force_nctt = getenv("PCS_CONVH_NCTT") ? atoi(getenv("PCS_CONVH_NCTT")) : 0;  // debug: narrower column tiles
   if (force_nctt && nctt > force_nctt && a.cout % (16 * force_nctt) == 0 && !a.stats) nctt = force_nctt;
   a.ncoltiles = (int)ceil_div(a.cout, 16 * nctt);
-  const bool nw8 = 2 * conv5_lds_est(a.tile_rows, nctt) > 160 * 1024;  // 4-wave workgroups while two of them fit a CU's LDS, else one 8-wave workgroup
+  const bool nw8 = conv_nw8(a.tile_rows, nctt);
   const bool tail = (a.cin % 32) != 0;
   // row blocks per group: the kernel is bound by the vector-memory address unit (TA ~65-80 % busy, MFMA pipe 10-20 %,
   // profiles/round3_convh_pmc.md): one 16-byte operand load per lane feeds R N / (R + N) MFMAs, so more row blocks per B
@@ -575,7 +491,6 @@ extern "C" int pcs_conv_gather_gemm_h_ex(const void *src, int64_t n_src, int32_t
                                          const int32_t *pairs, int32_t src_col, const int32_t *seg, int32_t tile_rows,
                                          int64_t n_dst, const float *bias, const pcs_conv_epilogue *ep, void *dst, int32_t dtype,
                                          double *bn_partial, const int32_t *tile_order, void *stream) {
-  const void *addend = ep ? ep->addend : nullptr;
   if (cin <= 0 || cout <= 0 || K <= 0 || n_dst < 0 || n_src < 0 || (src_col != 0 && src_col != 1) || (dtype != 1 && dtype != 2)) {
     set_error("pcs_conv_gather_gemm_h: bad sizes");
     return PCS_EINVAL;
@@ -590,11 +505,9 @@ extern "C" int pcs_conv_gather_gemm_h_ex(const void *src, int64_t n_src, int32_t
   a.dst = reinterpret_cast<uint16_t *>(dst); a.pairs = pairs; a.seg = seg;
   a.n_dst = n_dst; a.ntiles = ceil_div(n_dst, tile_rows); a.tile_rows = tile_rows;
   a.cin = cin; a.cout = cout; a.K = K; a.src_col = src_col; a.ncoltiles = 1; a.stats = bn_partial; a.order = tile_order;
+  const void *addend = nullptr;
+  if (conv_decode_epilogue(ep, "pcs_conv_gather_gemm_h_ex", 8, addend, a.act_slope) != PCS_OK) return PCS_EINVAL;
   a.addend = reinterpret_cast<const uint16_t *>(addend);
-  if (addend && ((uintptr_t)addend & 7)) { set_error("pcs_conv_gather_gemm_h_ex: misaligned addend"); return PCS_EINVAL; }
-  if (ep && ep->act_slope != 0.f && ep->act_slope != 1.f) a.act_slope = ep->act_slope;
-  if (ep && (ep->flags & ~PCS_EP_RELU)) { set_error("pcs_conv_gather_gemm_h_ex: unknown pcs_conv_epilogue.flags bits"); return PCS_EINVAL; }
-  if (ep && (ep->flags & PCS_EP_RELU)) a.act_slope = 0.f;   // ReLU = the kernels' LeakyReLU branch with slope 0
   if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, dtype)) {
     set_error("pcs_conv_gather_gemm_h: this shape / tile height does not produce BatchNorm partials");
     return PCS_EUNSUPPORTED;

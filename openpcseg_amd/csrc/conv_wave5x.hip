@@ -9,7 +9,7 @@
 // error against float64 to at most twice the fp32 MFMA kernel's).
 //
 // Structure = conv_wave5h.hip (output-stationary tile in LDS, wave-autonomous row-block groups, ticket-ordered phased commit,
-// shared epilogue with BatchNorm partials), operand side:
+// shared epilogue with BatchNorm partials: the skeleton of conv_wave_common.h), operand side:
 //   * A: lane (n = lane & 15, g = lane >> 4) gathers the 8 floats src[row_n][32 s + 8 g .. +7] (two 16-byte loads) and splits
 //     them in registers (v_cvt_pk_bf16_f32 on pairs) right before the MFMAs of the step;
 //   * B: the weights are split and re-packed once per layer call (pcs_conv_prepare_weights_x3) into three planes of MFMA
@@ -21,7 +21,7 @@
 //   * groups hold R = 4 row blocks at 64 columns, 3 at 96, 2 at 32: the kernel is bound by the vector-memory address path
 //     (TA 78-87 % busy, MFMA pipe 29-37 %; without the MFMAs the launch takes the same time), a column tile costs 2 A loads
 //     + 3 N / R weight-fragment loads per row block and step, and R is what 256 registers allow (profiles/round3_convx.md).
-#include "conv_common.h"
+#include "conv_wave_common.h"
 
 #ifndef PCS_ABLATEX
 #define PCS_ABLATEX 0  /* debug builds: 1 no operand split (planes = raw bits), 2 no B reloads inside a group, 3 no A reloads, 4 no MFMA */
@@ -64,36 +64,13 @@ __host__ __device__ inline int convx_nctt(int cout) {
   return 4;
 }
 
-// local column of lane n of 16-column tile tl inside a column tile (the 4- / 2-interleave the commit and epilogue assume)
-__host__ __device__ inline int x_local_col(int nctt, int tl, int n) {
-  const int n4 = nctt / 4;
-  if (tl < 4 * n4) return 64 * (tl / 4) + 4 * n + (tl % 4);
-  return 64 * n4 + 2 * n + (tl - 4 * n4);
-}
-
-// Wp plane p, block (k, global 16-column tile gt, step s) = 64 lanes x 8 bf16; lane 16 g + n, element j =
-//   plane_p(Wmath[k][32 s + 8 g + j][column(gt, n)]),  Wmath[k][c][col] = transpose ? W[k][col][c] : W[k][c][col].
-// Columns >= ccols and channels >= ccon are zero in every plane.
+// prepared weights: fragment order and values of conv_wfrag_values (conv_wave_common.h), split into three bf16 planes
 __global__ void __launch_bounds__(256) prepare_weights_x3_kernel(const float *__restrict__ W, int K, int A, int B, int transpose,
                                                                  int nctt, int nt16, int ns, uint4 *__restrict__ Wp) {
-  const int ccon = transpose ? B : A, ccols = transpose ? A : B;
   const int64_t total = (int64_t)K * nt16 * ns * 64;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int lane = (int)(i & 63);
-    int64_t b = i >> 6;
-    const int s = (int)(b % ns); b /= ns;
-    const int gt = (int)(b % nt16);
-    const int k = (int)(b / nt16);
-    const int n = lane & 15, g = lane >> 4;
-    const int col = (gt / nctt) * 16 * nctt + x_local_col(nctt, gt % nctt, n);
     float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = 32 * s + 8 * g + j;
-      v[j] = 0.f;
-      if (col < ccols && c < ccon)
-        v[j] = transpose ? W[((int64_t)k * A + col) * B + c] : W[((int64_t)k * A + c) * B + col];
-    }
+    conv_wfrag_values(W, i, A, B, transpose, nctt, nt16, ns, v);
     uint4 hi, mid, lo;
     split3(v[0], v[1], hi.x, mid.x, lo.x); split3(v[2], v[3], hi.y, mid.y, lo.y);
     split3(v[4], v[5], hi.z, mid.z, lo.z); split3(v[6], v[7], hi.w, mid.w, lo.w);
@@ -116,86 +93,28 @@ struct ConvArgsX {
   const int32_t *order;  // optional [ntiles]: workgroup slot -> row tile (heaviest first), as ConvArgs::order
 };
 
-template <int NCTT, int NW_, int R_>
-struct Conv5xCfg {
-  static constexpr int NW = NW_;
-  static constexpr int R = R_;
-  static constexpr int NT = 64 * NW;
-  static constexpr int CT = 16 * NCTT;
-  static constexpr int ACS = CT + 4;
-  static constexpr int N4 = NCTT / 4;
-  static constexpr int N2 = (NCTT % 4) / 2;
-  static constexpr size_t lds_bytes(int T) { return (size_t)((T + 1) * ACS) * 4 + 5 * 33 * 4 + 16; }
-};
-
 template <int NCTT, int NW, int MINW, int R, bool TAIL>
 __global__ void __launch_bounds__(64 * NW, MINW) conv_os5x_kernel(ConvArgsX a) {
-  using C = Conv5xCfg<NCTT, NW, R>;
+  using C = ConvWaveCfg<NCTT, NW, R>;
   static_assert(NCTT % 2 == 0 && R >= 2 && R <= 4, "tile pairs; partial groups hold 1 .. R - 1 row blocks");
   const int T = a.tile_rows;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *acc_l = reinterpret_cast<float *>(smem);            // [T+1][ACS], row T = sink for padding rows
-  int *kl_k = reinterpret_cast<int *>(acc_l + (T + 1) * C::ACS);  // [32] offset id
-  int *kl_s = kl_k + 32;                                     // [32] first pair
-  int *kl_m = kl_s + 32;                                     // [32] #pairs
-  int *kl_g = kl_m + 32;                                     // [33] first FULL group (prefix over the offsets)
-  int *kl_h = kl_g + 33;                                     // [33] first partial group (prefix)
-  int *commit = kl_h + 33;
-  const unsigned commit_lds = (unsigned)(size_t)(__attribute__((address_space(3))) int *)commit;  // LDS byte addresses
-  const unsigned acc_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float *)acc_l;
-  __shared__ int nk_s;
+  const ConvTileLds tl = conv_tile_lds<C, true>(smem, T);
+  float *acc_l = tl.acc;
+  int *kl_s = tl.kl_s, *kl_m = tl.kl_m, *kl_g = tl.kl_g, *kl_h = tl.kl_h;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, l15 = lane & 15;
-  const unsigned bid = blockIdx.x;
-  int64_t slot = bid / a.ncoltiles;
-  int ctile = bid % a.ncoltiles;
-  if (a.order) {  // tiles dealt round-robin over the XCDs, the column tiles of one row tile back to back on one XCD
-    const unsigned xcd = bid & 7, idx = bid >> 3;
-    slot = (int64_t)(idx / a.ncoltiles) * 8 + xcd;
-    ctile = idx % a.ncoltiles;
-    if (slot >= a.ntiles) return;  // the grid is padded to 8 * ncoltiles
-  }
+  int64_t slot;
+  int ctile;
+  conv_block_slot<false>(a, slot, ctile);
+  if (a.order && slot >= a.ntiles) return;  // the grid of an ordered launch is padded to 8 * ncoltiles
   const int64_t tile = a.order ? (int64_t)a.order[slot] : slot;
   const int n0 = ctile * C::CT;
   const int64_t row0 = tile * T;
-  const int64_t nt1 = a.ntiles + 1;
-
-  if (wid == 0) {  // non-empty offsets of this tile + prefix of their row-block groups (as conv_wave5.hip)
-    const int k = lane;
-    int s0 = 0, m = 0;
-    if (k < a.K) {
-      s0 = a.seg[(int64_t)k * nt1 + tile];
-      m = a.seg[(int64_t)k * nt1 + tile + 1] - s0;
-    }
-    const unsigned long long mask = __ballot(m > 0);
-    const int nrb = (m + 15) >> 4;
-    const int nfull = nrb / R, npart = (nrb % R) ? 1 : 0;
-    int incl = nfull | (npart << 16);
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (m > 0) {
-      const int pos = __popcll(mask & ((1ULL << lane) - 1ULL));
-      kl_k[pos] = k; kl_s[pos] = s0; kl_m[pos] = m;
-      kl_g[pos] = (incl & 0xFFFF) - nfull; kl_h[pos] = (incl >> 16) - npart;
-    }
-    const int total = __shfl(incl, 63, 64);
-    if (lane == 0) {
-      const int nkk = __popcll(mask);
-      nk_s = nkk; kl_g[nkk] = total & 0xFFFF; kl_h[nkk] = total >> 16; *commit = 0;
-    }
-  }
-  {  // zero the tile: (T + 1) * ACS floats, a multiple of four
-    float4 *z = reinterpret_cast<float4 *>(acc_l);
-    const int n4 = (T + 1) * (C::ACS / 4);
-    for (int i = tid; i < n4; i += C::NT) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
-  const int nk = __builtin_amdgcn_readfirstlane(nk_s);
-  const int total_full = nk > 0 ? __builtin_amdgcn_readfirstlane(kl_g[nk]) : 0;
-  const int total_grp = nk > 0 ? total_full + __builtin_amdgcn_readfirstlane(kl_h[nk]) : 0;
+  __shared__ int nk_s;
+  int nk, total_full, total_grp;  // wave-uniform scalars
+  conv_offset_prologue<C>(tl, a, tile, T, tid, lane, wid, &nk_s, nk, total_full, total_grp);
 
   // B fragments of this column tile: 16-column tiles that do not exist (beyond cout) read tile 0, results dropped
   const int gt0 = ctile * NCTT;
@@ -217,6 +136,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5x_kernel(ConvArgsX a) {
     int nr;
     unsigned vmask;
   };
+  // conv_locate of conv_wave_common.h, inline here: shared, the 96-column R = 3 instances spilled two more registers
   auto locate = [&](int grp, int &i_hint, int *pidx, unsigned &vmask, int &nr) {
     int rb0, e;
     if (grp < total_full) {
@@ -252,7 +172,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5x_kernel(ConvArgsX a) {
     }
     cx.vmask = vmask;
     cx.nr = nr;
-    cx.Wk = a.Wp + (((int64_t)kl_k[i_k & 31] * a.nt16 + gt0) * NS) * 1024 + lane * 16;
+    cx.Wk = a.Wp + (((int64_t)tl.kl_k[i_k & 31] * a.nt16 + gt0) * NS) * 1024 + lane * 16;
   };
   // operand registers that live across groups: the raw A pieces and the three B planes of the step about to be computed
   uint4 araw[R][2];
@@ -283,7 +203,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5x_kernel(ConvArgsX a) {
 #pragma unroll
     for (int t = 0; t < NCTT; ++t) load_b(cur.Wk, t);
   }
-  // one straight-line body per group loop (full groups: R row blocks, partial groups: one), see conv_wave5.hip
+  // one straight-line body per group loop (full groups: R row blocks, partial groups: 1 .. R - 1), see conv_wave5.hip's run_group
   auto run_group = [&](const int grp, auto nrc_tag) {
     constexpr int NRC = decltype(nrc_tag)::value;
     const int grpn = grp + C::NW < total_grp ? grp + C::NW : grp;
@@ -347,64 +267,11 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5x_kernel(ConvArgsX a) {
         }
       }
     }
-    // ---- in-order commit of the group's row blocks (conv_wave5.hip: addresses before the ticket wait, three fenced phases,
-    // bare ds_write_b32 ticket behind the tile writes) -----------------------------------------------------------------
+    // ---- in-order commit of the group's row blocks (conv_wave_common.h), one round per row block (registers) ----
     unsigned dq[R][4], dp[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned dl = (unsigned)__shfl(cur.dloc[r], 4 * g + j, 64);
-        dq[r][j] = acc_lds + 4u * dl * C::ACS + 16u * l15;
-        dp[r][j] = acc_lds + 4u * dl * C::ACS + 256u * C::N4 + 8u * l15;
-        asm volatile("" : "+v"(dq[r][j]), "+v"(dp[r][j]));
-      }
-    if (lane == 0) {
-      while (__hip_atomic_load(commit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != grp)
-        __builtin_amdgcn_s_sleep(1);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    __builtin_amdgcn_s_setprio(3);
-    {
-      typedef float v2f __attribute__((ext_vector_type(2)));
-      typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
-      typedef __attribute__((address_space(3))) const v2f lds_cf2;
-      typedef __attribute__((address_space(3))) f32x4 lds_f4;
-      typedef __attribute__((address_space(3))) v2f lds_f2;
-#pragma unroll
-      for (int r = 0; r < NRC; ++r) {  // one round per row block (registers)
-        f32x4 v4[4][C::N4 > 0 ? C::N4 : 1];
-        v2f v2[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-          for (int q = 0; q < C::N4; ++q) v4[j][q] = *(lds_cf4 *)(size_t)(dq[r][j] + 256u * q);
-          if (C::N2) v2[j] = *(lds_cf2 *)(size_t)dp[r][j];
-        }
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-          for (int q = 0; q < C::N4; ++q) {
-            v4[j][q].x += acc[r][4 * q + 0][j]; v4[j][q].y += acc[r][4 * q + 1][j];
-            v4[j][q].z += acc[r][4 * q + 2][j]; v4[j][q].w += acc[r][4 * q + 3][j];
-          }
-          if (C::N2) { v2[j].x += acc[r][4 * C::N4 + 0][j]; v2[j].y += acc[r][4 * C::N4 + 1][j]; }
-        }
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-          for (int q = 0; q < C::N4; ++q) *(lds_f4 *)(size_t)(dq[r][j] + 256u * q) = v4[j][q];
-          if (C::N2) *(lds_f2 *)(size_t)dp[r][j] = v2[j];
-        }
-        asm volatile("" ::: "memory");
-      }
-    }
-    // as conv_wave5.hip: the ticket store stays behind the tile writes in program order and the LDS executes one wave's
-    // instructions in order (the hardware assumption is stated once)
-    if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(grp + 1) : "memory");
-    __builtin_amdgcn_s_setprio(0);
+    conv_commit_addr<C::ACS, NCTT>(tl.acc_lds, cur.dloc, g, l15, dq, dp);
+    conv_ticket_wait(tl.commit, grp, lane);
+    conv_commit_rows<NCTT, 1, NRC>(dq, dp, acc, NRC, tl.commit_lds, grp + 1, lane);
     cur = nxt;
     i = in;
   };
@@ -423,28 +290,14 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5x_kernel(ConvArgsX a) {
   float *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
-                                   [&](int r, int cq, const float4 &v) {
-                                     *reinterpret_cast<float4 *>(drow + (int64_t)r * ldd + cq) = v;
-                                     return v;
-                                   });
+                                   ConvStoreF32{drow, nullptr, row0, n0, ldd, 1.f});
 }
 
 template <int NCTT, int NW, int MINW, int R, bool TAIL>
 int launch_conv5x(const ConvArgsX &a, hipStream_t st) {
-  using C = Conv5xCfg<NCTT, NW, R>;
-  const int64_t nblocks = a.order ? ceil_div(a.ntiles, 8) * 8 * a.ncoltiles : a.ntiles * a.ncoltiles;
-  if (nblocks <= 0) return PCS_OK;
-  if (nblocks > 0x7FFFFFFF) { set_error("pcs_conv_x3: grid too large"); return PCS_EUNSUPPORTED; }
-  auto kern = conv_os5x_kernel<NCTT, NW, MINW, R, TAIL>;
-  const size_t lds = C::lds_bytes(a.tile_rows);
-  if (lds > kMaxDynLds) { set_error("pcs_conv_x3: tile_rows too large for this column tile"); return PCS_EUNSUPPORTED; }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(C::NT), lds, st, a);
-  return check_launch("pcs_conv_gather_gemm_f32_bf16x3(wave5x)");
+  using C = ConvWaveCfg<NCTT, NW, R>;
+  return conv_wave_launch<conv_os5x_kernel<NCTT, NW, MINW, R, TAIL>>(a, a.order != nullptr, C::NT, C::lds_bytes(a.tile_rows), st, "pcs_conv_x3",
+                                                                      "pcs_conv_gather_gemm_f32_bf16x3(wave5x)");
 }
 
 inline bool convx_applies(int cin, int cout, int K) {
@@ -460,8 +313,7 @@ extern "C" int32_t pcs_conv_x3_column_tiles(int32_t cout) { return cout > 0 ? co
 extern "C" int32_t pcs_conv_x3_emits_bn_partials(int32_t cin, int32_t cout, int32_t K, int32_t tile_rows) {
   if (!convx_applies(cin, cout, K) || tile_rows < 16) return 0;
   const int nctt = convx_nctt(cout);
-  const size_t lds = (size_t)((tile_rows + 1) * (16 * nctt + 4)) * 4 + 1024;
-  return conv_stats_fit(tile_rows, 16 * nctt, 2 * lds > 160 * 1024 ? 512 : 256) ? 1 : 0;
+  return conv_stats_fit(tile_rows, 16 * nctt, conv_nw8(tile_rows, nctt) ? 512 : 256) ? 1 : 0;
 }
 
 extern "C" size_t pcs_conv_prepared_weights_x3_bytes(int32_t K, int32_t ccon, int32_t ccols) {
@@ -509,13 +361,12 @@ extern "C" int pcs_conv_gather_gemm_f32_bf16x3(const float *src, int64_t n_src, 
   a.nt16 = a.ncoltiles * nctt;
   a.ns = (int)ceil_div(cin, 32);
   a.plane_bytes = (int64_t)K * a.nt16 * a.ns * 1024;
-  const size_t lds = (size_t)((tile_rows + 1) * (16 * nctt + 4)) * 4 + 1024;
-  if (lds > kMaxDynLds) { set_error("pcs_conv_gather_gemm_f32_bf16x3: tile_rows too large for this column tile"); return PCS_EUNSUPPORTED; }
-  if (bn_partial && !conv_stats_fit(tile_rows, 16 * nctt, 2 * lds > 160 * 1024 ? 512 : 256)) {
+  const bool nw8 = conv_nw8(tile_rows, nctt);
+  if (conv5_lds_est(tile_rows, nctt) > kMaxDynLds) { set_error("pcs_conv_gather_gemm_f32_bf16x3: tile_rows too large for this column tile"); return PCS_EUNSUPPORTED; }
+  if (bn_partial && !conv_stats_fit(tile_rows, 16 * nctt, nw8 ? 512 : 256)) {
     set_error("pcs_conv_gather_gemm_f32_bf16x3: this tile height does not produce BatchNorm partials");
     return PCS_EUNSUPPORTED;
   }
-  const bool nw8 = 2 * lds > 160 * 1024;  // 4-wave workgroups while two of them fit a CU's LDS, else one 8-wave workgroup
   const bool tail = (cin % 32) != 0;
   hipStream_t st = as_stream(stream);
   // Row blocks per group. The kernel is bound by the vector-memory address path (TA 78-87 % busy, MFMA pipe 29-37 %,

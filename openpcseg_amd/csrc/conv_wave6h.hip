@@ -18,7 +18,7 @@
 // The slice table lives in registers (lane k = offset k; v_readlane), not in LDS: no table barrier in front of the first loads
 // and no LDS round trips in the per-sub-group bookkeeping.
 //
-// Commit: ticket-ordered read-add-write into the LDS tile as in conv_wave5h.hip, in the STATIC order (sub-group i of every wave,
+// Commit: ticket-ordered read-add-write into the LDS tile (the scheme of conv_commit_rows, conv_wave_common.h), in the STATIC order (sub-group i of every wave,
 // waves ascending): race-free, bit-reproducible (a fixed fp32 addition order per launch shape).
 // Epilogue: a thread owns 8 columns: one 16-byte store per row piece (conv_wave5h.hip: 8-byte stores).
 //
@@ -51,17 +51,10 @@ __device__ int g_ws_trace_blocks;
 #endif
 
 template <int NCTT, int NW_>
-struct Conv6hCfg {
-  static constexpr int NW = NW_;
-  static constexpr int NT = 64 * NW;
-  static constexpr int CT = 16 * NCTT;
-  static constexpr int ACS = CT + 4;
-  static constexpr int N4 = NCTT / 4;
-  static constexpr int N2 = (NCTT % 4) / 2;
-  static constexpr int SINK = kConvSinkRows;
-  static constexpr int Q8 = CT / 8;        // epilogue: threads per row (8 columns each)
-  static constexpr int NRG8 = NT / Q8;     // row groups
-  static constexpr size_t lds_bytes(int T) { return (size_t)((T + SINK) * ACS) * 4 + 64; }
+struct Conv6hCfg : ConvWaveCfg<NCTT, NW_> {   // no offset tables in LDS: the slice table lives in registers
+  static constexpr int Q8 = 16 * NCTT / 8;          // epilogue: threads per row (8 columns each)
+  static constexpr int NRG8 = 64 * NW_ / Q8;        // row groups
+  static constexpr size_t lds_bytes(int T) { return conv_tile_bytes(T, NCTT) + 64; }
 };
 
 // Tile epilogue with 16-byte stores: a thread owns 8 consecutive columns and every NRG-th row; `stats` as conv_tile_epilogue
@@ -148,26 +141,17 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
   const int T = a.tile_rows;
   WS_T(const long long tr_entry = __builtin_readcyclecounter(); long long tr_issue = 0, tr_mfma = 0, tr_ticket = 0, tr_commit = 0;)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *acc_l = reinterpret_cast<float *>(smem);                        // [T+SINK][ACS]
-  int *commit = reinterpret_cast<int *>(acc_l + (T + C::SINK) * C::ACS);
-  const unsigned commit_lds = (unsigned)(size_t)(__attribute__((address_space(3))) int *)commit;
-  const unsigned acc_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float *)acc_l;
+  const ConvTileLds tl = conv_tile_lds<C, false>(smem, T);
+  float *acc_l = tl.acc;
+  int *commit = tl.commit;
+  const unsigned commit_lds = tl.commit_lds, acc_lds = tl.acc_lds;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, l15 = lane & 15;
-  unsigned bid = blockIdx.x;
-  if (!a.order) {
-    const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int64_t slot = bid / a.ncoltiles;
-  int ctile = bid % a.ncoltiles;
-  if (a.order) {
-    const unsigned xcd = bid & 7, idx = bid >> 3;
-    slot = (int64_t)(idx / a.ncoltiles) * 8 + xcd;
-    ctile = idx % a.ncoltiles;
-    if (slot >= a.ntiles) return;
-  }
+  int64_t slot;
+  int ctile;
+  conv_block_slot<true>(a, slot, ctile);
+  if (a.order && slot >= a.ntiles) return;  // the grid of an ordered launch is padded to 8 * ncoltiles
   const int64_t tile = a.order ? (int64_t)a.order[slot] : slot;
   const int n0 = ctile * C::CT;
   const int64_t row0 = tile * T;
@@ -337,7 +321,9 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
         for (int t = 0; t < NCTT; ++t) acc[r][t] = mfma_h(HT{}, Ac.v[s][r], B[s][t], acc[r][t]);
     if (reload) load_b(wk_of(pn));   // one burst behind the run's last MFMAs; lands while the commit runs
 
-    // ---- ticket-ordered commit (as conv_wave5h.hip: addresses before the wait, three fenced phases) ----
+    // ---- ticket-ordered commit: addresses before the wait, three phases behind compiler barriers ----
+    // (inline here, not conv_commit_* of conv_wave_common.h -- the reference definition, where the LDS ordering assumption is
+    // stated: shared, this kernel's register allocation moved and instances gained spills; profiles/conv_skeleton_refactor.md)
     unsigned dq[RS][4], dp[RS][4];
 #pragma unroll
     for (int r = 0; r < RS; ++r)
@@ -413,7 +399,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
         asm volatile("" ::: "memory");
       }
     }
-    // the ticket store stays behind the tile writes (the LDS keeps one wave's instructions in order)
+    // the ticket store stays behind the tile writes (the LDS keeps one wave's instructions in order: conv_commit_rows, conv_wave_common.h)
     if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(commit_lds), "v"(ticket + 1) : "memory");
     __builtin_amdgcn_s_setprio(0);
 #if PCS_TRACE
@@ -449,24 +435,8 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
     half_tile_epilogue8<HT, C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, stats, tid, drow, ldd,
                                           a.addend ? a.addend + row0 * a.cout + n0 : nullptr, a.act_slope);
   } else {
-    conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, stats, tid, [&](int r, int cq4, const float4 &v0) {
-      float4 v = v0;
-      if (a.addend) {
-        const uint2 ad = *reinterpret_cast<const uint2 *>(a.addend + (row0 + r) * (int64_t)ldd + n0 + cq4);
-        v.x += h2f(HT{}, (uint16_t)(ad.x & 0xFFFFu)); v.y += h2f(HT{}, (uint16_t)(ad.x >> 16));
-        v.z += h2f(HT{}, (uint16_t)(ad.y & 0xFFFFu)); v.w += h2f(HT{}, (uint16_t)(ad.y >> 16));
-      }
-      if (a.act_slope != 1.f) {
-        v.x = v.x < 0.f ? v.x * a.act_slope : v.x; v.y = v.y < 0.f ? v.y * a.act_slope : v.y;
-        v.z = v.z < 0.f ? v.z * a.act_slope : v.z; v.w = v.w < 0.f ? v.w * a.act_slope : v.w;
-      }
-      const uint16_t hx = f2h(HT{}, v.x), hy = f2h(HT{}, v.y), hz = f2h(HT{}, v.z), hw = f2h(HT{}, v.w);
-      uint2 o;
-      o.x = hx | ((uint32_t)hy << 16);
-      o.y = hz | ((uint32_t)hw << 16);
-      *reinterpret_cast<uint2 *>(drow + (int64_t)r * ldd + cq4) = o;
-      return make_float4(h2f(HT{}, hx), h2f(HT{}, hy), h2f(HT{}, hz), h2f(HT{}, hw));
-    });
+    conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, stats, tid,
+                                     ConvStoreHalf<HT>{drow, a.addend, row0, n0, ldd, a.act_slope});
   }
 #if PCS_TRACE
   if (lane == 0 && g_ws_trace && (int)blockIdx.x < g_ws_trace_blocks) {
@@ -480,19 +450,8 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
 template <typename HT, int NCTT, int NS, int RS, int NW, int KC = 1>
 int launch6h(const ConvArgsH &a, hipStream_t st) {
   using C = Conv6hCfg<NCTT, NW>;
-  const int64_t nblocks = a.order ? ceil_div(a.ntiles, 8) * 8 * a.ncoltiles : a.ntiles * a.ncoltiles;
-  if (nblocks <= 0) return PCS_OK;
-  if (nblocks > 0x7FFFFFFF) { set_error("pcs_conv_h: grid too large"); return PCS_EUNSUPPORTED; }
-  auto kern = conv_os6h_kernel<HT, NCTT, NS, RS, NW, 2, KC>;
-  const size_t lds = C::lds_bytes(a.tile_rows);
-  if (lds > kMaxDynLds) { set_error("pcs_conv_h: tile_rows too large for this column tile"); return PCS_EUNSUPPORTED; }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(C::NT), lds, st, a);
-  return check_launch("pcs_conv_gather_gemm_h(wave6h)");
+  return conv_wave_launch<conv_os6h_kernel<HT, NCTT, NS, RS, NW, 2, KC>>(a, a.order != nullptr, C::NT, C::lds_bytes(a.tile_rows), st, "pcs_conv_h",
+                                                                          "pcs_conv_gather_gemm_h(wave6h)");
 }
 
 // (16-column tiles per column tile, 32-channel steps) the stationary-weight kernel is instantiated for, and the row blocks per
@@ -554,7 +513,7 @@ int launch_conv_wave6h(const ConvArgsH &a0, int dtype, hipStream_t st) {
   a.ncoltiles = (int)ceil_div(a.cout, 16 * nctt);
   int rs = conv6h_rs(nctt, a.ns);
   if (g_ws_rs == 1 && ((nctt == 6 && a.ns == 4) || (nctt == 8 && a.ns == 3))) rs = 2;   // A/B: two row blocks (spills a few registers)
-  const bool nw8 = 2 * conv5_lds_est(a.tile_rows, nctt) > 160 * 1024;
+  const bool nw8 = conv_nw8(a.tile_rows, nctt);
   if (dtype == 1) return nw8 ? dispatch6h<Bf16, 8>(a, nctt, rs, st) : dispatch6h<Bf16, 4>(a, nctt, rs, st);
   return nw8 ? dispatch6h<Fp16, 8>(a, nctt, rs, st) : dispatch6h<Fp16, 4>(a, nctt, rs, st);
 }

@@ -52,7 +52,7 @@ __device__ __forceinline__ void prepare_word(const Job &j, int64_t i) {
   const int gt = (int)(b % j.nt16);
   const int k = (int)(b / j.nt16);
   const int n = lane & 15, g = lane >> 4;
-  const int col = (gt / j.nctt) * 16 * j.nctt + h_local_col(j.nctt, gt % j.nctt, n);
+  const int col = (gt / j.nctt) * 16 * j.nctt + conv_local_col(j.nctt, gt % j.nctt, n);
   uint16_t h[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) {

@@ -282,6 +282,101 @@ def test_conv_on_tiny_maps_with_tile_order(hip, n):
         close(hip.conv_gather_gemm_h(xh, wp, 27, cout, entry.fwd, ordered="force").float(), refh, 1e-2)
 
 
+_GROUP_MAPS = {}
+_DENSE_MAP = {}
+
+
+def _group_shape_maps():
+    """Two full voxel blocks in one batch entry with their k3 submanifold map. With one row tile over a block, offset
+    (dx, dy, dz) holds (A-|dx|)(B-|dy|)(C-|dz|) pairs: 16-row-block counts {1, 2, 3, 4} on 2x5x5 and {3, ..., 7} on 2x6x9."""
+    if not _GROUP_MAPS:
+        from openpcseg_amd import functional as F
+        for dims in ((2, 5, 5), (2, 6, 9)):
+            cube = np.stack(np.meshgrid(*[np.arange(d) for d in dims], indexing="ij"), -1).reshape(-1, 3)
+            c = np.concatenate([cube, np.zeros((len(cube), 1), np.int64)], 1).astype(np.int32)
+            entry = F.build_kernel_map(t(c), t(c), (3, 3, 3), (1, 1, 1), (1, 1, 1))
+            nbmaps, nbsizes = orc.build_kmap(c, c, 3)
+            assert np.array_equal(entry[0].cpu().numpy().astype(np.int64), nbmaps)
+            _GROUP_MAPS[dims] = (entry, nbmaps, nbsizes, len(cube))
+    return _GROUP_MAPS
+
+
+def _assert_group_shape_coverage():
+    """From koff_host, before any kernel runs: the two maps together hold offsets of every 16-row-block count 1 ... 7, i.e. for
+    R = 2, 3 and 4 partial-only groups of 1 ... R - 1 row blocks, slices of full groups only, and full groups followed by every
+    partial size -- a change of map cannot silently empty the test below."""
+    counts = set()
+    for dims, want in (((2, 5, 5), {1, 2, 3, 4}), ((2, 6, 9), {3, 4, 5, 6, 7})):
+        koff = _group_shape_maps()[dims][0].fwd.koff_host
+        got = {(koff[k + 1] - koff[k] + 15) // 16 for k in range(27)}
+        assert got == want, (dims, got)
+        counts |= got
+    for r in (2, 3, 4):
+        shapes = {(n // r > 0, n % r) for n in counts}
+        assert {(False, p) for p in range(1, r)} <= shapes and (True, 0) in shapes and {(True, p) for p in range(1, r)} <= shapes
+
+
+@pytest.mark.parametrize("kernel,cin,cout,dtype", [
+    ("os5", 32, 32, None), ("os5", 64, 96, None), ("os5", 40, 64, None),
+    ("os5x", 32, 32, None), ("os5x", 64, 64, None), ("os5x", 64, 96, None), ("os5x", 40, 64, None),
+    ("os5h", 32, 64, torch.bfloat16), ("os5h", 32, 64, torch.float16), ("os5h", 40, 64, torch.bfloat16),
+    ("os5h", 40, 64, torch.float16), ("os6h", 64, 64, torch.bfloat16), ("os6h", 64, 64, torch.float16)])
+def test_conv_every_group_shape(hip, kernel, cin, cout, dtype):
+    """Group lookup and ticket-ordered commit of every wave kernel against the oracle, on maps whose offsets hold every row-block
+    count 1 ... 7 (every (R, rows-in-partial-group) path), at the narrowest channels that select each instance (fp32 R = 2; x3
+    R = 2 / 4 / 3 at 32 / 64 / 96 columns; TAIL at 40 inputs): one partly filled tile (128 rows) and several tiles with a partly
+    filled last one (32), heaviest-first and row order bit-identical, a repeated launch bit-identical."""
+    import ctypes
+    ws = hip.lib.pcs_debug_convh_ws
+    ws.restype, ws.argtypes = None, [ctypes.c_int32] * 3
+    _assert_group_shape_coverage()
+    for dims, (entry, nbmaps, nbsizes, n) in _group_shape_maps().items():
+        rng = np.random.default_rng(cin * 1000 + cout + n)
+        x = rng.normal(size=(n, cin)).astype(np.float32)
+        w = (rng.normal(size=(27, cin, cout)) / np.sqrt(cin * 27)).astype(np.float32)
+        if dtype is None:
+            ref, tol = orc.conv_fwd(x, w, nbmaps, nbsizes, (n, n)), 2e-5
+            if kernel == "os5":
+                dx, dw = t(x), t(w)
+                run = lambda tile, ordered: hip.conv_gather_gemm(dx, dw, entry.fwd, tile_rows=tile, ordered=ordered)
+            else:
+                assert hip.lib.pcs_conv_x3_applies(cin, cout, 27)
+                dx, wp = t(x), hip.prepare_weights_x3(t(w), transpose=False)
+                run = lambda tile, ordered: hip.conv_gather_gemm_x3(dx, wp, 27, cout, entry.fwd, tile_rows=tile, ordered=ordered)
+        else:
+            dx, wp = t(x).to(dtype), hip.prepare_weights_h(t(w), dtype, transpose=False)
+            ref = orc.conv_fwd(dx.float().cpu().numpy(), t(w).to(dtype).float().cpu().numpy(), nbmaps, nbsizes, (n, n))
+            tol = 1e-2
+            run = lambda tile, ordered: hip.conv_gather_gemm_h(dx, wp, 27, cout, entry.fwd, tile_rows=tile, ordered=ordered)
+        try:
+            for tile in (128, 32):
+                if kernel == "os5h":
+                    ws(0, 0, 0)                           # conv_os5h_kernel serves every shape
+                y = run(tile, "force")
+                close(y.float(), ref, tol)
+                assert torch.equal(y, run(tile, False)) and torch.equal(y, run(tile, "force"))
+        finally:
+            ws(-1, 0, 0)
+    if kernel == "os6h":
+        # Which kernel served: the default mode really ran conv_os6h_kernel for this shape -- same products, another fp32 addition
+        # order than conv_os5h_kernel (mode 0). That shows only where enough sums of many terms get rounded, so on a full 24^3
+        # block (13 824 rows of up to 27 offsets; the maps above are too small to tell two kernels apart bit for bit).
+        if not _DENSE_MAP:
+            from openpcseg_amd import functional as F
+            cube = np.stack(np.meshgrid(*[np.arange(24)] * 3, indexing="ij"), -1).reshape(-1, 3)
+            dc = t(np.concatenate([cube, np.zeros((len(cube), 1), np.int64)], 1).astype(np.int32))
+            _DENSE_MAP[24] = F.build_kernel_map(dc, dc, (3, 3, 3), (1, 1, 1), (1, 1, 1))
+        km = _DENSE_MAP[24].fwd
+        xd = torch.randn(km.n_dst, cin, device=DEV, generator=torch.Generator(device=DEV).manual_seed(5)).to(dtype)
+        try:
+            y6 = hip.conv_gather_gemm_h(xd, wp, 27, cout, km)
+            ws(0, 0, 0)
+            y5 = hip.conv_gather_gemm_h(xd, wp, 27, cout, km)
+        finally:
+            ws(-1, 0, 0)
+        assert not torch.equal(y6, y5)
+
+
 @pytest.mark.parametrize("cin,cout", [(4, 32), (32, 32), (32, 64), (96, 96), (128, 96), (192, 128), (256, 256),
                                       (384, 256), (64, 20), (5, 33), (56, 112)])
 @pytest.mark.parametrize("tile", [64, 128])

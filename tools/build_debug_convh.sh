@@ -9,11 +9,13 @@ name=$1; shift
 python -m openpcseg_amd.build > /dev/null
 mkdir -p $ROOT/openpcseg_amd/lib/dbg /tmp/pcsh_$name
 rm -f /tmp/pcsh_$name/*.o
+# compile lines = openpcseg_amd/build.py: FLAGS + the file's EXTRA_FLAGS
+flags() { python -c "import sys; from openpcseg_amd import build as b; print(' '.join([b.HIPCC] + b.FLAGS + b.EXTRA_FLAGS.get(sys.argv[1], [])))" $1; }
+cd $ROOT
 skip=""
 for f in conv_wave5h.hip conv_wave6h.hip; do
   [ -f $ROOT/openpcseg_amd/csrc/$f ] || continue
-  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -fPIC -Wno-unused-value -Wno-array-bounds \
-    -fno-slp-vectorize "$@" -c $ROOT/openpcseg_amd/csrc/$f -o /tmp/pcsh_$name/$f.o &
+  $(flags $f) "$@" -c $ROOT/openpcseg_amd/csrc/$f -o /tmp/pcsh_$name/$f.o &
   skip="$skip\|/$f.o"
 done
 wait

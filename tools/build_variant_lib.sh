@@ -10,10 +10,11 @@ name=$1; shift
 python -m openpcseg_amd.build > /dev/null
 mkdir -p $ROOT/openpcseg_amd/lib/dbg /tmp/pcsvar_$name
 rm -f /tmp/pcsvar_$name/*.o
-CC="/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -fPIC -Wno-unused-value -Wno-array-bounds"
+# compile lines = openpcseg_amd/build.py: FLAGS + the file's EXTRA_FLAGS
+flags() { python -c "import sys; from openpcseg_amd import build as b; print(' '.join([b.HIPCC] + b.FLAGS + b.EXTRA_FLAGS.get(sys.argv[1], [])))" $1; }
+cd $ROOT
 for f in $ROOT/openpcseg_amd/csrc/conv*.hip; do
-  extra=""; case $(basename $f) in conv_wave5*.hip) extra="-fno-slp-vectorize";; esac  # as openpcseg_amd/build.py EXTRA_FLAGS
-  $CC $extra "$@" -c $f -o /tmp/pcsvar_$name/$(basename $f).o &
+  $(flags $(basename $f)) "$@" -c $f -o /tmp/pcsvar_$name/$(basename $f).o &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC /tmp/pcsvar_$name/*.o \
