@@ -471,6 +471,44 @@ int pcs_bn_bwd_apply_act(const void *dy, const void *x, const void *y, const uin
                          const double *sums2, double count, const double *count_dev, const float *w, int64_t n, int32_t c,
                          int32_t relu, int32_t dtype, float in_slope, void *dx, void *dres, int64_t lddy, void *stream);
 
+/* ---- ReconBlock (DDCM) gate of Cylinder3D (additive, still ABI v12) -----------------------------
+ *   R:pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:337-384
+ *   `out = x * (sigmoid(bn0(conv3x1x1(x))) + sigmoid(bn0_2(conv1x3x1(x))) + sigmoid(bn0_3(conv1x1x3(x))))` with the three conv
+ *   outputs a0, a1, a2 (n, c) given. stat3 = 3 x (mean | invstd) (3 x 2c doubles, branch after branch), gamma3 / beta3 =
+ *   3 x c floats or NULL; bn_k(a) = fma(a, sc, sh) by the expression of pcs_bn_apply_*, xhat_k = (a - mean_k) * invstd_k.
+ *     pcs_recon_gate_*:           out = x * ((s0 + s1) + s2), s_k = 1 / (1 + expf(-bn_k(a_k))); fp32 registers, one rounding
+ *                                 on the store, the gates are never written.
+ *     pcs_recon_gate_bwd_stats_*: with g_k = dy * x * s_k * (1 - s_k): sums2 = 3 x [sum g_k (c) | sum g_k * xhat_k (c)] as
+ *                                 6c doubles FOLLOWED BY the same 6c values as floats (9c doubles of storage, the sums2
+ *                                 convention of ABI v7; `sums2_doubles` < 9c is PCS_EWORKSPACE). Two-level, fixed order:
+ *                                 bit-identical from run to run. partial_ws: pcs_bn_num_partials() * 6c floats. The 6c doubles
+ *                                 are what a data-parallel run all-reduces: one collective for the whole block.
+ *     pcs_recon_gate_bwd_apply_*: dx_gate = dy * ((s0 + s1) + s2) (the gradient of x through the product only) and
+ *                                 da_k = (g_k - sum_g_k / N - xhat_k * sum_gxhat_k / N) * invstd_k * gamma_k; the sigmoids are
+ *                                 recomputed from a_k. count / count_dev as pcs_bn_bwd_apply_* take them.
+ *   (dgamma_k = sums2[(2k + 1)c ..], dbeta_k = sums2[2kc ..].) No atomics; every output element is written exactly once.
+ *   fp32: c % 4 == 0; _h (all tensors bf16, dtype 1, or fp16, dtype 2; any other dtype is PCS_EINVAL): c % 8 == 0; every row
+ *   pointer 16-byte aligned; anything else is PCS_EUNSUPPORTED with nothing launched. n == 0 is a no-op that returns PCS_OK
+ *   before any pointer is looked at (nothing is written, sums2 included); a NULL tensor with n > 0 is PCS_EINVAL. */
+int pcs_recon_gate_f32(const float *a0, const float *a1, const float *a2, const float *x, const double *stat3,
+                       const float *gamma3, const float *beta3, int64_t n, int32_t c, float *out, void *stream);
+int pcs_recon_gate_h(const void *a0, const void *a1, const void *a2, const void *x, const double *stat3, const float *gamma3,
+                     const float *beta3, int64_t n, int32_t c, int32_t dtype, void *out, void *stream);
+int pcs_recon_gate_bwd_stats_f32(const float *dy, const float *x, const float *a0, const float *a1, const float *a2,
+                                 const double *stat3, const float *gamma3, const float *beta3, int64_t n, int32_t c,
+                                 float *partial_ws, double *sums2, int64_t sums2_doubles, void *stream);
+int pcs_recon_gate_bwd_stats_h(const void *dy, const void *x, const void *a0, const void *a1, const void *a2,
+                               const double *stat3, const float *gamma3, const float *beta3, int64_t n, int32_t c,
+                               int32_t dtype, float *partial_ws, double *sums2, int64_t sums2_doubles, void *stream);
+int pcs_recon_gate_bwd_apply_f32(const float *dy, const float *x, const float *a0, const float *a1, const float *a2,
+                                 const double *stat3, const float *gamma3, const float *beta3, const double *sums2,
+                                 double count, const double *count_dev, int64_t n, int32_t c, float *dx_gate, float *da0,
+                                 float *da1, float *da2, void *stream);
+int pcs_recon_gate_bwd_apply_h(const void *dy, const void *x, const void *a0, const void *a1, const void *a2,
+                               const double *stat3, const float *gamma3, const float *beta3, const double *sums2, double count,
+                               const double *count_dev, int64_t n, int32_t c, int32_t dtype, void *dx_gate, void *da0,
+                               void *da1, void *da2, void *stream);
+
 /* ---- device-side sparse_quantize ---------------------------------------------------------------
  * Replaces the dataloader-side NumPy voxel dedup TS:torchsparse/utils/quantize.py:9-46
  * (ravel_hash :9-21, sparse_quantize :24-46; called from R:pcseg/data/dataset/semantickitti/

@@ -346,6 +346,43 @@ class TorchCpuBackend:
         y, mask = self.bn_apply(_cpu(lin, "input").float(), None, stat, gamma, beta, True, want_mask=True)
         return self.devoxelize_fwd(vox, idx8, w8) + y, mask
 
+    # -- ReconBlock gate of Cylinder3D (csrc/recongate.hip), the same formulas in plain torch
+    @staticmethod
+    def _recon_terms(a3, stat3, gamma3, beta3):
+        """-> per branch (s_k, xhat_k, invstd_k * gamma_k): s_k = sigmoid(bn_k(a_k)), fp32."""
+        c = a3[0].shape[1]
+        out = []
+        for k, a in enumerate(a3):
+            a = _cpu(a, "input").float()
+            mean, invstd = stat3[2 * k * c:(2 * k + 1) * c].float(), stat3[(2 * k + 1) * c:(2 * k + 2) * c].float()
+            sc = invstd * gamma3[k * c:(k + 1) * c] if gamma3 is not None else invstd
+            sh = (beta3[k * c:(k + 1) * c] if beta3 is not None else 0.0) - mean * sc
+            out.append((1.0 / (1.0 + torch.exp(-(a * sc + sh))), (a - mean) * invstd, sc))
+        return out
+
+    def recon_gate(self, a3, x, stat3, gamma3, beta3):
+        (s0, _, _), (s1, _, _), (s2, _, _) = self._recon_terms(a3, stat3, gamma3, beta3)
+        return _cpu(x, "input").float() * ((s0 + s1) + s2)
+
+    def recon_gate_bwd_stats(self, dy, x, a3, stat3, gamma3, beta3):
+        p = (dy * x).float()
+        parts = []
+        for s, xh, _ in self._recon_terms(a3, stat3, gamma3, beta3):
+            g = p * (s * (1.0 - s))
+            parts += [g.double().sum(0), (g * xh).double().sum(0)]
+        return torch.cat(parts)
+
+    def recon_gate_bwd_apply(self, dy, x, a3, stat3, gamma3, beta3, sums2, count, count_dev=None):
+        c = x.shape[1]
+        n = float(count_dev[0]) if count_dev is not None else float(count)
+        n = n if n > 0 else 1.0
+        p, terms = (dy * x).float(), self._recon_terms(a3, stat3, gamma3, beta3)
+        da = []
+        for k, (s, xh, sc) in enumerate(terms):
+            g = p * (s * (1.0 - s))
+            da.append((g - (sums2[2 * k * c:(2 * k + 1) * c] / n).float() - xh * (sums2[(2 * k + 1) * c:(2 * k + 2) * c] / n).float()) * sc)
+        return dy.float() * ((terms[0][0] + terms[1][0]) + terms[2][0]), da
+
     def bn_bwd_stats(self, dy, x, gate, stat, relu):
         c = x.shape[1]
         g = dy * self._gate(gate, c) if relu else dy

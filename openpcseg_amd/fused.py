@@ -66,6 +66,34 @@ def _stats_group():
     return g or None
 
 
+def _train_stat(be, x, pre, sync, eps, momentum, running_mean, running_var):
+    """Training-mode statistics of one BatchNorm over the contiguous (n, c) tensor x -> (stat = mean | invstd, host count, device
+    count or None); the running statistics are updated. pre: what the producing convolution handed over, or None."""
+    n, c = x.shape
+    # [sum x | sum x^2 | n]: handed over by the producing convolution (its write-back computed them), else one pass
+    syncing = _syncing(sync)
+    # an empty tensor (a rank without voxels): count read as 1, as the kernels read a zero device count
+    count, count_dev, stat = float(max(n, 1)), None, None
+    raw = pre is not None and pre.numel() != 2 * c + 1 and pre.numel() > 0 and pre.numel() % (2 * c) == 0
+    if raw and not syncing and n > 0:
+        # the producing convolution's per-tile partials: reduction and finalize in one launch (nothing to all-reduce)
+        stat = be.bn_reduce_finalize(pre, c, n, eps, momentum, running_mean, running_var)
+    elif raw:
+        sums = be.bn_reduce_partials(pre, c, n)
+    elif pre is not None and pre.numel() == 2 * c + 1:
+        sums = pre.clone() if syncing else pre  # the all-reduce below works in place
+    else:
+        sums = be.bn_stats(x)
+    if syncing:
+        # ONE collective per layer and direction: the row count rides in the statistics vector and the global
+        # count stays on the device (finalize / bwd_apply read it there) -- no count all-reduce, no host sync
+        dist.all_reduce(sums, group=_stats_group())
+        count_dev = sums[2 * c:]
+    if stat is None:
+        stat = be.bn_finalize(sums, count, eps, momentum, running_mean, running_var, count_dev=count_dev)
+    return stat, count, count_dev
+
+
 class _FusedBN(Function):
     """Feature tensors may be fp32, bf16 or fp16 (mixed precision: the half convolutions hand on halfs); statistics,
     scale / shift and running stats are fp32 / double whatever the storage format."""
@@ -83,27 +111,7 @@ class _FusedBN(Function):
         x = x.contiguous()
         res = res.contiguous() if res is not None else None
         n, c = x.shape
-        # [sum x | sum x^2 | n]: handed over by the producing convolution (its write-back computed them), else one pass
-        syncing = _syncing(sync)
-        # an empty tensor (a rank without voxels): count read as 1, as the kernels read a zero device count
-        count, count_dev, stat = float(max(n, 1)), None, None
-        raw = pre is not None and pre.numel() != 2 * c + 1 and pre.numel() > 0 and pre.numel() % (2 * c) == 0
-        if raw and not syncing and n > 0:
-            # the producing convolution's per-tile partials: reduction and finalize in one launch (nothing to all-reduce)
-            stat = be.bn_reduce_finalize(pre, c, n, eps, momentum, running_mean, running_var)
-        elif raw:
-            sums = be.bn_reduce_partials(pre, c, n)
-        elif pre is not None and pre.numel() == 2 * c + 1:
-            sums = pre.clone() if syncing else pre  # the all-reduce below works in place
-        else:
-            sums = be.bn_stats(x)
-        if syncing:
-            # ONE collective per layer and direction: the row count rides in the statistics vector and the global
-            # count stays on the device (finalize / bwd_apply read it there) -- no count all-reduce, no host sync
-            dist.all_reduce(sums, group=_stats_group())
-            count_dev = sums[2 * c:]
-        if stat is None:
-            stat = be.bn_finalize(sums, count, eps, momentum, running_mean, running_var, count_dev=count_dev)
+        stat, count, count_dev = _train_stat(be, x, pre, sync, eps, momentum, running_mean, running_var)
         # c % 32 == 0: the backward passes read the ReLU gate as a bit mask (1/32 of a tensor) instead of y
         if relu and c % 32 == 0 and c % 4 == 0:
             y, gate = be.bn_apply(x, res, stat, weight, bias, relu, want_mask=True, tail=tail)
@@ -162,9 +170,10 @@ class FusedBatchNorm(nn.Module):
     def extra_repr(self):
         return "%d, eps=%g, momentum=%g, sync=%s" % (self.num_features, self.eps, self.momentum, self.sync)
 
-    def forward(self, input, residual=None, relu=False, cat_with=None):
+    def forward(self, input, residual=None, relu=False, cat_with=None, in_slope=None):
         """cat_with: a SparseTensor / tensor on the same coordinates; the result then carries cat([bn(x), cat_with], 1)
-        (torchsparse.cat of the reference's decoder, fused into the apply pass)."""
+        (torchsparse.cat of the reference's decoder, fused into the apply pass). in_slope: the input is the output of a
+        LeakyReLU that the producing convolution applied in its write-back (`_FusedBN.forward`)."""
         x = input.feats
         r = residual.feats if isinstance(residual, SparseTensor) else residual
         tail = cat_with.feats if isinstance(cat_with, SparseTensor) else cat_with
@@ -182,7 +191,7 @@ class FusedBatchNorm(nn.Module):
                 sums, of, ver = pre
                 pre = sums if (of is x and x._version == ver) else None
             y = _FusedBN.apply(x, r, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
-                               self.momentum, relu, self.sync, input.cmaps, input.stride, pre, tail)
+                               self.momentum, relu, self.sync, input.cmaps, input.stride, pre, tail, in_slope)
         else:
             inv = torch.rsqrt(self.running_var.double() + self.eps)
             stat = torch.cat([self.running_mean.double(), inv]).contiguous()
@@ -465,3 +474,120 @@ def point_merge(bn, lin_out, vox_feats, idx8, w8):
         return be.point_merge(vox_feats.contiguous(), idx8.contiguous().int(), w8.contiguous().float(), lin_out.contiguous(),
                               stat, bn.weight, bn.bias)[0]
     return F_.spdevoxelize(vox_feats, idx8, w8) + be.bn_apply(lin_out.contiguous(), None, stat, bn.weight, bn.bias, True)
+
+
+# ---- Cylinder3D's ReconBlock gate ------------------------------------------------------------------------------------------
+def _gate_enabled():
+    import os
+    return os.environ.get("PCS_RECON_GATE", "1") != "0"   # A/B switch: 0 = the literal sequence
+
+
+def _feats_pre(t):
+    """(features, statistics the producing convolution handed over for exactly this tensor or None) of a SparseTensor / tensor."""
+    if not isinstance(t, SparseTensor):
+        return t, None
+    x, pre = t.feats, getattr(t, "bn_sums", None)
+    if pre is not None:
+        sums, of, ver = pre
+        pre = sums if (of is x and x._version == ver) else None
+    return x, pre
+
+
+def _bn_sync(bn):
+    return bool(getattr(bn, "sync", isinstance(bn, nn.SyncBatchNorm)))
+
+
+def _running_stat(bn):
+    inv = torch.rsqrt(bn.running_var.double() + bn.eps)
+    return torch.cat([bn.running_mean.double(), inv]).contiguous()
+
+
+class _ReconGate(Function):
+    """out = x * (sigmoid(bn0(a0)) + sigmoid(bn1(a1)) + sigmoid(bn2(a2))) with training-mode statistics
+    (R:pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:368-384): the three apply passes, the sigmoids, the adds and the
+    multiply in ONE kernel per direction (csrc/recongate.hip). Statistics, all-reduce and running statistics per branch as
+    `_FusedBN`; backward all-reduces the three branches' sums as one 6c vector. Only the forward's inputs are saved. The gradient
+    returned for x is the one through the product; the one through the convolutions arrives by a0..a2."""
+
+    @staticmethod
+    def forward(ctx, x, a0, a1, a2, w0, b0, w1, b1, w2, b2, bns, pres):
+        be = native.backend()
+        x = x.contiguous()
+        a3 = [a0.contiguous(), a1.contiguous(), a2.contiguous()]
+        stats, count, count_dev = [], float(max(x.shape[0], 1)), None
+        for bn, a, pre in zip(bns, a3, pres):
+            stat, count, cd = _train_stat(be, a, pre, _bn_sync(bn), bn.eps, bn.momentum, bn.running_mean, bn.running_var)
+            stats.append(stat)
+            count_dev = cd if count_dev is None else count_dev   # the same global row count in every branch
+        stat3 = torch.cat(stats)
+        gamma3, beta3 = torch.cat([w0, w1, w2]).float(), torch.cat([b0, b1, b2]).float()
+        out = be.recon_gate(a3, x, stat3, gamma3, beta3)
+        ctx.save_for_backward(x, a3[0], a3[1], a3[2], stat3, gamma3, beta3, count_dev)
+        ctx.cfg = (count, any(_bn_sync(bn) for bn in bns), w0.dtype, (x.dtype, a0.dtype, a1.dtype, a2.dtype))
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        be = native.backend()
+        x, a0, a1, a2, stat3, gamma3, beta3, count_dev = ctx.saved_tensors
+        count, sync, wdtype, in_dtypes = ctx.cfg
+        c = x.shape[1]
+        a3 = [a0, a1, a2]
+        dy = dy.contiguous()
+        local = be.recon_gate_bwd_stats(dy, x, a3, stat3, gamma3, beta3)
+        sums2 = local
+        if _syncing(sync):
+            sums2 = local.clone()
+            dist.all_reduce(sums2, group=_stats_group())   # ONE collective for the three BatchNorms
+        dx, da = be.recon_gate_bwd_apply(dy, x, a3, stat3, gamma3, beta3, sums2, count, count_dev=count_dev)
+        lw = getattr(local, "_pcs_f32", None)   # local sums: DDP averages parameter grads
+        if lw is None or lw.dtype != wdtype:
+            lw = local.to(wdtype)
+        wb = []
+        for k in range(3):
+            wb += [lw[(2 * k + 1) * c:(2 * k + 2) * c], lw[2 * k * c:(2 * k + 1) * c]]
+        grads = [g if g.dtype == d else g.to(d) for g, d in zip([dx] + list(da), in_dtypes)]
+        return (*grads, *wb, None, None)
+
+
+def recon_gate(bns, conv_outs, x):
+    """`x * (sigmoid(bns[0](conv_outs[0])) + sigmoid(bns[1](conv_outs[1])) + sigmoid(bns[2](conv_outs[2])))`: the ReconBlock gate of
+    Cylinder3D -> (N, C) features. bns: three FusedBatchNorm (or BatchNorm1d-shaped) modules; conv_outs: the three convolutions'
+    outputs, SparseTensors (whose write-back statistics are used where present) or (N, C) tensors; x: SparseTensor or tensor.
+    One kernel per direction when the backend has `recon_gate`, the width is a multiple of 4 (fp32) / 8 (16 bits) and the rows
+    are 16-byte aligned (PCS_RECON_GATE=0 switches it off); otherwise the literal sequence: three fused BatchNorm applies,
+    torch.sigmoid, adds, multiply. Eval mode: the running statistics, same kernel."""
+    be = native.backend()
+    xf = x.feats if isinstance(x, SparseTensor) else x
+    got = [_feats_pre(t) for t in conv_outs]
+    feats = [xf] + [a for a, _ in got]
+    halfs = (torch.bfloat16, torch.float16)
+    dt = xf.dtype if all(t.dtype == xf.dtype for t in feats) else torch.float32
+    fused = (_gate_enabled() and hasattr(be, "recon_gate") and len(bns) == 3 and len(got) == 3 and
+             all(t.dim() == 2 and t.shape == xf.shape and t.dtype in (torch.float32,) + halfs for t in feats) and
+             xf.shape[1] % (8 if dt in halfs else 4) == 0 and
+             (all(t.is_cuda for t in feats) or getattr(be, "name", "") == "torch-cpu") and
+             all(t.data_ptr() % 16 == 0 or not t.is_contiguous() for t in feats) and
+             all(bn.weight is not None and bn.bias is not None for bn in bns) and
+             all(bn.training == bns[0].training for bn in bns))
+    if any(bn.training for bn in bns):
+        for bn in bns:
+            if bn.training and not getattr(bn, "counted_by_parent", False):
+                bn.num_batches_tracked += 1
+    if fused and bns[0].training:
+        return _ReconGate.apply(xf, got[0][0], got[1][0], got[2][0], bns[0].weight, bns[0].bias, bns[1].weight, bns[1].bias,
+                                bns[2].weight, bns[2].bias, list(bns), [pre for _, pre in got])
+    if fused:
+        stat3 = torch.cat([_running_stat(bn) for bn in bns])
+        return be.recon_gate([a.contiguous() for a, _ in got], xf.contiguous(), stat3,
+                             torch.cat([bn.weight for bn in bns]).float(), torch.cat([bn.bias for bn in bns]).float())
+    gate = None
+    for bn, (a, pre) in zip(bns, got):
+        if bn.training:
+            y = _FusedBN.apply(a, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, False,
+                               _bn_sync(bn), None, None, pre, None)
+        else:
+            y = be.bn_apply(a.contiguous(), None, _running_stat(bn), bn.weight, bn.bias, False)
+        s = torch.sigmoid(y)
+        gate = s if gate is None else gate + s
+    return gate * xf

@@ -38,6 +38,14 @@ SIGNATURES = {
     "pcs_devoxelize_bwd_csr_h": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
     "pcs_point_merge_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P]),
     "pcs_point_merge_h": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P]),
+    "pcs_recon_gate_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P]),
+    "pcs_recon_gate_h": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
+    "pcs_recon_gate_bwd_stats_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, c_int64, _P]),
+    "pcs_recon_gate_bwd_stats_h": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P]),
+    "pcs_recon_gate_bwd_apply_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_double, _P, c_int64, c_int32,
+                                               _P, _P, _P, _P, _P]),
+    "pcs_recon_gate_bwd_apply_h": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_double, _P, c_int64, c_int32, c_int32,
+                                             _P, _P, _P, _P, _P]),
     "pcs_corner_map_f32": (c_int32, [_P, c_int32, c_int64, c_int32, _P, c_int64, _P, _P, _P]),
     "pcs_ti_weights_f32": (c_int32, [_P, c_int32, _P, c_int64, c_float, _P, _P]),
     "pcs_downsample_pack": (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, _P, _P, _P, _P]),
@@ -1188,6 +1196,64 @@ class HipBackend:
         else:
             _check(self.lib.pcs_bn_bwd_apply_h(*head, self._HALF[x.dtype], *tail), "pcs_bn_bwd_apply_h")
         return dx, dres
+
+    # -- ReconBlock gate of Cylinder3D (csrc/recongate.hip) ------------------------------------------------
+    def _recon_rows(self, tensors):
+        """The (n, c) tensors of one gate call in ONE storage dtype (fp32 beside 16 bits is cast up), contiguous -> (list, code)."""
+        ts = [self._feat(t, "input") for t in tensors]
+        dt = ts[0].dtype if all(t.dtype == ts[0].dtype for t in ts) else torch.float32
+        ts = [(t if t.dtype == dt else t.to(dt)).contiguous() for t in ts]
+        if any(t.dim() != 2 or t.shape != ts[0].shape for t in ts):
+            raise ValueError("openpcseg_amd: the recon gate takes (n, c) tensors of one shape, got %s" % [tuple(t.shape) for t in ts])
+        return ts, (0 if dt == torch.float32 else self._HALF[dt])
+
+    def recon_gate(self, a3, x, stat3, gamma3, beta3):
+        """out = x * ((s0 + s1) + s2), s_k = sigmoid(bn_k(a3[k])): the ReconBlock gate in one pass. stat3 (6c,) float64 =
+        3 x (mean | invstd); gamma3 / beta3 (3c,) float32 or None."""
+        (a0, a1, a2, x), code = self._recon_rows(list(a3) + [x])
+        n, c = x.shape
+        out = torch.empty_like(x)
+        args = [_ptr(a0), _ptr(a1), _ptr(a2), _ptr(x), _ptr(stat3), _ptr(gamma3) if gamma3 is not None else None,
+                _ptr(beta3) if beta3 is not None else None, n, c]
+        if code:
+            _check(self.lib.pcs_recon_gate_h(*args, code, _ptr(out), _stream()), "pcs_recon_gate_h")
+        else:
+            _check(self.lib.pcs_recon_gate_f32(*args, _ptr(out), _stream()), "pcs_recon_gate_f32")
+        return out
+
+    def recon_gate_bwd_stats(self, dy, x, a3, stat3, gamma3, beta3):
+        """-> sums2 (6c,) float64 = 3 x [sum g_k | sum g_k xhat_k]; `._pcs_f32`: the same values in fp32 (dbeta_k | dgamma_k)."""
+        (dy, x, a0, a1, a2), code = self._recon_rows([dy, x] + list(a3))
+        n, c = x.shape
+        buf = torch.empty(9 * c, dtype=torch.float64, device=x.device) if n > 0 else \
+            torch.zeros(9 * c, dtype=torch.float64, device=x.device)   # an empty shard: the entry returns before it writes
+        ws = torch.empty(self.lib.pcs_bn_num_partials() * 6 * c, dtype=torch.float32, device=x.device)
+        sums2 = buf[:6 * c]
+        sums2._pcs_f32 = buf[6 * c:].view(torch.float32)
+        args = [_ptr(dy), _ptr(x), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(stat3), _ptr(gamma3) if gamma3 is not None else None,
+                _ptr(beta3) if beta3 is not None else None, n, c]
+        tail = [_ptr(ws), _ptr(sums2), buf.numel(), _stream()]
+        if code:
+            _check(self.lib.pcs_recon_gate_bwd_stats_h(*args, code, *tail), "pcs_recon_gate_bwd_stats_h")
+        else:
+            _check(self.lib.pcs_recon_gate_bwd_stats_f32(*args, *tail), "pcs_recon_gate_bwd_stats_f32")
+        return sums2
+
+    def recon_gate_bwd_apply(self, dy, x, a3, stat3, gamma3, beta3, sums2, count, count_dev=None):
+        """-> (dx_gate, [da0, da1, da2]): the gradient of x through the product, and of the three conv outputs."""
+        (dy, x, a0, a1, a2), code = self._recon_rows([dy, x] + list(a3))
+        n, c = x.shape
+        dx = torch.empty_like(x)
+        da = [torch.empty_like(x) for _ in range(3)]
+        args = [_ptr(dy), _ptr(x), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(stat3), _ptr(gamma3) if gamma3 is not None else None,
+                _ptr(beta3) if beta3 is not None else None, _ptr(sums2), float(count),
+                _ptr(count_dev) if count_dev is not None else None, n, c]
+        tail = [_ptr(dx), _ptr(da[0]), _ptr(da[1]), _ptr(da[2]), _stream()]
+        if code:
+            _check(self.lib.pcs_recon_gate_bwd_apply_h(*args, code, *tail), "pcs_recon_gate_bwd_apply_h")
+        else:
+            _check(self.lib.pcs_recon_gate_bwd_apply_f32(*args, *tail), "pcs_recon_gate_bwd_apply_f32")
+        return dx, da
 
     # -- device-side sparse_quantize --------------------------------------------------------------------
     def quantize(self, points, voxel_size3, want_index, want_inverse):

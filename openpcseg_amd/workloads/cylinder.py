@@ -1,0 +1,289 @@
+"""Cylinder3D (Cylinder_TS) workload on the HIP operator API.
+
+Architecture and state_dict layout of R:pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:387-588 (so reference
+checkpoints load): point MLP `PPmodel` (BatchNorm over the raw 9 point features, three Linear-BatchNorm-ReLU, a Linear) ->
+scatter-max voxelisation (R:tools/utils/common/seg_utils.py:172-188) -> `fea_compression` -> ResContextBlock `downCntx` ->
+four ResBlocks with a strided k3 `pool` (stride 2, 2, then (2, 2, 1) twice) -> four UpBlocks (`trans_dilao`, transposed
+`up_subm`, skip add, three asymmetric convs) -> ReconBlock `ReconNet` -> concat -> k3 `logits` conv with bias -> point
+refinement (`change_dim`, `point_logits`). Every block convolution is conv -> LeakyReLU -> BatchNorm: the slope rides in
+the convolution's write-back and in the BatchNorm backward (`in_slope`), and the statistics come from the write-back where
+the kernel emits them -- the fusions block_fusion.py applies to the reference's own blocks. The ReconBlock gate
+
+    out = x * (sigmoid(bn0(conv3x1x1(x))) + sigmoid(bn0_2(conv1x3x1(x))) + sigmoid(bn0_3(conv1x1x3(x))))      (cylinder_ts.py:368-384)
+
+is one kernel per direction behind the three convolutions (fused.recon_gate, csrc/recongate.hip); PCS_RECON_GATE=0 and widths
+the kernel does not serve take the literal sequence. cy480 = init_size 32 (R:tools/cfgs/voxel/semantic_kitti/cylinder_cy480_cr10.yaml).
+"""
+import os
+
+import numpy as np
+import torch
+from torch import nn
+
+from .. import functional as F
+from .. import fused, native
+from .. import modules as spnn
+from ..block_fusion import _PointLinear
+from ..fused import FusedBatchNorm, _FusedBN
+from ..scatter import scatter_max
+from ..sparse import SparseTensor
+from .losses import SegLoss
+
+SLOPE = 0.01   # nn.LeakyReLU() of the reference's blocks
+CYL_FUSED = os.environ.get("PCS_CYL_FUSED", "1") != "0"    # LeakyReLU in the convolution's write-back (A/B switch of block_fusion)
+SKIP_FUSED = os.environ.get("PCS_SKIP_FUSED", "1") != "0"  # a block input's two gradients added in the dgrad write-back
+
+
+def _linear(lin, x):
+    """nn.Linear over point / voxel rows; on the device the weight gradient runs on the split-reduction kernel."""
+    if x.is_cuda and lin.out_features % 4 == 0 and x.shape[0] >= 4096:
+        return _PointLinear.apply(x, lin.weight, lin.bias)
+    return lin(x)
+
+
+def _dense_bn(bn, h, relu=False):
+    """A FusedBatchNorm over plain (N, C) rows (the point MLPs): the fused statistics / apply passes."""
+    if bn.training:
+        if not bn.counted_by_parent:
+            bn.num_batches_tracked += 1
+        return _FusedBN.apply(h, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu, bn.sync,
+                              None, None, None, None)
+    return native.backend().bn_apply(h.contiguous(), None, fused._running_stat(bn), bn.weight, bn.bias, relu)
+
+
+def _cab(conv, bn, x, residual=None, want_skip=False):
+    """conv -> LeakyReLU -> BatchNorm (+ residual) on a SparseTensor; -> (result, x routed through conv when want_skip)."""
+    if CYL_FUSED and conv.bias is None and conv.kernel.dim() == 3 and F.conv_act_fusable(x.feats, conv.kernel):
+        skip = want_skip and SKIP_FUSED and torch.is_grad_enabled() and x.feats.requires_grad
+        out = F.conv3d(x, conv.kernel, kernel_size=conv.kernel_size, stride=conv.stride, dilation=conv.dilation,
+                       transposed=conv.transposed, bn_stats=bn.training, with_skip=skip, act_slope=SLOPE)
+        h, xs = out if skip else (out, x)
+        y = bn(h, residual=residual, in_slope=SLOPE)
+    else:
+        h, xs = conv(x), x
+        h.F = torch.nn.functional.leaky_relu(h.F, SLOPE)
+        y = bn(h, residual=residual)
+    return (y, xs) if want_skip else y
+
+
+def _conv(cin, cout, ks, stride=1, transposed=False, bias=False):
+    return spnn.Conv3d(cin, cout, kernel_size=ks, stride=stride, bias=bias, transposed=transposed)
+
+
+class ResContextBlock(nn.Module):       # cylinder_ts.py:88-155
+    first, second = (1, 3, 3), (3, 1, 3)
+
+    def __init__(self, cin, cout, dist):
+        super().__init__()
+        self.conv1, self.act1, self.bn0 = _conv(cin, cout, self.first), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+        self.conv1_2, self.act1_2, self.bn0_2 = _conv(cout, cout, self.second), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+        self.conv2, self.act2, self.bn1 = _conv(cin, cout, self.second), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+        self.conv3, self.act3, self.bn2 = _conv(cout, cout, self.first), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+
+    def forward(self, x):
+        shortcut, xs = _cab(self.conv1, self.bn0, x, want_skip=True)
+        shortcut = _cab(self.conv1_2, self.bn0_2, shortcut)
+        res_a = _cab(self.conv2, self.bn1, xs)
+        return _cab(self.conv3, self.bn2, res_a, residual=shortcut)
+
+
+class ResBlock(ResContextBlock):        # cylinder_ts.py:158-250: the other order of the asymmetric pair, then `pool`
+    first, second = (3, 1, 3), (1, 3, 3)
+
+    def __init__(self, cin, cout, dist, height_pooling):
+        super().__init__(cin, cout, dist)
+        self.pool = _conv(cout, cout, 3, stride=2 if height_pooling else (2, 2, 1))
+
+    def forward(self, x):
+        res_a = super().forward(x)
+        return self.pool(res_a), res_a
+
+
+class UpBlock(nn.Module):               # cylinder_ts.py:253-334
+    def __init__(self, cin, cout, dist, height_pooling):
+        super().__init__()
+        self.trans_dilao, self.trans_act, self.trans_bn = _conv(cin, cout, 3), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+        self.conv1, self.act1, self.bn1 = _conv(cout, cout, (1, 3, 3)), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+        self.conv2, self.act2, self.bn2 = _conv(cout, cout, (3, 1, 3)), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+        self.conv3, self.act3, self.bn3 = _conv(cout, cout, 3), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+        self.up_subm = _conv(cout, cout, 3, stride=2 if height_pooling else (2, 2, 1), transposed=True)
+
+    def forward(self, x, skip):
+        up_a = self.up_subm(_cab(self.trans_dilao, self.trans_bn, x))
+        up_a.F = up_a.F + skip.F
+        up_e = _cab(self.conv1, self.bn1, up_a)
+        up_e = _cab(self.conv2, self.bn2, up_e)
+        return _cab(self.conv3, self.bn3, up_e)
+
+
+class ReconBlock(nn.Module):            # cylinder_ts.py:337-384
+    def __init__(self, cin, cout, dist):
+        super().__init__()
+        self.conv1, self.bn0, self.act1 = _conv(cin, cout, (3, 1, 1)), FusedBatchNorm(cout, sync=dist), nn.Sigmoid()
+        self.conv1_2, self.bn0_2, self.act1_2 = _conv(cin, cout, (1, 3, 1)), FusedBatchNorm(cout, sync=dist), nn.Sigmoid()
+        self.conv1_3, self.bn0_3, self.act1_3 = _conv(cin, cout, (1, 1, 3)), FusedBatchNorm(cout, sync=dist), nn.Sigmoid()
+        for conv in (self.conv1, self.conv1_2, self.conv1_3):   # the statistics of the three conv outputs from their write-back
+            conv.emit_bn_stats = os.environ.get("PCS_CONV_BN_STATS", "1") != "0"
+
+    def forward(self, x):
+        outs = [self.conv1(x), self.conv1_2(x), self.conv1_3(x)]
+        return outs[0]._like(fused.recon_gate([self.bn0, self.bn0_2, self.bn0_3], outs, x))
+
+
+def voxelize(z_feats, z_coords):
+    """`voxelize(z)` of R:tools/utils/common/seg_utils.py:172-188: hash of the points' integer cells, unique with first index and
+    inverse, count, scatter_max -> SparseTensor whose rows follow the sorted unique hashes. z_coords (N, 4) float, batch last."""
+    icoords = z_coords.int()
+    pc_hash = F.sphash(icoords)
+    be = native.backend()
+    if icoords.is_cuda and hasattr(be, "unique_inverse_csr"):
+        sparse_hash, idx_query, _ = be.unique_inverse_csr(pc_hash)   # unique + inverse + count from one stable sort
+    else:
+        sparse_hash, idx_query = torch.unique(pc_hash, return_inverse=True)
+    m, n = sparse_hash.shape[0], pc_hash.shape[0]
+    # a voxel's representative: its first point (every point of a voxel carries the same integer coordinates)
+    inds = torch.full((m,), n, dtype=torch.int64, device=pc_hash.device).scatter_reduce(
+        0, idx_query, torch.arange(n, device=pc_hash.device), "amin")
+    x = SparseTensor(scatter_max(z_feats, idx_query, dim=0, dim_size=m)[0], icoords[inds].contiguous(), 1)
+    x.cmaps.setdefault(x.stride, x.coords)
+    return x
+
+
+class CylinderTS(nn.Module):
+    def __init__(self, num_class=20, in_dim=9, init_size=32, point_refinement=True, dist=False, label_smoothing=0.0, ignore_label=0):
+        super().__init__()
+        s = init_size
+        self.num_class, self.in_dim, self.init_size, self.point_refinement = num_class, in_dim, init_size, point_refinement
+        norm = lambda c: FusedBatchNorm(c, sync=dist)
+        self.PPmodel = nn.Sequential(norm(in_dim), nn.Linear(in_dim, 64), norm(64), nn.ReLU(), nn.Linear(64, 128), norm(128), nn.ReLU(),
+                                     nn.Linear(128, 256), norm(256), nn.ReLU(), nn.Linear(256, 256))
+        self.fea_compression = nn.Sequential(nn.Linear(256, 16), nn.ReLU())
+        self.downCntx = ResContextBlock(16, s, dist)
+        self.resBlock2 = ResBlock(s, 2 * s, dist, height_pooling=True)
+        self.resBlock3 = ResBlock(2 * s, 4 * s, dist, height_pooling=True)
+        self.resBlock4 = ResBlock(4 * s, 8 * s, dist, height_pooling=False)
+        self.resBlock5 = ResBlock(8 * s, 16 * s, dist, height_pooling=False)
+        self.upBlock0 = UpBlock(16 * s, 16 * s, dist, height_pooling=False)
+        self.upBlock1 = UpBlock(16 * s, 8 * s, dist, height_pooling=False)
+        self.upBlock2 = UpBlock(8 * s, 4 * s, dist, height_pooling=True)
+        self.upBlock3 = UpBlock(4 * s, 2 * s, dist, height_pooling=True)
+        self.ReconNet = ReconBlock(2 * s, 2 * s, dist)
+        self.logits = _conv(4 * s, num_class, 3, bias=True)
+        if point_refinement:
+            self.change_dim = nn.Sequential(nn.Linear(4 * s, 256), norm(256), nn.LeakyReLU())
+            self.point_logits = nn.Linear(256, num_class)
+        self.criterion = SegLoss(ignore_index=ignore_label, label_smoothing=label_smoothing)          # CE + Lovasz on the voxels
+        self.loss_funs = nn.CrossEntropyLoss(ignore_index=ignore_label, label_smoothing=label_smoothing)  # the point term
+        # num_batches_tracked of all BatchNorm layers: one _foreach_add_ per training step
+        self._bn_layers = [m for m in self.modules() if isinstance(m, FusedBatchNorm)]
+        for m in self._bn_layers:
+            m.counted_by_parent = True
+
+    def _point_mlp(self, x):
+        pp = self.PPmodel
+        h = _dense_bn(pp[0], x)
+        for i in (1, 4, 7):
+            h = _dense_bn(pp[i + 1], _linear(pp[i], h), relu=True)
+        return _linear(pp[10], h)
+
+    def _refine_rows(self, batch, up0e, voxel_hash):
+        """The row of the voxel features every point receives in the point refinement, as cylinder_ts.py:539-542 takes it: the
+        position of the point's voxel in `voxel_coord`, used as a row of the output tensor. The two orders differ (the dataset's
+        quantisation order against the sorted hashes), so a point reads the features of ANOTHER voxel, possibly of another frame
+        of the batch; the fixtures and the reference's checkpoints were made with exactly this pairing, and it is kept."""
+        return F.sphashquery(F.sphash(batch["point_coord"].int()), voxel_hash)
+
+    def forward(self, batch):
+        """batch: the dict of the reference's collate_batch (point_feature (N, in_dim), point_coord (N, 4), voxel_coord (M, 4),
+        voxel_label (M,), point_label (N,), offset) -> {"logits": voxel logits in the output tensor's row order, "logit_coords",
+        "point_logits", and in train mode "loss"}."""
+        if self.training and self._bn_layers:
+            torch._foreach_add_([m.num_batches_tracked for m in self._bn_layers], 1)
+        point_feature = self._point_mlp(batch["point_feature"])
+        ret = voxelize(point_feature, batch["point_coord"].float())
+        ret.F = torch.relu(_linear(self.fea_compression[0], ret.F))
+        ret = self.downCntx(ret)
+        down1c, down1b = self.resBlock2(ret)
+        down2c, down2b = self.resBlock3(down1c)
+        down3c, down3b = self.resBlock4(down2c)
+        down4c, down4b = self.resBlock5(down3c)
+        up4e = self.upBlock0(down4c, down4b)
+        up3e = self.upBlock1(up4e, down3b)
+        up2e = self.upBlock2(up3e, down2b)
+        up1e = self.upBlock3(up2e, down1b)
+        up0e = self.ReconNet(up1e)
+        up0e.F = torch.cat((up0e.F, up1e.F.to(up0e.F.dtype)), 1)
+        logits = self.logits(up0e).F
+        out = {"logits": logits, "logit_coords": up0e.C}
+        voxel_hash = None
+        if self.point_refinement:
+            voxel_hash = F.sphash(batch["voxel_coord"].int())
+            from_voxel = up0e.F[self._refine_rows(batch, up0e, voxel_hash)]
+            cd = self.change_dim
+            from_voxel = torch.nn.functional.leaky_relu(_dense_bn(cd[1], _linear(cd[0], from_voxel)), cd[2].negative_slope)
+            out["point_logits"] = _linear(self.point_logits, point_feature + from_voxel.to(point_feature.dtype))
+        if self.training:
+            if voxel_hash is None:
+                voxel_hash = F.sphash(batch["voxel_coord"].int())
+            target = batch["voxel_label"][F.sphashquery(F.sphash(up0e.C), voxel_hash)]
+            loss = self.criterion(logits.float(), target.long())
+            if self.point_refinement:
+                loss = loss + self.loss_funs(out["point_logits"].float(), batch["point_label"].long())
+            out["loss"] = loss
+        return out
+
+    def predict(self, batch, evaluator=None):
+        """Evaluation forward + the voxel -> point mapping of cylinder_ts.py:572-586 for the whole batch at once: the batch index is
+        part of the hash, so ONE query of the points against the logits' coordinates gives every point its row, and the arg-max of
+        that row is taken by the prediction tail kernel (no per-frame host loop, no gathered (N, C) tensor). ->
+        {"logits", "logit_coords", "point_predict": flat int64 device tensor, frame after frame, each cut to batch["num_points"]
+        where given, "point_offset": its host offsets}. evaluator: a SegEvaluator that also counts batch["point_label"]."""
+        if self.training:
+            raise RuntimeError("CylinderTS.predict is an evaluation pass: call model.eval() first")
+        with torch.inference_mode():
+            out = self.forward(batch)
+            logits = out["logits"].float().contiguous()
+            pc = batch["point_coord"]
+            rows = F.sphashquery(F.sphash(pc.int()), F.sphash(out["logit_coords"]))
+            labels = batch["point_label"].long() if (evaluator is not None and batch.get("point_label") is not None) else None
+            frame = pc[:, -1].long()
+            num_points = batch.get("num_points")
+            if num_points is not None:
+                num_points = [int(v) for v in np.asarray(num_points.cpu() if isinstance(num_points, torch.Tensor) else num_points).reshape(-1)]
+                counts = torch.bincount(frame, minlength=len(num_points))
+                if sum(num_points) != pc.shape[0]:   # `[:num_points[idx]]`: a frame keeps the head of its points
+                    start = torch.cumsum(counts, 0) - counts
+                    keep = (torch.arange(pc.shape[0], device=pc.device) - start[frame]) < torch.tensor(num_points, device=pc.device)[frame]
+                    rows = rows[keep]
+                    labels = labels[keep] if labels is not None else None
+                offsets = [0] + np.cumsum(num_points).tolist()
+            else:
+                offsets = [0] + torch.cumsum(torch.bincount(frame), 0).cpu().tolist()   # the one read-back of a batch without num_points
+            be = native.backend()
+            if logits.is_cuda and hasattr(be, "predict_points"):
+                hist = bad = None
+                if labels is not None:
+                    evaluator._ensure(logits.device)
+                    hist, bad = evaluator.hist, evaluator.bad
+                pred, _ = be.predict_points(logits, inverse=rows.contiguous(), labels=labels if hist is not None else None, hist=hist, bad=bad)
+            else:
+                pred = logits[rows].argmax(1)
+            if evaluator is not None:
+                evaluator.last_offsets = offsets
+        return {"logits": logits, "logit_coords": out["logit_coords"], "point_predict": pred, "point_offset": offsets}
+
+
+def cylinder_batch(samples):
+    """collate_batch of the reference's cylinder dataset (R:pcseg/data/dataset/semantickitti/semantickitti_cylinder.py:176-213)
+    over the dicts `openpcseg_amd.cylinder.cylinder_sample` returns: the frame index becomes the last coordinate column."""
+    def with_frame(key):
+        return torch.cat([torch.cat([s[key], torch.full((s[key].shape[0], 1), i, dtype=s[key].dtype, device=s[key].device)], 1)
+                          for i, s in enumerate(samples)])
+    batch = {"point_feature": torch.cat([s["point_feature"] for s in samples]), "point_coord": with_frame("point_coord"),
+             "voxel_coord": with_frame("voxel_coord"), "voxel_label": torch.cat([s["voxel_label"] for s in samples]),
+             "point_label": torch.cat([s["point_label"] for s in samples]),
+             "offset": torch.cumsum(torch.tensor([s["voxel_coord"].shape[0] for s in samples]), 0).int(),
+             "num_points": np.array([int(s["point_feature"].shape[0]) for s in samples])}
+    if all("inverse_map" in s for s in samples):
+        batch["inverse_map"] = torch.cat([s["inverse_map"] for s in samples])
+    return batch
