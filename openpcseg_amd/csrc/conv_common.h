@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "pcs_common.h"
+#include "row_storage.h"
 
 // debug-build switches (tools/conv_ablation.sh, tools/conv_trace.py through PCS_LIB_PATH); all 0 in the product
 #ifndef PCS_TRACE
@@ -49,22 +50,8 @@ struct ConvArgs {
   float act_slope = 1.f;  // LeakyReLU in the write-back: v < 0 -> v * act_slope (1 = none), before the store and the statistics
 };
 
-// storage-format tags of the half-precision kernels (features / prepared weights / outputs)
-struct Bf16 {};
-struct Fp16 {};
-struct Fp32 {};
-__device__ __forceinline__ float h2f(Bf16, uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ float h2f(Fp16, uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t f2h(Bf16, float f) {  // round to nearest even; NaN stays NaN
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ uint16_t f2h(Fp16, float f) {
-  const _Float16 h = (_Float16)f;
-  return __builtin_bit_cast(uint16_t, h);
-}
+// the storage-format tags Bf16 / Fp16 / Fp32 of the half-precision kernels (features / prepared weights / outputs) and
+// h2f / f2h: row_storage.h
 
 constexpr size_t kMaxDynLds = 160 * 1024 - 256;  // per-workgroup LDS ceiling of a gfx950 CU, minus the static part
 

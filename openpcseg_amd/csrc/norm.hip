@@ -5,63 +5,30 @@
 // single write); backward = one reduction pass + one apply pass producing dx and (optionally) the residual grad.
 // Statistics are two-level (per-workgroup partials, then a fixed-order reduction): deterministic, and the
 // (sum, sumsq) vector is what a multi-GPU run all-reduces between the two kernels (SyncBN semantics).
-#include <type_traits>
-
-#include "pcs_common.h"
+#include "row_storage.h"
 
 using namespace pcs;
 
 namespace {
 
-constexpr int kStatBlocks = 1024;  // partial rows; each workgroup strides over the feature rows
-
 // storage format of the feature tensors (x, residual, y, dy, dx, dres): fp32, or bf16 / fp16 under mixed precision
-// (statistics, scale / shift and all arithmetic stay fp32 / double)
-struct F32 {};
-struct B16 {};
-struct H16 {};
-__device__ __forceinline__ float h2f(B16, uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ float h2f(H16, uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t f2h(B16, float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ uint16_t f2h(H16, float f) { const _Float16 h = (_Float16)f; return __builtin_bit_cast(uint16_t, h); }
-// element `e` (a multiple of V) of a tensor -> V floats; and back
-template <int V> __device__ __forceinline__ typename std::conditional<V == 4, float4, float>::type ldv(F32, const void *p, int64_t e) {
-  return *reinterpret_cast<const typename std::conditional<V == 4, float4, float>::type *>(reinterpret_cast<const float *>(p) + e);
-}
-template <int V, typename HT> __device__ __forceinline__ typename std::conditional<V == 4, float4, float>::type ldv(HT, const void *p, int64_t e) {
-  const uint16_t *h = reinterpret_cast<const uint16_t *>(p) + e;
-  if constexpr (V == 4) {
-    const uint2 r = *reinterpret_cast<const uint2 *>(h);
-    return make_float4(h2f(HT{}, (uint16_t)(r.x & 0xFFFFu)), h2f(HT{}, (uint16_t)(r.x >> 16)),
-                       h2f(HT{}, (uint16_t)(r.y & 0xFFFFu)), h2f(HT{}, (uint16_t)(r.y >> 16)));
-  } else {
-    return h2f(HT{}, h[0]);
-  }
-}
-__device__ __forceinline__ void stv(F32, void *p, int64_t e, const float4 &v) { *reinterpret_cast<float4 *>(reinterpret_cast<float *>(p) + e) = v; }
-__device__ __forceinline__ void stv(F32, void *p, int64_t e, const float &v) { reinterpret_cast<float *>(p)[e] = v; }
-template <typename HT> __device__ __forceinline__ void stv(HT, void *p, int64_t e, const float4 &v) {
-  uint2 o;
-  o.x = f2h(HT{}, v.x) | ((uint32_t)f2h(HT{}, v.y) << 16);
-  o.y = f2h(HT{}, v.z) | ((uint32_t)f2h(HT{}, v.w) << 16);
-  *reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(p) + e) = o;
-}
-template <typename HT> __device__ __forceinline__ void stv(HT, void *p, int64_t e, const float &v) {
-  reinterpret_cast<uint16_t *>(p)[e] = f2h(HT{}, v);
-}
-
-// the value a store leaves in memory, read back: what a later `y > 0` sees (fp16 rounds (0, 2^-25] to 0)
-__device__ __forceinline__ float stored(F32, float f) { return f; }
-template <typename HT> __device__ __forceinline__ float stored(HT, float f) { return h2f(HT{}, f2h(HT{}, f)); }
-
+// (row_storage.h; statistics, scale / shift and all arithmetic stay fp32 / double)
+// element `e` (a multiple of V) of a tensor -> V floats; and back (the kernels below work on float4 / float values)
 template <int V> struct NV;
 template <> struct NV<4> { using T = float4; };
 template <> struct NV<1> { using T = float; };
+template <int V, typename ET> __device__ __forceinline__ typename NV<V>::T ldv(ET, const void *p, int64_t e) {
+  const Acc<V> a = widen(ET{}, *reinterpret_cast<const typename Raw<ET, V>::T *>(reinterpret_cast<const typename Elem<ET>::T *>(p) + e));
+  if constexpr (V == 4) return make_float4(a.f[0], a.f[1], a.f[2], a.f[3]);
+  else return a.f[0];
+}
+template <typename ET> __device__ __forceinline__ void stv(ET, void *p, int64_t e, const float4 &v) {
+  *reinterpret_cast<typename Raw<ET, 4>::T *>(reinterpret_cast<typename Elem<ET>::T *>(p) + e) = narrow(ET{}, Acc<4>{{v.x, v.y, v.z, v.w}});
+}
+template <typename ET> __device__ __forceinline__ void stv(ET, void *p, int64_t e, const float &v) {
+  reinterpret_cast<typename Elem<ET>::T *>(p)[e] = narrow(ET{}, Acc<1>{{v}});
+}
+
 __device__ __forceinline__ float comp(const float4 &v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
 __device__ __forceinline__ float comp(const float &v, int) { return v; }
 __device__ __forceinline__ void setc(float4 &v, int i, float s) { if (i == 0) v.x = s; else if (i == 1) v.y = s; else if (i == 2) v.z = s; else v.w = s; }
@@ -148,8 +115,6 @@ __global__ void __launch_bounds__(256) bn_partial_kernel(const void *__restrict_
 //   f32copy (2c floats): the sums again in fp32 -- backward: the weight / bias gradients in the parameters' dtype;
 //   stat (2c doubles):   bn_finalize_kernel's mean / invstd + running statistics with count = n -- the forward of a
 //                        single-process run, where nothing has to be all-reduced between the reduction and the finalize.
-constexpr int kRedCh = 4;       // channels per workgroup of bn_reduce_kernel
-constexpr int kRedLanes = 256;  // row lanes per workgroup
 template <typename PT>
 __global__ void __launch_bounds__(1024) bn_reduce_kernel(const PT *__restrict__ partial, int nblk, int c,
                                                          const float *__restrict__ pivot, int64_t n,
@@ -342,33 +307,17 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const void *__restric
   }
 }
 
-struct Geo { dim3 block, grid; int cv; };
-template <int V> Geo geo(int64_t n, int c) {
-  Geo g; g.cv = c / V;
-  // one x-lane per channel vector up to 64 (NOT rounded to a power of two: 96 channels = 24 vectors would idle 8 of 32
-  // lanes on the two widest levels); rows of a workgroup are contiguous in memory either way. The ReLU-mask shuffles of
-  // bn_apply_kernel work on aligned groups of 8 lanes: c % 32 == 0 there, so cv % 8 == 0 and the groups stay aligned.
-  const int tx = g.cv < 64 ? (g.cv > 0 ? g.cv : 1) : 64;
-  g.block = dim3(tx, 256 / tx);
-  int64_t gr = ceil_div(n > 0 ? n : 1, (256 / tx) * 4);
-  if (gr > 2048) gr = 2048;
-  g.grid = dim3((unsigned)gr);
-  return g;
-}
+// kRowsExact4: one x-lane per channel vector up to 64 (NOT rounded to a power of two: 96 channels = 24 vectors would idle 8 of
+// 32 lanes on the two widest levels); rows of a workgroup are contiguous in memory either way. The ReLU-mask shuffles of
+// bn_apply_kernel work on aligned groups of 8 lanes: c % 32 == 0 there, so cv % 8 == 0 and the groups stay aligned.
+template <int V> RowLaunch geo(int64_t n, int c) { return row_launch(n, c / V, kRowsExact4); }
 
 }  // namespace
 
 extern "C" int32_t pcs_bn_num_partials(void) { return kStatBlocks + 1; }  // + the widened pivot row
 
-// dtype of the feature tensors: 0 fp32, 1 bf16, 2 fp16. alignment unit of a V = 4 access: 16 B (fp32) / 8 B (halfs)
-#define PCS_BN_DISPATCH(DT, CALL)                         \
-  do {                                                    \
-    if ((DT) == 0) { using ET = F32; CALL; }              \
-    else if ((DT) == 1) { using ET = B16; CALL; }         \
-    else { using ET = H16; CALL; }                        \
-  } while (0)
-
-static bool al_v4(int dtype, const void *p) { return ((uintptr_t)p & (dtype == 0 ? 15 : 7)) == 0; }
+// alignment unit of a V = 4 access: 16 B (fp32) / 8 B (halfs)
+static bool al_v4(int dtype, const void *p) { return aligned(p, dtype == 0 ? 16 : 8); }
 
 static int bn_partial(bool bwd, int dtype, const void *x, const void *dy, const void *y, const uint32_t *mask, const double *stat,
                       int64_t n, int c, int relu, float *partial, double *sums, hipStream_t st, int64_t lddy = 0) {
@@ -377,17 +326,16 @@ static int bn_partial(bool bwd, int dtype, const void *x, const void *dy, const 
   const bool vec = (c & 3) == 0 && (lddy & 3) == 0 && al_v4(dtype, x) && al_v4(dtype, dy) && al_v4(dtype, y);
   if (mask && (!vec || (c & 31))) { set_error("pcs_bn: the ReLU bit mask needs c % 32 == 0 and aligned rows"); return PCS_EUNSUPPORTED; }
   const int V = vec ? 4 : 1, cv = c / V;
-  const int tx = cv < 64 ? cv : 64;   // as geo(): one x-lane per channel vector, no power-of-two rounding
-  dim3 block(tx, 256 / tx);
-  const size_t lds = (size_t)(256 / tx) * 2 * tx * V * sizeof(float);
+  const dim3 block = row_launch(n, cv, kRowsExact4).block;   // one x-lane per channel vector, no power-of-two rounding
+  const size_t lds = (size_t)block.y * 2 * block.x * V * sizeof(float);
   if (vec) {
-    if (bwd) PCS_BN_DISPATCH(dtype, hipLaunchKernelGGL((bn_partial_kernel<true, 4, ET>), dim3(kStatBlocks), block, lds, st, x, dy, y, mask, stat, n, c, cv, relu, partial, lddy));
-    else PCS_BN_DISPATCH(dtype, hipLaunchKernelGGL((bn_partial_kernel<false, 4, ET>), dim3(kStatBlocks), block, lds, st, x, dy, y, mask, stat, n, c, cv, relu, partial, lddy));
+    if (bwd) PCS_DTYPE(dtype, hipLaunchKernelGGL((bn_partial_kernel<true, 4, ET>), dim3(kStatBlocks), block, lds, st, x, dy, y, mask, stat, n, c, cv, relu, partial, lddy));
+    else PCS_DTYPE(dtype, hipLaunchKernelGGL((bn_partial_kernel<false, 4, ET>), dim3(kStatBlocks), block, lds, st, x, dy, y, mask, stat, n, c, cv, relu, partial, lddy));
   } else {
-    if (bwd) PCS_BN_DISPATCH(dtype, hipLaunchKernelGGL((bn_partial_kernel<true, 1, ET>), dim3(kStatBlocks), block, lds, st, x, dy, y, mask, stat, n, c, cv, relu, partial, lddy));
-    else PCS_BN_DISPATCH(dtype, hipLaunchKernelGGL((bn_partial_kernel<false, 1, ET>), dim3(kStatBlocks), block, lds, st, x, dy, y, mask, stat, n, c, cv, relu, partial, lddy));
+    if (bwd) PCS_DTYPE(dtype, hipLaunchKernelGGL((bn_partial_kernel<true, 1, ET>), dim3(kStatBlocks), block, lds, st, x, dy, y, mask, stat, n, c, cv, relu, partial, lddy));
+    else PCS_DTYPE(dtype, hipLaunchKernelGGL((bn_partial_kernel<false, 1, ET>), dim3(kStatBlocks), block, lds, st, x, dy, y, mask, stat, n, c, cv, relu, partial, lddy));
   }
-    const float *pivot = bwd ? nullptr : partial + (size_t)kStatBlocks * 2 * c;  // written by workgroup 0 above
+  const float *pivot = bwd ? nullptr : partial + (size_t)kStatBlocks * 2 * c;  // written by workgroup 0 above
   // backward: the sums once more in fp32 behind the 2c doubles (the parameter gradients, no conversion launch)
   hipLaunchKernelGGL(bn_reduce_kernel<float>, dim3((unsigned)ceil_div(c, kRedCh)), dim3(kRedCh, kRedLanes), 0, st, partial, kStatBlocks, c,
                      pivot, n, sums, bwd ? 0 : 1, bwd ? reinterpret_cast<float *>(sums + 2 * (size_t)c) : (float *)nullptr,
@@ -408,11 +356,11 @@ static int bn_apply_any(int dtype, const void *x, const void *res, const double 
                    al_v4(dtype, tail);
   if (mask && (!vec || (c & 31))) { set_error("pcs_bn_apply: the ReLU bit mask needs c % 32 == 0 and aligned rows"); return PCS_EUNSUPPORTED; }
   if (vec) {
-    Geo g = geo<4>(n, c);
-    PCS_BN_DISPATCH(dtype, hipLaunchKernelGGL((bn_apply_kernel<4, ET>), g.grid, g.block, 0, st, x, res, stat, w, b, n, c, g.cv, relu, y, mask, ldy, tail, ctail));
+    const RowLaunch g = geo<4>(n, c);
+    PCS_DTYPE(dtype, hipLaunchKernelGGL((bn_apply_kernel<4, ET>), g.grid, g.block, 0, st, x, res, stat, w, b, n, c, g.cv, relu, y, mask, ldy, tail, ctail));
   } else {
-    Geo g = geo<1>(n, c);
-    PCS_BN_DISPATCH(dtype, hipLaunchKernelGGL((bn_apply_kernel<1, ET>), g.grid, g.block, 0, st, x, res, stat, w, b, n, c, g.cv, relu, y, mask, ldy, tail, ctail));
+    const RowLaunch g = geo<1>(n, c);
+    PCS_DTYPE(dtype, hipLaunchKernelGGL((bn_apply_kernel<1, ET>), g.grid, g.block, 0, st, x, res, stat, w, b, n, c, g.cv, relu, y, mask, ldy, tail, ctail));
   }
   return check_launch("pcs_bn_apply");
 }
@@ -431,16 +379,14 @@ static int bn_bwd_apply_any(int dtype, const void *dy, const void *x, const void
   const bool vec = (c & 3) == 0 && (lddy & 3) == 0 && al_v4(dtype, dy) && al_v4(dtype, x) && al_v4(dtype, y) && al_v4(dtype, dx) && al_v4(dtype, dres);
   if (mask && (!vec || (c & 31))) { set_error("pcs_bn_bwd_apply: the ReLU bit mask needs c % 32 == 0 and aligned rows"); return PCS_EUNSUPPORTED; }
   if (vec) {
-    Geo g = geo<4>(n, c);
-    PCS_BN_DISPATCH(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<4, ET>), g.grid, g.block, 0, st, dy, x, y, mask, stat, sums2, count, count_dev, w, n, c, g.cv, relu, dx, dres, lddy, in_slope));
+    const RowLaunch g = geo<4>(n, c);
+    PCS_DTYPE(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<4, ET>), g.grid, g.block, 0, st, dy, x, y, mask, stat, sums2, count, count_dev, w, n, c, g.cv, relu, dx, dres, lddy, in_slope));
   } else {
-    Geo g = geo<1>(n, c);
-    PCS_BN_DISPATCH(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<1, ET>), g.grid, g.block, 0, st, dy, x, y, mask, stat, sums2, count, count_dev, w, n, c, g.cv, relu, dx, dres, lddy, in_slope));
+    const RowLaunch g = geo<1>(n, c);
+    PCS_DTYPE(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<1, ET>), g.grid, g.block, 0, st, dy, x, y, mask, stat, sums2, count, count_dev, w, n, c, g.cv, relu, dx, dres, lddy, in_slope));
   }
   return check_launch("pcs_bn_bwd_apply");
 }
-
-static bool bad_half(int32_t dtype) { return dtype != 1 && dtype != 2; }
 
 // n == 0 (a rank with an empty shard under SyncBN): the tensors may be NULL, the sums are zero with count 0
 extern "C" int pcs_bn_stats_f32(const float *x, int64_t n, int32_t c, float *partial_ws, double *sums, void *stream) {
@@ -448,7 +394,7 @@ extern "C" int pcs_bn_stats_f32(const float *x, int64_t n, int32_t c, float *par
   return bn_partial(false, 0, x, nullptr, nullptr, nullptr, nullptr, n, c, 0, partial_ws, sums, as_stream(stream));
 }
 extern "C" int pcs_bn_stats_h(const void *x, int64_t n, int32_t c, int32_t dtype, float *partial_ws, double *sums, void *stream) {
-  if (n < 0 || c <= 0 || (n > 0 && !x) || !partial_ws || !sums || bad_half(dtype)) { set_error("pcs_bn_stats_h: bad args"); return PCS_EINVAL; }
+  if (n < 0 || c <= 0 || (n > 0 && !x) || !partial_ws || !sums || !is_half(dtype)) { set_error("pcs_bn_stats_h: bad args"); return PCS_EINVAL; }
   return bn_partial(false, dtype, x, nullptr, nullptr, nullptr, nullptr, n, c, 0, partial_ws, sums, as_stream(stream));
 }
 
@@ -493,7 +439,7 @@ extern "C" int pcs_bn_apply_f32(const float *x, const float *res, const double *
 extern "C" int pcs_bn_apply_h(const void *x, const void *res, const double *stat, const float *w, const float *b,
                               int64_t n, int32_t c, int32_t relu, int32_t dtype, void *y, uint32_t *mask, int64_t ldy,
                               const void *tail, int32_t ctail, void *stream) {
-  if (bad_half(dtype)) { set_error("pcs_bn_apply_h: dtype must be 1 (bf16) or 2 (fp16)"); return PCS_EINVAL; }
+  if (bad_half("pcs_bn_apply_h", dtype, false)) return PCS_EINVAL;
   return bn_apply_any(dtype, x, res, stat, w, b, n, c, relu, y, mask, ldy, tail, ctail, stream);
 }
 
@@ -507,7 +453,7 @@ extern "C" int pcs_bn_bwd_stats_f32(const float *dy, const float *x, const float
 extern "C" int pcs_bn_bwd_stats_h(const void *dy, const void *x, const void *y, const uint32_t *mask,
                                   const double *stat, int64_t n, int32_t c, int32_t relu, int32_t dtype, float *partial_ws,
                                   double *sums2, int64_t sums2_doubles, int64_t lddy, void *stream) {
-  if (n < 0 || c <= 0 || (n > 0 && (!dy || !x || (relu && !y && !mask))) || !stat || !partial_ws || !sums2 || bad_half(dtype)) { set_error("pcs_bn_bwd_stats_h: bad args"); return PCS_EINVAL; }
+  if (n < 0 || c <= 0 || (n > 0 && (!dy || !x || (relu && !y && !mask))) || !stat || !partial_ws || !sums2 || !is_half(dtype)) { set_error("pcs_bn_bwd_stats_h: bad args"); return PCS_EINVAL; }
   if (sums2_doubles < 3 * (int64_t)c) { set_error("pcs_bn_bwd_stats_h: sums2 must hold 3c doubles (2c sums + the same 2c values as floats)"); return PCS_EWORKSPACE; }
   return bn_partial(true, dtype, x, dy, y, mask, stat, n, c, relu, partial_ws, sums2, as_stream(stream), lddy);
 }
@@ -531,6 +477,6 @@ extern "C" int pcs_bn_bwd_apply_h(const void *dy, const void *x, const void *y, 
                                   const double *stat, const double *sums2, double count, const double *count_dev,
                                   const float *w, int64_t n, int32_t c, int32_t relu, int32_t dtype, void *dx, void *dres,
                                   int64_t lddy, void *stream) {
-  if (bad_half(dtype)) { set_error("pcs_bn_bwd_apply_h: dtype must be 1 (bf16) or 2 (fp16)"); return PCS_EINVAL; }
+  if (bad_half("pcs_bn_bwd_apply_h", dtype, false)) return PCS_EINVAL;
   return bn_bwd_apply_any(dtype, dy, x, y, mask, stat, sums2, count, count_dev, w, n, c, relu, dx, dres, lddy, stream);
 }

@@ -11,61 +11,11 @@
 // Launch shape of the K9 kernels: a 256-thread workgroup covers 256/TX points, TX lanes x 16 bytes per row, grid-stride
 // over the points; the corner indices and weights of a point are loaded once per pass of the lane row (one pass up to
 // c = 256 in fp32, 512 in 16 bits). No LDS, no atomics; every output row and mask word is written exactly once.
-#include "pcs_common.h"
+#include "row_storage.h"
 
 using namespace pcs;
 
 namespace {
-
-struct F32 {};
-struct B16 {};
-struct H16 {};
-__device__ __forceinline__ float h2f(B16, uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ float h2f(H16, uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t f2h(B16, float f) {  // round to nearest even; NaN stays NaN
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ uint16_t f2h(H16, float f) { const _Float16 h = (_Float16)f; return __builtin_bit_cast(uint16_t, h); }
-
-// bn(x) as pcs_bn_apply_* would store it, read back: the ReLU gate of the mask is that of the stored value
-__device__ __forceinline__ float stored(F32, float f) { return f; }
-template <typename HT> __device__ __forceinline__ float stored(HT, float f) { return h2f(HT{}, f2h(HT{}, f)); }
-
-// one 16-byte piece of a row: 4 floats or 8 halfs, widened to fp32 registers
-template <typename ET> struct Piece;
-template <> struct Piece<F32> { static constexpr int V = 4; };
-template <> struct Piece<B16> { static constexpr int V = 8; };
-template <> struct Piece<H16> { static constexpr int V = 8; };
-
-template <int V> struct Acc { float f[V]; };
-
-__device__ __forceinline__ Acc<4> widen(F32, const uint4 &r) {
-  Acc<4> a;
-  a.f[0] = __uint_as_float(r.x); a.f[1] = __uint_as_float(r.y); a.f[2] = __uint_as_float(r.z); a.f[3] = __uint_as_float(r.w);
-  return a;
-}
-template <typename HT> __device__ __forceinline__ Acc<8> widen(HT, const uint4 &r) {
-  Acc<8> a;
-  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    a.f[2 * q] = h2f(HT{}, (uint16_t)(w[q] & 0xFFFFu));
-    a.f[2 * q + 1] = h2f(HT{}, (uint16_t)(w[q] >> 16));
-  }
-  return a;
-}
-__device__ __forceinline__ uint4 narrow(F32, const Acc<4> &a) {
-  return make_uint4(__float_as_uint(a.f[0]), __float_as_uint(a.f[1]), __float_as_uint(a.f[2]), __float_as_uint(a.f[3]));
-}
-template <typename HT> __device__ __forceinline__ uint4 narrow(HT, const Acc<8> &a) {  // the one rounding of an output element
-  uint32_t w[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) w[q] = (uint32_t)f2h(HT{}, a.f[2 * q]) | ((uint32_t)f2h(HT{}, a.f[2 * q + 1]) << 16);
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 // rows are addressed in 16-byte pieces: piece j of row r of a (rows, c) tensor sits at uint4 index r * cv + j
 template <typename ET>
@@ -122,8 +72,6 @@ __global__ void __launch_bounds__(256) point_merge_kernel(const uint4 *__restric
   }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 // dtype 0 fp32, 1 bf16, 2 fp16
 int point_merge_any(const char *what, int dtype, const void *vox, const int32_t *idx8, const float *w8, const void *lin,
                     const double *stat, const float *gamma, const float *beta, int64_t n, int32_t c, void *out,
@@ -132,7 +80,7 @@ int point_merge_any(const char *what, int dtype, const void *vox, const int32_t 
   if (c & 31) { set_error("%s: c = %d is not a multiple of 32 (the ReLU bit mask is made of whole words)", what, (int)c); return PCS_EUNSUPPORTED; }
   if (n == 0) return PCS_OK;
   if (!idx8 || !w8 || !lin || !stat || !out || !mask) { set_error("%s: null pointer", what); return PCS_EINVAL; }
-  if (!aligned16(vox) || !aligned16(lin) || !aligned16(out)) {
+  if (!aligned(vox, 16) || !aligned(lin, 16) || !aligned(out, 16)) {
     set_error("%s: vox, lin and out rows must be 16-byte aligned", what);
     return PCS_EUNSUPPORTED;
   }
@@ -140,19 +88,10 @@ int point_merge_any(const char *what, int dtype, const void *vox, const int32_t 
     set_error("%s: misaligned mask / idx8 / w8 / stat", what);
     return PCS_EINVAL;
   }
-  const int cv = c / (dtype == 0 ? 4 : 8);
-  int tx = 1;
-  while (tx < cv && tx < 64) tx <<= 1;   // >= 4: c >= 32
-  const int ty = 256 / tx;
-  int64_t g = ceil_div(n, ty);
-  if (g > 256 * 16) g = 256 * 16;
-  const dim3 grid((unsigned)g), block(tx, ty);
-  hipStream_t st = as_stream(stream);
-  const uint4 *v = reinterpret_cast<const uint4 *>(vox), *l = reinterpret_cast<const uint4 *>(lin);
-  uint4 *o = reinterpret_cast<uint4 *>(out);
-  if (dtype == 0) hipLaunchKernelGGL(point_merge_kernel<F32>, grid, block, 0, st, v, idx8, w8, l, stat, gamma, beta, n, c, cv, o, mask);
-  else if (dtype == 1) hipLaunchKernelGGL(point_merge_kernel<B16>, grid, block, 0, st, v, idx8, w8, l, stat, gamma, beta, n, c, cv, o, mask);
-  else hipLaunchKernelGGL(point_merge_kernel<H16>, grid, block, 0, st, v, idx8, w8, l, stat, gamma, beta, n, c, cv, o, mask);
+  const RowLaunch rl = row_launch(n, c / (dtype == 0 ? 4 : 8), kRowsPow2);   // TX >= 4: c >= 32
+  PCS_DTYPE(dtype, hipLaunchKernelGGL(point_merge_kernel<ET>, rl.grid, rl.block, 0, as_stream(stream), reinterpret_cast<const uint4 *>(vox),
+                                      idx8, w8, reinterpret_cast<const uint4 *>(lin), stat, gamma, beta, n, c, rl.cv,
+                                      reinterpret_cast<uint4 *>(out), mask));
   return check_launch(what);
 }
 
@@ -167,6 +106,6 @@ extern "C" int pcs_point_merge_f32(const float *vox, const int32_t *idx8, const 
 extern "C" int pcs_point_merge_h(const void *vox, const int32_t *idx8, const float *w8, const void *lin, const double *stat,
                                  const float *gamma, const float *beta, int64_t n, int32_t c, int32_t dtype, void *out,
                                  uint32_t *mask, void *stream) {
-  if (dtype != 1 && dtype != 2) { set_error("pcs_point_merge_h: dtype must be 1 (bf16) or 2 (fp16), got %d", (int)dtype); return PCS_EINVAL; }
+  if (bad_half("pcs_point_merge_h", dtype)) return PCS_EINVAL;
   return point_merge_any("pcs_point_merge_h", dtype, vox, idx8, w8, lin, stat, gamma, beta, n, c, out, mask, stream);
 }

@@ -14,59 +14,11 @@
 // and the statistics are two-level with a fixed order (per-workgroup partial rows, then a double reduction), so results
 // are deterministic. The 6c-double vector of the statistics is what a data-parallel run all-reduces: one collective for
 // the whole block.
-#include "pcs_common.h"
+#include "row_storage.h"
 
 using namespace pcs;
 
 namespace {
-
-constexpr int kStatBlocks = 1024;  // partial rows of the backward statistics (pcs_bn_num_partials() - 1)
-
-struct F32 {};
-struct B16 {};
-struct H16 {};
-__device__ __forceinline__ float h2f(B16, uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ float h2f(H16, uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t f2h(B16, float f) {  // round to nearest even; NaN stays NaN
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ uint16_t f2h(H16, float f) { const _Float16 h = (_Float16)f; return __builtin_bit_cast(uint16_t, h); }
-
-// one 16-byte piece of a row: 4 floats or 8 halfs, widened to fp32 registers
-template <typename ET> struct Piece;
-template <> struct Piece<F32> { static constexpr int V = 4; };
-template <> struct Piece<B16> { static constexpr int V = 8; };
-template <> struct Piece<H16> { static constexpr int V = 8; };
-
-template <int V> struct Acc { float f[V]; };
-
-__device__ __forceinline__ Acc<4> widen(F32, const uint4 &r) {
-  Acc<4> a;
-  a.f[0] = __uint_as_float(r.x); a.f[1] = __uint_as_float(r.y); a.f[2] = __uint_as_float(r.z); a.f[3] = __uint_as_float(r.w);
-  return a;
-}
-template <typename HT> __device__ __forceinline__ Acc<8> widen(HT, const uint4 &r) {
-  Acc<8> a;
-  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    a.f[2 * q] = h2f(HT{}, (uint16_t)(w[q] & 0xFFFFu));
-    a.f[2 * q + 1] = h2f(HT{}, (uint16_t)(w[q] >> 16));
-  }
-  return a;
-}
-__device__ __forceinline__ uint4 narrow(F32, const Acc<4> &a) {
-  return make_uint4(__float_as_uint(a.f[0]), __float_as_uint(a.f[1]), __float_as_uint(a.f[2]), __float_as_uint(a.f[3]));
-}
-template <typename HT> __device__ __forceinline__ uint4 narrow(HT, const Acc<8> &a) {  // the one rounding of an output element
-  uint32_t w[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) w[q] = (uint32_t)f2h(HT{}, a.f[2 * q]) | ((uint32_t)f2h(HT{}, a.f[2 * q + 1]) << 16);
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 __device__ __forceinline__ float sigmoidf(float t) { return 1.f / (1.f + expf(-t)); }
 
@@ -184,9 +136,9 @@ __global__ void __launch_bounds__(256) recon_gate_partial_kernel(Branches b, con
 
 // sums[col] = sum over the nblk partial rows of partial[b][col], col < ncols = 6c, accumulated in double in the FIXED order of
 // bn_reduce_kernel (norm.hip): lane ty sums rows ty, ty + 256, ...; groups of 16 lanes in order; the 16 group sums in order.
-// f32copy: the same values as floats (the parameter gradients without a conversion launch).
-constexpr int kRedCh = 4;       // columns per workgroup
-constexpr int kRedLanes = 256;  // row lanes per workgroup
+// f32copy: the same values as floats (the parameter gradients without a conversion launch). A kernel of its own rather than a
+// launch of bn_reduce_kernel<float> over 2 x 3c columns (same bits): half the workgroups with twice the loads each took 5.9 us
+// against this kernel's 4.9 us per launch (profiles/row_storage_refactor.md), and the pass is pure latency.
 __global__ void __launch_bounds__(1024) recon_gate_reduce_kernel(const float *__restrict__ partial, int nblk, int ncols,
                                                                  double *__restrict__ sums, float *__restrict__ f32copy) {
   __shared__ double red[kRedLanes][kRedCh + 1];
@@ -270,21 +222,8 @@ __global__ void __launch_bounds__(256) recon_gate_bwd_apply_kernel(Branches b, c
   }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-struct Launch { dim3 grid, block; int cv; };
-// one x-lane per 16-byte piece up to 64 (not rounded to a power of two, as norm.hip's geo()); capped grid of 16 workgroups per CU
-Launch launch_shape(int dtype, int64_t n, int c) {
-  Launch l;
-  l.cv = c / (dtype == 0 ? 4 : 8);
-  const int tx = l.cv < 64 ? l.cv : 64;
-  const int ty = 256 / tx;
-  l.block = dim3(tx, ty);
-  int64_t g = ceil_div(n, ty);
-  if (g > 256 * 16) g = 256 * 16;
-  l.grid = dim3((unsigned)g);
-  return l;
-}
+// one x-lane per 16-byte piece up to 64 (not rounded to a power of two, as the BatchNorm passes); capped grid of 16 workgroups per CU
+RowLaunch launch_shape(int dtype, int64_t n, int c) { return row_launch(n, c / (dtype == 0 ? 4 : 8), kRowsExact); }
 
 // the checks every entry shares; PCS_OK with *go = false: nothing to do (n == 0)
 int recon_check(const char *what, int dtype, int64_t n, int32_t c, bool *go) {
@@ -297,13 +236,6 @@ int recon_check(const char *what, int dtype, int64_t n, int32_t c, bool *go) {
   *go = n > 0;
   return PCS_OK;
 }
-
-#define PCS_RG_DISPATCH(DT, KERNEL, ...)                                  \
-  do {                                                                    \
-    if ((DT) == 0) hipLaunchKernelGGL(KERNEL<F32>, __VA_ARGS__);          \
-    else if ((DT) == 1) hipLaunchKernelGGL(KERNEL<B16>, __VA_ARGS__);     \
-    else hipLaunchKernelGGL(KERNEL<H16>, __VA_ARGS__);                    \
-  } while (0)
 
 Branches branches(const void *a0, const void *a1, const void *a2, const double *stat3, const float *gamma3, const float *beta3) {
   Branches b;
@@ -318,14 +250,14 @@ int recon_gate_any(const char *what, int dtype, const void *a0, const void *a1, 
   const int rc = recon_check(what, dtype, n, c, &go);
   if (rc != PCS_OK || !go) return rc;
   if (!a0 || !a1 || !a2 || !x || !stat3 || !out) { set_error("%s: null pointer", what); return PCS_EINVAL; }
-  if (!aligned16(a0) || !aligned16(a1) || !aligned16(a2) || !aligned16(x) || !aligned16(out)) {
+  if (!aligned(a0, 16) || !aligned(a1, 16) || !aligned(a2, 16) || !aligned(x, 16) || !aligned(out, 16)) {
     set_error("%s: a0, a1, a2, x and out rows must be 16-byte aligned", what);
     return PCS_EUNSUPPORTED;
   }
   if (((uintptr_t)stat3 & 7) || ((uintptr_t)gamma3 & 3) || ((uintptr_t)beta3 & 3)) { set_error("%s: misaligned stat3 / gamma3 / beta3", what); return PCS_EINVAL; }
-  const Launch l = launch_shape(dtype, n, c);
-  PCS_RG_DISPATCH(dtype, recon_gate_kernel, l.grid, l.block, 0, as_stream(stream), branches(a0, a1, a2, stat3, gamma3, beta3),
-                  reinterpret_cast<const uint4 *>(x), n, c, l.cv, reinterpret_cast<uint4 *>(out));
+  const RowLaunch l = launch_shape(dtype, n, c);
+  PCS_DTYPE(dtype, hipLaunchKernelGGL(recon_gate_kernel<ET>, l.grid, l.block, 0, as_stream(stream), branches(a0, a1, a2, stat3, gamma3, beta3),
+                  reinterpret_cast<const uint4 *>(x), n, c, l.cv, reinterpret_cast<uint4 *>(out)));
   return check_launch(what);
 }
 
@@ -340,7 +272,7 @@ int recon_gate_bwd_stats_any(const char *what, int dtype, const void *dy, const 
     set_error("%s: sums2 must hold 9c doubles (3 x 2c sums + the same 6c values as floats)", what);
     return PCS_EWORKSPACE;
   }
-  if (!aligned16(dy) || !aligned16(x) || !aligned16(a0) || !aligned16(a1) || !aligned16(a2)) {
+  if (!aligned(dy, 16) || !aligned(x, 16) || !aligned(a0, 16) || !aligned(a1, 16) || !aligned(a2, 16)) {
     set_error("%s: dy, x, a0, a1 and a2 rows must be 16-byte aligned", what);
     return PCS_EUNSUPPORTED;
   }
@@ -348,12 +280,12 @@ int recon_gate_bwd_stats_any(const char *what, int dtype, const void *dy, const 
     set_error("%s: misaligned stat3 / sums2 / partial_ws / gamma3 / beta3", what);
     return PCS_EINVAL;
   }
-  const Launch l = launch_shape(dtype, n, c);
+  const RowLaunch l = launch_shape(dtype, n, c);
   const int V = dtype == 0 ? 4 : 8;
   const size_t lds = (size_t)l.block.y * 2 * l.block.x * V * sizeof(float);   // <= 256 * 2 * 8 * 4 = 16 KB
   hipStream_t st = as_stream(stream);
-  PCS_RG_DISPATCH(dtype, recon_gate_partial_kernel, dim3(kStatBlocks), l.block, lds, st, branches(a0, a1, a2, stat3, gamma3, beta3),
-                  reinterpret_cast<const uint4 *>(dy), reinterpret_cast<const uint4 *>(x), n, c, l.cv, partial_ws);
+  PCS_DTYPE(dtype, hipLaunchKernelGGL(recon_gate_partial_kernel<ET>, dim3(kStatBlocks), l.block, lds, st, branches(a0, a1, a2, stat3, gamma3, beta3),
+                  reinterpret_cast<const uint4 *>(dy), reinterpret_cast<const uint4 *>(x), n, c, l.cv, partial_ws));
   const int ncols = 6 * c;
   hipLaunchKernelGGL(recon_gate_reduce_kernel, dim3((unsigned)ceil_div(ncols, kRedCh)), dim3(kRedCh, kRedLanes), 0, st, partial_ws,
                      kStatBlocks, ncols, sums2, reinterpret_cast<float *>(sums2 + ncols));
@@ -369,8 +301,8 @@ int recon_gate_bwd_apply_any(const char *what, int dtype, const void *dy, const 
   if (rc != PCS_OK || !go) return rc;   // n == 0 before the count: an empty tensor has none
   if (!dy || !x || !a0 || !a1 || !a2 || !stat3 || !sums2 || !dx_gate || !da0 || !da1 || !da2) { set_error("%s: null pointer", what); return PCS_EINVAL; }
   if (!count_dev && !(count > 0)) { set_error("%s: count must be positive", what); return PCS_EINVAL; }
-  if (!aligned16(dy) || !aligned16(x) || !aligned16(a0) || !aligned16(a1) || !aligned16(a2) || !aligned16(dx_gate) ||
-      !aligned16(da0) || !aligned16(da1) || !aligned16(da2)) {
+  if (!aligned(dy, 16) || !aligned(x, 16) || !aligned(a0, 16) || !aligned(a1, 16) || !aligned(a2, 16) || !aligned(dx_gate, 16) ||
+      !aligned(da0, 16) || !aligned(da1, 16) || !aligned(da2, 16)) {
     set_error("%s: dy, x, a_k, dx_gate and da_k rows must be 16-byte aligned", what);
     return PCS_EUNSUPPORTED;
   }
@@ -378,19 +310,13 @@ int recon_gate_bwd_apply_any(const char *what, int dtype, const void *dy, const 
     set_error("%s: misaligned stat3 / sums2 / count_dev / gamma3 / beta3", what);
     return PCS_EINVAL;
   }
-  const Launch l = launch_shape(dtype, n, c);
+  const RowLaunch l = launch_shape(dtype, n, c);
   Grads o;
   o.dx = reinterpret_cast<uint4 *>(dx_gate);
   o.da[0] = reinterpret_cast<uint4 *>(da0); o.da[1] = reinterpret_cast<uint4 *>(da1); o.da[2] = reinterpret_cast<uint4 *>(da2);
-  PCS_RG_DISPATCH(dtype, recon_gate_bwd_apply_kernel, l.grid, l.block, 0, as_stream(stream), branches(a0, a1, a2, stat3, gamma3, beta3),
-                  reinterpret_cast<const uint4 *>(dy), reinterpret_cast<const uint4 *>(x), sums2, count, count_dev, n, c, l.cv, o);
+  PCS_DTYPE(dtype, hipLaunchKernelGGL(recon_gate_bwd_apply_kernel<ET>, l.grid, l.block, 0, as_stream(stream), branches(a0, a1, a2, stat3, gamma3, beta3),
+                  reinterpret_cast<const uint4 *>(dy), reinterpret_cast<const uint4 *>(x), sums2, count, count_dev, n, c, l.cv, o));
   return check_launch(what);
-}
-
-bool bad_half(const char *what, int32_t dtype) {
-  if (dtype == 1 || dtype == 2) return false;
-  set_error("%s: dtype must be 1 (bf16) or 2 (fp16), got %d", what, (int)dtype);
-  return true;
 }
 
 }  // namespace

@@ -4,23 +4,11 @@
 // All HBM-bound. scatter_max runs as a per-voxel segmented reduction over a sorted CSR (deterministic, no float
 // atomic-max tricks, argmax = first point in CSR order); the range scatter runs tiled over a CSR of the pixels
 // (full-line NCHW accesses, no atomics); the reference's atomic dataflow is kept for odd channel counts and A/B.
-#include "pcs_common.h"
+#include "row_storage.h"
 
 using namespace pcs;
 
 namespace {
-
-struct RowGrid { dim3 block, grid; };
-RowGrid row_grid(int64_t rows, int c) {
-  int tx = 1;
-  while (tx < c && tx < 64) tx <<= 1;
-  RowGrid r;
-  r.block = dim3(tx, 256 / tx);
-  int64_t g = ceil_div(rows > 0 ? rows : 1, 256 / tx);
-  if (g > 256 * 16) g = 256 * 16;
-  r.grid = dim3((unsigned)g);
-  return r;
-}
 
 // out[v, j] = max over the points of voxel v of src[i, j]; arg[v, j] = that point (first in CSR order on ties);
 // empty voxels: out = 0, arg = -1. V = 4: one lane owns 4 channels (16-byte loads, 16-byte stores of out and arg).
@@ -189,10 +177,10 @@ extern "C" int pcs_scatter_max_fwd_f32(const float *src, const int64_t *order, c
   if (m == 0) return PCS_OK;
   if (!src || !order || !rowptr || !out || !arg) { set_error("pcs_scatter_max_fwd: null pointer"); return PCS_EINVAL; }
   if ((c & 3) == 0 && (((uintptr_t)src | (uintptr_t)out | (uintptr_t)arg) & 15) == 0) {
-    RowGrid rg = row_grid(m, c / 4);
+    const RowLaunch rg = row_launch(m, c / 4, kRowsPow2);
     hipLaunchKernelGGL(scatter_max_csr_kernel<4>, rg.grid, rg.block, 0, as_stream(stream), src, order, rowptr, m, c, c / 4, out, arg);
   } else {
-    RowGrid rg = row_grid(m, c);
+    const RowLaunch rg = row_launch(m, c, kRowsPow2);
     hipLaunchKernelGGL(scatter_max_csr_kernel<1>, rg.grid, rg.block, 0, as_stream(stream), src, order, rowptr, m, c, c, out, arg);
   }
   return check_launch("pcs_scatter_max_fwd");
@@ -208,7 +196,7 @@ extern "C" int pcs_scatter_max_bwd_f32(const float *gout, const int32_t *arg, in
   }
   if (m == 0 || n == 0) return PCS_OK;
   if (!gout || !arg) { set_error("pcs_scatter_max_bwd: null pointer"); return PCS_EINVAL; }
-  RowGrid rg = row_grid(m, c);
+  const RowLaunch rg = row_launch(m, c, kRowsPow2);
   hipLaunchKernelGGL(scatter_max_bwd_kernel, rg.grid, rg.block, 0, st, gout, arg, m, c, gsrc);
   return check_launch("pcs_scatter_max_bwd");
 }
@@ -231,7 +219,7 @@ extern "C" int pcs_denselize_fwd_f32(const float *feat, const int32_t *count_map
   if (hipMemsetAsync(out, 0, (size_t)B * C * H * W * 4, st) != hipSuccess) { set_error("pcs_denselize_fwd: memset failed"); return PCS_ELAUNCH; }
   if (n == 0) return PCS_OK;
   if (!feat || !pxpy) { set_error("pcs_denselize_fwd: null pointer"); return PCS_EINVAL; }
-  RowGrid rg = row_grid(n, C);
+  const RowLaunch rg = row_launch(n, C, kRowsPow2);
   hipLaunchKernelGGL(denselize_fwd_kernel, rg.grid, rg.block, 0, st, feat, count_map, pxpy, n, B, C, H, W, out);
   return check_launch("pcs_denselize_fwd");
 }
@@ -277,7 +265,7 @@ extern "C" int pcs_denselize_bwd_f32(const float *gout, const int32_t *count_map
   if (n < 0 || B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("pcs_denselize_bwd: bad sizes"); return PCS_EINVAL; }
   if (n == 0) return PCS_OK;
   if (!gout || !count_map || !pxpy || !gfeat) { set_error("pcs_denselize_bwd: null pointer"); return PCS_EINVAL; }
-  RowGrid rg = row_grid(n, C);
+  const RowLaunch rg = row_launch(n, C, kRowsPow2);
   hipLaunchKernelGGL(denselize_bwd_kernel, rg.grid, rg.block, 0, as_stream(stream), gout, count_map, pxpy, n, B, C, H, W, gfeat);
   return check_launch("pcs_denselize_bwd");
 }

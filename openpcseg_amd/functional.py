@@ -60,7 +60,7 @@ def spcount(coords, num):
 # ---------------------------------------------------------------------------------------------
 # voxelize / devoxelize under autocast. "fp32" (library default): the feature tensor is cast to fp32 and the fp32 kernels run, fp32
 # out -- every point <-> voxel hop of a bf16 model then converts in front and the consumer converts back. "keep": no cast; a
-# bf16 / fp16 tensor runs on the 16-bit kernels (csrc/pointvoxel_half.hip: fp32 accumulation, one rounding on the store) and
+# bf16 / fp16 tensor runs on the 16-bit kernels (csrc/pointvoxel.hip: fp32 accumulation, one rounding on the store) and
 # leaves in its own dtype, an fp32 tensor stays on the fp32 kernels. "keep" never casts fp32 DOWN: initial_voxelize averages
 # voxel COORDINATES through spvoxelize, and the reference's `custom_fwd(cast_inputs=torch.half)`
 # (TS:torchsparse/nn/functional/voxelize.py) rounds those to fp16 under --amp, where coordinates above 2048 lose their low

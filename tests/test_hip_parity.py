@@ -1,11 +1,13 @@
 """Parity of the HIP path (through the C ABI) with the oracle and the reference goldens.
 Run with `-m gpu` on an MI355X. Integer / index work: bit-exact. fp32: tolerance stated per test.
 """
+import functools
 import os
 import numpy as np
 import pytest
 import torch
 
+from openpcseg_amd import native
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -109,6 +111,138 @@ def test_devoxelize(hip, c, m):
     close(hip.devoxelize_fwd(t(feat), t(idx8), t(w8)), orc.devoxelize_fwd(feat, idx8, w8), 1e-6)
     gout = rng.normal(size=(n, c)).astype(np.float32)
     close(hip.devoxelize_bwd(t(gout), t(idx8), t(w8), m), orc.devoxelize_bwd(gout, idx8, w8, m), 1e-5)
+
+
+# The fp32 CSR entries run the kernel family they share with the 16-bit rows (csrc/pointvoxel.hip). Inputs on which every fp32
+# operation is exact, so the result has to equal a float64 evaluation bit for bit whatever the instance (V = 4 / 1, one or
+# two passes of the lane row, lane-row or wave-per-voxel K10).
+CSR_RUNS = (0, 1, 2, 3, 4, 5, 7, 16)   # entries per voxel: empty, every remainder of the groups of 2 / 4 row loads, one long run
+
+
+def _f32_bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+def _exact_f32(y64):
+    y32 = y64.astype(np.float32)
+    assert (y32.astype(np.float64) == y64).all()   # the reference itself is representable: no rounding anywhere
+    return _f32_bits(y32)
+
+
+@functools.lru_cache(maxsize=None)
+def csr_exact_case(c):
+    """Small-integer features, weights that are multiples of 1/8, counts that are powers of two: every quotient, product and
+    partial sum is exact in fp32. The float64 references are computed here once; nothing mutates them."""
+    rng = np.random.default_rng(7000 + c)
+    m, runs = len(CSR_RUNS), np.array(CSR_RUNS)
+    rowptr = np.concatenate([[0], np.cumsum(runs)]).astype(np.int64)
+    ne = int(rowptr[-1])                                                    # 38 entries
+    k = dict(c=c, m=m, rowptr=rowptr)
+    # K7: 38 points, `order` = their rows sorted by voxel
+    k["feats"] = rng.integers(-8, 9, size=(ne, c)).astype(np.float32)
+    k["order7"] = rng.permutation(ne).astype(np.int64)
+    k["counts_pow2"] = np.array([0, 1, 2, 4, 4, 8, 8, 16], np.int32)
+    k["counts_true"] = runs.astype(np.int32)
+    y7 = np.zeros((m, c))
+    y7t = np.zeros((m, c), np.float32)
+    for v in range(m):
+        for e in range(rowptr[v], rowptr[v + 1]):
+            row = k["feats"][k["order7"][e]]
+            y7[v] += row.astype(np.float64) / float(k["counts_pow2"][v])
+            y7t[v] = y7t[v] + row / np.float32(k["counts_true"][v])        # float32: divide, then add in `order` order
+    k["vox_exact"], k["vox_true"] = _exact_f32(y7), _f32_bits(y7t)
+    # K9 / K10: 6 points; 38 of the first 40 (point, corner) slots hold a voxel, point 5 has none
+    n = 6
+    slots = np.sort(rng.permutation(40)[:ne])
+    flat = np.full(n * 8, -1, np.int32)
+    flat[slots] = rng.permutation(np.repeat(np.arange(m), runs)).astype(np.int32)
+    k["n"], k["idx8"] = n, flat.reshape(n, 8)
+    k["order10"] = slots[np.argsort(flat[slots], kind="stable")].astype(np.int64)
+    k["w8"] = (rng.integers(0, 9, size=(n, 8)) / 8.0).astype(np.float32)
+    k["feat"] = rng.integers(-8, 9, size=(m, c)).astype(np.float32)
+    k["gout"] = rng.integers(-8, 9, size=(n, c)).astype(np.float32)
+    y9 = np.zeros((n, c))
+    for i in range(n):
+        for j in range(8):
+            if k["idx8"][i, j] >= 0:
+                y9[i] += float(k["w8"][i, j]) * k["feat"][k["idx8"][i, j]].astype(np.float64)
+    y10 = np.zeros((m, c))
+    for v in range(m):
+        for e in range(rowptr[v], rowptr[v + 1]):
+            p_ = int(k["order10"][e])
+            assert k["idx8"].reshape(-1)[p_] == v
+            y10[v] += float(k["w8"].reshape(-1)[p_]) * k["gout"][p_ >> 3].astype(np.float64)
+    k["devox_exact"], k["devox_bwd_exact"] = _exact_f32(y9), _exact_f32(y10)
+    return k
+
+
+def _rows_f32(a, off, fill=None):
+    """(rows, c) fp32 device tensor with the values of `a` (or `fill`), its base pointer `off` floats past an aligned one."""
+    buf = torch.full((a.shape[0] * a.shape[1] + off,), float("nan") if fill is None else fill, dtype=torch.float32, device=DEV)
+    v = buf[off:].view(a.shape[0], a.shape[1])
+    assert v.data_ptr() % 16 == 4 * off
+    if fill is None:
+        v.copy_(torch.from_numpy(a))
+    return v
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c,off", [(3, 0), (4, 0), (36, 0), (260, 0), (36, 1)])
+def test_fp32_csr_entries_are_exact(hip, c, off):
+    """pcs_voxelize_fwd_csr_f32, pcs_devoxelize_fwd_f32 and pcs_devoxelize_bwd_csr_f32 on csr_exact_case: c = 3 scalar accesses,
+    4 one 16-byte piece (the wave-per-voxel K10), 36 nine pieces (the lane-row K10), 260 two passes of the lane row; off = 1: the
+    same rows behind a base pointer one float off, which takes the scalar instances. Outputs are NaN-prefilled: every row is
+    written, rows of empty runs and of the point without a voxel as exact +0."""
+    k = csr_exact_case(c)
+    lib, ptr, st = native.load_library(), native._ptr, native._stream()
+    m, n, rowptr = k["m"], k["n"], t(k["rowptr"])
+    nan = float("nan")
+    feats, order7 = _rows_f32(k["feats"], off), t(k["order7"])
+    for counts, want in ((t(k["counts_pow2"]), k["vox_exact"]), (t(k["counts_true"]), k["vox_true"])):
+        out = _rows_f32(np.empty((m, c), np.float32), off, nan)
+        assert lib.pcs_voxelize_fwd_csr_f32(ptr(feats), ptr(order7), ptr(rowptr), ptr(counts), m, c, ptr(out), st) == 0
+        got = _f32_bits(out.cpu().numpy())
+        assert np.array_equal(got, want), (c, off, np.argwhere(got != want)[:4])
+        assert (got[0] == 0).all()
+    idx8, w8, feat = t(k["idx8"]), t(k["w8"]), _rows_f32(k["feat"], off)
+    out = _rows_f32(np.empty((n, c), np.float32), off, nan)
+    assert lib.pcs_devoxelize_fwd_f32(ptr(feat), ptr(idx8), ptr(w8), n, c, ptr(out), st) == 0
+    got = _f32_bits(out.cpu().numpy())
+    assert np.array_equal(got, k["devox_exact"]), (c, off)
+    assert (got[5] == 0).all()
+    gout, order10, gfeat = _rows_f32(k["gout"], off), t(k["order10"]), _rows_f32(np.empty((m, c), np.float32), off, nan)
+    assert lib.pcs_devoxelize_bwd_csr_f32(ptr(gout), ptr(order10), ptr(rowptr), ptr(w8), m, c, ptr(gfeat), st) == 0
+    got = _f32_bits(gfeat.cpu().numpy())
+    assert np.array_equal(got, k["devox_bwd_exact"]), (c, off)
+    assert (got[0] == 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("c", [4, 8])
+def test_voxelize_bwd_keeps_its_zeros(hip, c, dtype):
+    """K8 on a gradient row of -0 and on a point without a voxel. This pins the PRESENT behaviour of each storage format (the
+    kernels of the three formats are one template now); it is not a statement about the reference: the fp32 kernel stores the
+    quotient itself, so the row keeps the sign bit of gout / count, the 16-bit kernels add the quotient to a zeroed accumulator
+    and store +0. The row of the point without a voxel is +0 in all three."""
+    lib, ptr, st = native.load_library(), native._ptr, native._stream()
+    gout = np.stack([np.full(c, -0.0, np.float32), np.arange(1, c + 1, dtype=np.float32) * np.float32(-0.75)])
+    idx, counts = t(np.array([0, 1, -1, 0], np.int32)), t(np.array([2, 1], np.int32))   # (held: the calls below take raw pointers)
+    g = t(gout).to(dtype)
+    gin = torch.full((4, c), float("nan"), dtype=dtype, device=DEV)
+    if dtype == torch.float32:
+        rc = lib.pcs_voxelize_bwd_f32(ptr(g), ptr(idx), ptr(counts), 4, c, ptr(gin), st)
+        bits = gin.view(torch.int32).cpu().numpy()
+        minus_zero = _f32_bits(gout[0] / np.float32(2))                      # the sign bit of gout / count
+        assert (minus_zero == np.int32(-2 ** 31)).all()
+    else:
+        rc = lib.pcs_voxelize_bwd_h(ptr(g), ptr(idx), ptr(counts), 4, c, 1 if dtype == torch.bfloat16 else 2, ptr(gin), st)
+        bits = gin.view(torch.int16).cpu().numpy()
+        minus_zero = np.zeros(c, np.int16)                                   # +0, as the 16-bit kernels always gave
+    assert rc == 0
+    assert np.array_equal(bits[0], minus_zero) and np.array_equal(bits[3], minus_zero)
+    assert (bits[2] == 0).all()
+    assert torch.equal(gin[1], g[1])                                         # count 1: the row itself (-0.75 j is exact in all three)
 
 
 def test_ti_weights_golden(hip, golden):

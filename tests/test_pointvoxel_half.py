@@ -1,4 +1,4 @@
-"""spvoxelize / spdevoxelize with 16-bit features (csrc/pointvoxel_half.hip) against a float64 oracle.
+"""spvoxelize / spdevoxelize with 16-bit features (the bf16 / fp16 instances of csrc/pointvoxel.hip) against a float64 oracle.
 
 The features arrive as bf16 / fp16 and leave in the same format; the kernels accumulate in fp32 registers and round once on the
 store. Bound (derived, not measured): with y the float64 result computed from the STORED inputs (already rounded to 16 bits,

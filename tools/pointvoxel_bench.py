@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """spvoxelize / spdevoxelize on the 12-scan bench batch at the shapes of SPVCNN's point <-> voxel hops: today's autocast path
-(bf16 -> fp32 cast, the fp32 kernel, fp32 -> bf16 cast for the consumer) against the 16-bit kernels of csrc/pointvoxel_half.hip,
+(bf16 -> fp32 cast, the fp32 kernel, fp32 -> bf16 cast for the consumer) against the 16-bit instances of csrc/pointvoxel.hip,
 the latter as shipped and, where the kernel has that choice (the lane-row segmented kernels), forced to 2 and to 4 row loads in
 flight.
 
