@@ -356,6 +356,101 @@ except ImportError:   # older torch: the pass rule and the version counters alon
     pass
 
 
+def _conv_family(be, hd, on_device, cin, cout, k, x3=True):
+    """Which kernel family serves a (k, cin, cout) convolution: "half" (conv_gather_gemm_h), "x3" (conv_gather_gemm_x3) or "fp32"
+    (conv_gather_gemm, rounded afterwards when a half dtype `hd` is in play). The rules are in DESIGN.md, "Convolution routing".
+    A host operand is fp32 without asking the backend anything: host backends need none of the shape queries."""
+    if not on_device:
+        return "fp32"
+    if hd is not None:
+        return "half" if be.conv_h_applies(cin, cout, k) else "fp32"
+    if x3 and _CONV_POLICY["mode"] == "bf16x3" and be.conv_x3_applies(cin, cout, k):
+        return "x3"
+    return "fp32"
+
+
+def _memo(cache, key, make):
+    if cache is None:
+        return make()
+    if key not in cache:
+        cache[key] = make()
+    return cache[key]
+
+
+# Where the derived copies of one weight (and the answers of its shape queries) are kept: kept(key, make) -> value. Weight keys are
+# _WeightPrep's -- ("t",), (half dtype, transpose) -- plus ("x3", transpose), which no cache of the training path holds.
+def _per_call(key, make):
+    return make()
+
+
+def _kept_in_pass(be, weight):
+    """The per-pass _WEIGHT_PREP cache for the copies it holds of the weights it serves, else per call."""
+    return lambda key, make: (_WEIGHT_PREP.get(be, weight, key) if (key == ("t",) or key[0] in _HALF) and _WeightPrep.usable(be, weight)
+                              else make())
+
+
+def _kept_in(memo, prefix=()):
+    """A dict owned by the caller, who drops it when the weight changes (the `prepared` dict of the inference path)."""
+    return lambda key, make: _memo(memo, prefix + key, make)
+
+
+def _weight_copy(be, w3, key, kept):
+    """The copy `key` of the fp32 master weights w3 (K, A, B), from where `kept` keeps it."""
+    def make():
+        w = w3.detach().float().contiguous()
+        if key == ("t",):
+            return be.transpose_weights(w)
+        return be.prepare_weights_x3(w, transpose=key[1]) if key[0] == "x3" else be.prepare_weights_h(w, key[0], transpose=key[1])
+    return kept(key, make)
+
+
+def _run_conv(be, fam, x, w3, kmap, hd, kept, transpose=False, bias=None, stats=None, addend=None, cast_addend=False,
+              act_slope=None, relu=False, rounded=True):
+    """One routed convolution: x over kmap with the fp32 master weights w3 (K, A, B) on the family `fam` names -- the operand cast,
+    the weight copy from `kept`, the backend entry, and (rounded) an fp32 result rounded to hd -> (out, the cast operand, took).
+    transpose: contract over B (dgrad). stats: a list for the write-back's BatchNorm statistics; emptied again when the result is
+    rounded (they describe the fp32 values). addend / relu: write-back extras the kernel takes where it can; `took` says whether
+    it did, the caller does them itself otherwise. An addend rides as it is, in a kernel whose output is final in the addend's
+    dtype, or (cast_addend) cast to the kernel's. act_slope is not negotiable: the caller asked conv_act_fusable() first."""
+    k, a, b = w3.shape
+    cin, cout = (b, a) if transpose else (a, b)
+    kdt = hd if fam == "half" else torch.float32   # what the kernel reads and writes
+    x = x.contiguous().to(hd) if fam == "half" else x.contiguous().float()
+    if fam != "fp32":
+        wp = _weight_copy(be, w3, (hd if fam == "half" else "x3", transpose), kept)
+    else:
+        wp = _weight_copy(be, w3, ("t",), kept) if transpose else w3.float().contiguous()
+    kw = {}
+    if bias is not None:
+        kw["bias"] = bias
+    if stats is not None:
+        kw["bn_sums"] = stats
+        if getattr(be, "supports_bn_raw", False):
+            kw["bn_raw"] = True   # the per-tile partials themselves: the BatchNorm reduces and finalizes them in ONE launch
+    if act_slope is not None:
+        assert fam != "x3", "act_slope: the bf16x3 entry has no write-back extras (conv_act_fusable)"
+        kw["act_slope"] = float(act_slope)
+    took = False
+    if (addend is not None or relu) and fam != "x3" and hasattr(be, "conv_supports_addend") and \
+            (not relu or getattr(be, "conv_epilogue_relu", False)) and \
+            (addend is None or cast_addend or (addend.is_cuda and addend.dtype == kdt == (hd or torch.float32))):
+        code = native.HipBackend._HALF[hd] if fam == "half" else 0
+        took = kept(("epilogue?", code, transpose), lambda: be.conv_supports_addend(cin, cout, k, code))
+    if took and addend is not None:
+        kw["addend"] = addend.to(hd) if fam == "half" else addend.float()
+    if took and relu:
+        kw["relu"] = True
+    if fam == "fp32":
+        out = be.conv_gather_gemm(x, wp, kmap, **kw)
+    else:
+        out = getattr(be, "conv_gather_gemm_h" if fam == "half" else "conv_gather_gemm_x3")(x, wp, k, cout, kmap, **kw)
+    if rounded and hd is not None and out.dtype != hd:
+        out = out.to(hd)
+        if stats is not None:
+            del stats[:]
+    return out, x, took
+
+
 class _SparseConv(Function):
     """out = conv(input) over a kernel map; backward = dgrad (same fused kernel on the other
     map, per-offset transposed weights) + wgrad (split reduction).
@@ -386,28 +481,8 @@ class _SparseConv(Function):
         k, cin, cout = w3.shape
         kmap = entry.rev if transposed else entry.fwd
         got = [] if want_stats else None
-        kw = {"bn_sums": got} if want_stats else {}
-        if want_stats and getattr(be, "supports_bn_raw", False):
-            kw["bn_raw"] = True   # the per-tile partials themselves: the BatchNorm reduces and finalizes them in ONE launch
-        if act_slope is not None:
-            kw["act_slope"] = float(act_slope)
-        if hd is not None and input.is_cuda and be.conv_h_applies(cin, cout, k):
-            x = input.contiguous().to(hd)
-            if _WeightPrep.usable(be, weight):
-                wp = _WEIGHT_PREP.get(be, weight, (hd, False))
-            else:
-                wp = be.prepare_weights_h(w3.detach().float().contiguous(), hd, transpose=False)
-            out = be.conv_gather_gemm_h(x, wp, k, cout, kmap, **kw)
-        elif hd is None and input.is_cuda and _CONV_POLICY["mode"] == "bf16x3" and be.conv_x3_applies(cin, cout, k):
-            x = input.contiguous().float()
-            wp = be.prepare_weights_x3(w3.detach().float().contiguous(), transpose=False)
-            out = be.conv_gather_gemm_x3(x, wp, k, cout, kmap, **kw)
-        else:
-            x = input.contiguous().float()
-            out = be.conv_gather_gemm(x, w3.float().contiguous(), kmap, **kw)
-            if hd is not None:
-                out = out.to(hd)
-                got = [] if want_stats else None  # statistics of the fp32 values, not of the rounded ones: not used
+        fam = _conv_family(be, hd, input.is_cuda, cin, cout, k)
+        out, x, _ = _run_conv(be, fam, input, w3, kmap, hd, _kept_in_pass(be, weight), stats=got, act_slope=act_slope)
         ctx.for_backwards = (x, weight, entry, transposed, hd)
         ctx.with_skip = with_skip
         ctx.in_dtype = input.dtype
@@ -437,35 +512,13 @@ class _SparseConv(Function):
         # would need cross-stream ordering)
         if need_dx:
             dmap = entry.fwd if transposed else entry.rev
-            out_dtype = x.dtype if hd is None else hd   # the gradient leaves in the dtype the forward input arrived in
-            rides = (grad_skip is not None and grad_skip.is_cuda and grad_skip.dtype == out_dtype and
-                     hasattr(be, "conv_supports_addend"))   # the skip gradient as the dgrad kernel's write-back addend
-            if hd is not None and be.conv_h_applies(cout, cin, k):
-                if _WeightPrep.usable(be, weight):
-                    wp = _WEIGHT_PREP.get(be, weight, (hd, True))
-                else:
-                    wp = be.prepare_weights_h(w3.detach().float().contiguous(), hd, transpose=True)
-                ok = be.conv_supports_addend(cout, cin, k, 1) if rides else False
-                kw = {}
-                if rides and ok:
-                    kw["addend"], grad_skip = grad_skip, None
-                grad_input = be.conv_gather_gemm_h(grad_output.contiguous().to(hd), wp, k, cin, dmap, **kw)
-            elif hd is None and grad_output.is_cuda and _CONV_POLICY["mode"] == "bf16x3" and be.conv_x3_applies(cout, cin, k):
-                wp = be.prepare_weights_x3(w3.detach().float().contiguous(), transpose=True)
-                grad_input = be.conv_gather_gemm_x3(grad_output.contiguous().float(), wp, k, cin, dmap)
-            else:
-                if _WeightPrep.usable(be, weight):
-                    wt = _WEIGHT_PREP.get(be, weight, ("t",))
-                else:
-                    wt = be.transpose_weights(w3.detach().float().contiguous())
-                ok = (hd is None and out_dtype == torch.float32 and be.conv_supports_addend(cout, cin, k, 0)) if rides else False
-                kw = {}
-                if rides and ok:
-                    kw["addend"], grad_skip = grad_skip, None
-                grad_input = be.conv_gather_gemm(grad_output.contiguous().float(), wt, dmap, **kw)
-            grad_input = grad_input.to(out_dtype)
-            if grad_skip is not None:   # a kernel that takes no addend (generic shapes, the split kernels, other backends)
-                grad_input = grad_input + grad_skip.to(out_dtype)
+            # the gradient leaves in the dtype the forward input arrived in; the skip gradient rides as the dgrad kernel's
+            # write-back addend where the kernel takes one (not: generic shapes, the split kernels, other backends)
+            fam = _conv_family(be, hd, grad_output.is_cuda, cout, cin, k)
+            grad_input, _, took = _run_conv(be, fam, grad_output, w3, dmap, hd, _kept_in_pass(be, weight), transpose=True,
+                                            addend=grad_skip)
+            if grad_skip is not None and not took:
+                grad_input = grad_input + grad_skip.to(grad_input.dtype)
         elif grad_skip is not None:
             grad_input = grad_skip
         if need_dw:
@@ -484,15 +537,11 @@ class _SparseConv(Function):
 def conv_act_fusable(feats, weight):
     """The convolution of these operands runs on a kernel that takes the write-back extras (LeakyReLU, addend)."""
     be = _be()
-    if not (feats.is_cuda and hasattr(be, "conv_supports_addend") and weight.dim() == 3):
+    if not (feats.is_cuda and hasattr(be, "conv_supports_addend") and weight.dim() == 3) or _channel_padding(feats, weight) != (0, 0):
         return False
     k, cin, cout = weight.shape
-    if _channel_padding(feats, weight) != (0, 0) or (_amp_dtype(feats) is None and _CONV_POLICY["mode"] == "bf16x3"):
-        return False
-    hd = _amp_dtype(feats)
-    if hd is not None and be.conv_h_applies(cin, cout, k):
-        return True
-    return be.conv_supports_addend(cin, cout, k, 0)
+    fam = _conv_family(be, _amp_dtype(feats), True, cin, cout, k)   # what _SparseConv.forward will pick
+    return fam == "half" or (fam == "fp32" and be.conv_supports_addend(cin, cout, k, 0))
 
 
 def _identity_map(n, device, cache):
@@ -571,28 +620,17 @@ def _channel_padding(feats, weight):
 def _sparse_conv(feats, weight, entry, transposed, bn_stats, with_skip=False, act_slope=None):
     """-> (out, bn_sums or None[, skip alias of feats when with_skip])."""
     pin, pout = _channel_padding(feats, weight)
-    if act_slope is not None:
-        assert not (pin or pout), "act_slope: the caller checks conv_act_fusable()"
-        outs = _SparseConv.apply(feats, weight, entry, transposed, bool(bn_stats), bool(with_skip), float(act_slope))
-        outs = outs if isinstance(outs, tuple) else (outs,)
-        sums = outs[1] if bn_stats else None
-        res = (outs[0], (sums if sums is not None and sums.numel() else None))
-        return res + (outs[-1],) if with_skip else res
+    assert act_slope is None or not (pin or pout), "act_slope: the caller checks conv_act_fusable()"
+    x, cout, node_skip = feats, weight.shape[-1], bool(with_skip)
     if pin or pout:
-        cout = weight.shape[2]
-        padded = torch.nn.functional.pad(feats, (0, pin)) if pin else feats
+        x = torch.nn.functional.pad(feats, (0, pin)) if pin else feats
         weight = torch.nn.functional.pad(weight, (0, pout, 0, pin))
-        out = _SparseConv.apply(padded, weight, entry, transposed)
-        res = ((out[:, :cout].contiguous() if pout else out), None)   # the epilogue statistics would cover the padded columns: not used
-        return res + (feats,) if with_skip else res
-    if not bn_stats and not with_skip:
-        return _SparseConv.apply(feats, weight, entry, transposed), None
-    outs = _SparseConv.apply(feats, weight, entry, transposed, bool(bn_stats), bool(with_skip))
+        bn_stats = node_skip = False   # the epilogue statistics would cover the padded columns; the skip is the unpadded input
+    outs = _SparseConv.apply(x, weight, entry, transposed, bool(bn_stats), node_skip, act_slope)
     outs = outs if isinstance(outs, tuple) else (outs,)
-    out = outs[0]
-    sums = outs[1] if bn_stats else None
-    res = (out, (sums if sums is not None and sums.numel() else None))
-    return res + (outs[-1],) if with_skip else res
+    out = outs[0][:, :cout].contiguous() if pout else outs[0]
+    sums = outs[1] if bn_stats and outs[1].numel() else None
+    return (out, sums, outs[-1] if node_skip else feats) if with_skip else (out, sums)
 
 
 def prebuild_coords(x, steps):
@@ -683,14 +721,6 @@ def conv3d(input, weight, kernel_size, bias=None, stride=1, dilation=1, transpos
     return output
 
 
-def _memo(cache, key, make):
-    if cache is None:
-        return make()
-    if key not in cache:
-        cache[key] = make()
-    return cache[key]
-
-
 def conv3d_inference(input, weight, bias, kernel_size, stride=1, dilation=1, transposed=False, addend=None, relu=False,
                      prepared=None):
     """Forward-only convolution of the inference path (openpcseg_amd.inference): act(conv(x, weight) + bias [+ addend]) in ONE
@@ -718,44 +748,21 @@ def conv3d_inference(input, weight, bias, kernel_size, stride=1, dilation=1, tra
     else:
         kmap = None   # host backends: a 1x1x1 convolution is a matrix product
     pin, pout = _channel_padding(feats, w3)
-    epilogue = bool(getattr(be, "conv_epilogue_relu", False)) and hasattr(be, "conv_supports_addend") and not (pin or pout)
     fused = False
     if kmap is None:
         out = feats.float().matmul(w3[0].float())
         if bias is not None:
             out = out + bias
-    elif pin or pout:
-        x = torch.nn.functional.pad(feats, (0, pin)) if pin else feats
-        wpad = _memo(prepared, ("pad", pin, pout), lambda: torch.nn.functional.pad(w3.float(), (0, pout, 0, pin)).contiguous())
-        bpad = None if bias is None else _memo(prepared, ("bpad", pout), lambda: torch.nn.functional.pad(bias.float(), (0, pout)))
-        if hd is not None and be.conv_h_applies(cin + pin, cout + pout, k):
-            wp = _memo(prepared, ("padh", hd, pin, pout), lambda: be.prepare_weights_h(wpad, hd, transpose=False))
-            out = be.conv_gather_gemm_h(x.contiguous().to(hd), wp, k, cout + pout, kmap, bias=bpad)
-        else:
-            out = be.conv_gather_gemm(x.contiguous().float(), wpad, kmap, bias=bpad)
-        out = out[:, :cout].contiguous() if pout else out
-    elif hd is not None and feats.is_cuda and _memo(prepared, ("h?", hd), lambda: be.conv_h_applies(cin, cout, k)):
-        wp = _memo(prepared, (hd,), lambda: be.prepare_weights_h(w3.float().contiguous(), hd, transpose=False))
-        kw = {}
-        fused = epilogue and (not (relu or addend is not None) or
-                              _memo(prepared, ("epilogue?", hd), lambda: be.conv_supports_addend(cin, cout, k, be._HALF[hd])))
-        if fused and addend is not None:
-            kw["addend"] = addend.to(hd)
-        if fused and relu:
-            kw["relu"] = True
-        out = be.conv_gather_gemm_h(feats.contiguous().to(hd), wp, k, cout, kmap, bias=bias, **kw)
-    elif hd is None and feats.is_cuda and _CONV_POLICY["mode"] == "bf16x3" and be.conv_x3_applies(cin, cout, k):
-        wp = _memo(prepared, ("x3",), lambda: be.prepare_weights_x3(w3.float().contiguous(), transpose=False))
-        out = be.conv_gather_gemm_x3(feats.contiguous().float(), wp, k, cout, kmap, bias=bias)   # this entry has no epilogue
     else:
-        kw = {}
-        fused = epilogue and (not (relu or addend is not None) or
-                              _memo(prepared, ("epilogue?", None), lambda: be.conv_supports_addend(cin, cout, k, 0)))
-        if fused and addend is not None:
-            kw["addend"] = addend.float()
-        if fused and relu:
-            kw["relu"] = True
-        out = be.conv_gather_gemm(feats.contiguous().float(), w3.float().contiguous(), kmap, bias=bias, **kw)
+        x, extras, kept = feats, {"addend": addend, "relu": relu, "cast_addend": True}, _kept_in(prepared, (pin, pout))
+        if pin or pout:   # zero-padded widths: no bf16x3 kernel, no write-back extras
+            x, extras = torch.nn.functional.pad(feats, (0, pin)) if pin else feats, {}
+            w3 = kept(("pad",), lambda: torch.nn.functional.pad(w3.float(), (0, pout, 0, pin)).contiguous())
+            bias = None if bias is None else kept(("bpad",), lambda: torch.nn.functional.pad(bias.float(), (0, pout)))
+        fam = kept(("family", hd, _CONV_POLICY["mode"]),
+                   lambda: _conv_family(be, hd, feats.is_cuda, cin + pin, cout + pout, k, x3=not (pin or pout)))
+        out, _, fused = _run_conv(be, fam, x, w3, kmap, hd, kept, bias=bias, rounded=False, **extras)
+        out = out[:, :cout].contiguous() if pout else out
     if not fused:
         if addend is not None:
             out = out.add_(addend.to(out.dtype))

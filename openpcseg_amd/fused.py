@@ -208,20 +208,12 @@ class _SkinnyLinear(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, cache, hd=None):
         """hd: the half dtype under autocast (the 16-bit MFMA kernel serves the forward when its shape rules allow)."""
-        from .functional import _identity_map
+        from . import functional as F_
         be = native.backend()
-        km = _identity_map(x.shape[0], x.device, cache)
+        km = F_._identity_map(x.shape[0], x.device, cache)
         w1 = weight.detach().float().t().contiguous().unsqueeze(0)  # (1, in, out)
-        cin, cout = w1.shape[1], w1.shape[2]
-        if hd is not None and be.conv_h_applies(cin, cout, 1):
-            x = x.contiguous().to(hd)
-            y = be.conv_gather_gemm_h(x, be.prepare_weights_h(w1, hd, transpose=False), 1, cout, km,
-                                      bias.float() if bias is not None else None)
-        else:
-            x = x.contiguous().float()
-            y = be.conv_gather_gemm(x, w1, km, bias.float() if bias is not None else None)
-            if hd is not None:
-                y = y.to(hd)
+        fam = F_._conv_family(be, hd, x.is_cuda, w1.shape[1], w1.shape[2], 1, x3=False)
+        y, x, _ = F_._run_conv(be, fam, x, w1, km, hd, F_._per_call, bias=bias.float() if bias is not None else None)
         ctx.save_for_backward(x, weight)
         ctx.km, ctx.hd, ctx.in_dtype = km, hd, x.dtype
         return y
@@ -253,9 +245,9 @@ class _SkinnyLinearParts(Function):
 
     @staticmethod
     def forward(ctx, weight, bias, cache, hd, *parts):
-        from .functional import _identity_map
+        from . import functional as F_
         be = native.backend()
-        km = _identity_map(parts[0].shape[0], parts[0].device, cache)
+        km = F_._identity_map(parts[0].shape[0], parts[0].device, cache)
         wt = weight.detach().float().t().contiguous()  # (in, out)
         saved, y, col = [], None, 0
         for i, x in enumerate(parts):
@@ -264,13 +256,10 @@ class _SkinnyLinearParts(Function):
             b = bias.float() if (bias is not None and i == 0) else None
             # a part that ARRIVES in half runs on the 16-bit kernel; an fp32 part stays fp32 even under autocast: the
             # pass is HBM-bound, and casting first (read 4 + write 2 + read 2 bytes per element) costs twice the fp32 read
-            if x.dtype != torch.float32 and be.conv_h_applies(cin, w1.shape[2], 1):
-                x = x.contiguous()
-                t = be.conv_gather_gemm_h(x, be.prepare_weights_h(w1.contiguous(), x.dtype, transpose=False), 1, w1.shape[2], km, b).float()
-            else:
-                x = x.contiguous().float()
-                t = be.conv_gather_gemm(x, w1.contiguous(), km, b)
-            y = t if y is None else y.add_(t)
+            hx = x.dtype if x.dtype != torch.float32 else None
+            fam = F_._conv_family(be, hx, x.is_cuda, cin, w1.shape[2], 1, x3=False)
+            t, x, _ = F_._run_conv(be, fam, x, w1, km, hx, F_._per_call, bias=b, rounded=False)   # the sum stays fp32
+            y = t.float() if y is None else y.add_(t.float())
             saved.append(x)
             col += cin
         ctx.save_for_backward(weight, *saved)

@@ -127,13 +127,8 @@ class FoldedLinear:
         be = native.backend()
         km = F._identity_map(xf.shape[0], xf.device, cache)
         hd = xf.dtype if xf.dtype != torch.float32 else None
-        if hd is not None and be.conv_h_applies(cin, cout, 1):
-            wp = F._memo(part, hd, lambda: be.prepare_weights_h(w1, hd, transpose=False))
-            v = be.conv_gather_gemm_h(xf.contiguous(), wp, 1, cout, km)
-        else:
-            v = be.conv_gather_gemm(xf.contiguous().float(), w1, km)
-            if hd is not None:
-                v = v.to(hd)
+        fam = F._conv_family(be, hd, True, cin, cout, 1, x3=False)
+        v = F._run_conv(be, fam, xf, w1, km, hd, F._kept_in(part))[0]
         return F.spdevoxelize(v.float(), idx, wts)
 
 

@@ -390,15 +390,21 @@ class HipBackend:
         _check(self.lib.pcs_count(_ptr(idx), idx.numel(), _ptr(out), int(num), _stream()), "pcs_count")
         return out
 
+    # -- the fp32 / 16-bit twins of the memory-bound operators ----------------------------------
+    _CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}   # dtype code of the _h entries; 0: the _f32 entry
+
+    def _twin(self, stem, code, head, tail):
+        """<stem>_f32(*head, *tail), or for 16-bit rows <stem>_h(*head, code, *tail)."""
+        name = stem + ("_h" if code else "_f32")
+        _check(getattr(self.lib, name)(*head, *((code,) if code else ()), *tail), name)
+
     # -- K7-K10 ---------------------------------------------------------------------------------
     def _pv_feats(self, t, name):
         """A feature tensor of the point <-> voxel operators: fp32, bf16 or fp16 -> (tensor, dtype code of the _h entries or 0)."""
         t = _dev(t, name)
-        if t.dtype == torch.float32:
-            return t, 0
-        if t.dtype not in self._HALF:
+        if t.dtype not in self._CODE:
             raise TypeError("openpcseg_amd: `%s` must be float32, bfloat16 or float16, got %s" % (name, t.dtype))
-        return t, self._HALF[t.dtype]
+        return t, self._CODE[t.dtype]
 
     def voxelize_fwd(self, feats, idx, counts, cache_on=None):
         """out[v] = sum over the points i of voxel v of feats[i] / counts[v]: segmented over the points sorted by
@@ -413,12 +419,7 @@ class HipBackend:
         holder = cache_on if cache_on is not None else idx
         csr = _cached(holder, "_pcs_vox_csr", _cache_key(holder) + (m, idx.shape[0]), lambda: self._csr(idx, m))
         out = torch.empty((m, c), dtype=feats.dtype, device=feats.device)
-        if code:
-            _check(self.lib.pcs_voxelize_fwd_csr_h(_ptr(feats), _ptr(csr[0]), _ptr(csr[1]), _ptr(counts), m, c, code,
-                                                   _ptr(out), _stream()), "pcs_voxelize_fwd_csr_h")
-        else:
-            _check(self.lib.pcs_voxelize_fwd_csr_f32(_ptr(feats), _ptr(csr[0]), _ptr(csr[1]), _ptr(counts), m, c,
-                                                     _ptr(out), _stream()), "pcs_voxelize_fwd_csr_f32")
+        self._twin("pcs_voxelize_fwd_csr", code, [_ptr(feats), _ptr(csr[0]), _ptr(csr[1]), _ptr(counts), m, c], [_ptr(out), _stream()])
         return out
 
     def voxelize_fwd_atomic(self, feats, idx, counts):
@@ -439,12 +440,7 @@ class HipBackend:
         gout, code = self._pv_feats(gout, "grad_output")
         c = gout.shape[1]
         gin = torch.empty((n, c), dtype=gout.dtype, device=gout.device)
-        if code:
-            _check(self.lib.pcs_voxelize_bwd_h(_ptr(gout), _ptr(idx), _ptr(counts), n, c, code, _ptr(gin),
-                                               _stream()), "pcs_voxelize_bwd_h")
-        else:
-            _check(self.lib.pcs_voxelize_bwd_f32(_ptr(gout), _ptr(idx), _ptr(counts), n, c, _ptr(gin),
-                                                 _stream()), "pcs_voxelize_bwd_f32")
+        self._twin("pcs_voxelize_bwd", code, [_ptr(gout), _ptr(idx), _ptr(counts), n, c], [_ptr(gin), _stream()])
         return gin
 
     def devoxelize_fwd(self, feats, idx8, w8):
@@ -454,12 +450,7 @@ class HipBackend:
         w8 = _dev(w8, "weights", torch.float32)
         n, c = idx8.shape[0], feats.shape[1]
         out = torch.empty((n, c), dtype=feats.dtype, device=feats.device)
-        if code:
-            _check(self.lib.pcs_devoxelize_fwd_h(_ptr(feats), _ptr(idx8), _ptr(w8), n, c, code, _ptr(out),
-                                                 _stream()), "pcs_devoxelize_fwd_h")
-        else:
-            _check(self.lib.pcs_devoxelize_fwd_f32(_ptr(feats), _ptr(idx8), _ptr(w8), n, c, _ptr(out),
-                                                   _stream()), "pcs_devoxelize_fwd_f32")
+        self._twin("pcs_devoxelize_fwd", code, [_ptr(feats), _ptr(idx8), _ptr(w8), n, c], [_ptr(out), _stream()])
         return out
 
     def point_merge(self, vox, idx8, w8, lin, stat, gamma, beta):
@@ -479,12 +470,8 @@ class HipBackend:
                              % (tuple(vox.shape), tuple(lin.shape), tuple(idx8.shape), tuple(w8.shape)))
         out = torch.empty((n, c), dtype=lin.dtype, device=lin.device)
         mask = torch.empty((n, c // 32), dtype=torch.int32, device=lin.device)
-        args = [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(lin), _ptr(stat), _ptr(gamma) if gamma is not None else None,
-                _ptr(beta) if beta is not None else None, n, c]
-        if vcode:
-            _check(self.lib.pcs_point_merge_h(*args, vcode, _ptr(out), _ptr(mask), _stream()), "pcs_point_merge_h")
-        else:
-            _check(self.lib.pcs_point_merge_f32(*args, _ptr(out), _ptr(mask), _stream()), "pcs_point_merge_f32")
+        self._twin("pcs_point_merge", vcode, [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(lin), _ptr(stat), _ptr(gamma), _ptr(beta), n, c],
+                   [_ptr(out), _ptr(mask), _stream()])
         return out, mask
 
     def devoxelize_bwd(self, gout, idx8, w8, m):
@@ -498,11 +485,7 @@ class HipBackend:
         gfeat = torch.empty((m, c), dtype=gout.dtype, device=gout.device)
         if code:
             w8 = _dev(w8, "weights", torch.float32)
-            _check(self.lib.pcs_devoxelize_bwd_csr_h(_ptr(gout), _ptr(csr[0]), _ptr(csr[1]), _ptr(w8), m, c, code,
-                                                     _ptr(gfeat), _stream()), "pcs_devoxelize_bwd_csr_h")
-        else:
-            _check(self.lib.pcs_devoxelize_bwd_csr_f32(_ptr(gout), _ptr(csr[0]), _ptr(csr[1]), _ptr(w8), m, c,
-                                                       _ptr(gfeat), _stream()), "pcs_devoxelize_bwd_csr_f32")
+        self._twin("pcs_devoxelize_bwd_csr", code, [_ptr(gout), _ptr(csr[0]), _ptr(csr[1]), _ptr(w8), m, c], [_ptr(gfeat), _stream()])
         return gfeat
 
     def devoxelize_bwd_atomic(self, gout, idx8, w8, m):
@@ -553,7 +536,7 @@ class HipBackend:
         info = torch.empty(3, dtype=torch.int64, device=keys.device)
         ws_bytes = self.lib.pcs_sort_unique_ws_bytes(nk)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=keys.device)
-        _check(self.lib.pcs_sort_unique_i64(_ptr(keys), nk, _ptr(buf), _ptr(info), _ptr(err) if err is not None else None, _ptr(ws),
+        _check(self.lib.pcs_sort_unique_i64(_ptr(keys), nk, _ptr(buf), _ptr(info), _ptr(err), _ptr(ws),
                                             ws_bytes, _stream()), "pcs_sort_unique_i64")
         return buf, info
 
@@ -663,11 +646,12 @@ class HipBackend:
         return order
 
     # -- convolution ----------------------------------------------------------------------------
-    def _bn_partial(self, kmap, t, cin, cout, k, dtype_code, bn_sums, device):
+    def _bn_partial(self, kmap, t, cin, cout, k, dtype_code, bn_sums, device, x3=False):
         """Workspace for the BatchNorm partials of one conv launch, or None when not asked for / not produced."""
         if bn_sums is None or kmap.n_dst == 0:
             return None
-        if not self.lib.pcs_conv_emits_bn_partials(cin, cout, k, t, dtype_code):
+        if not (self.lib.pcs_conv_x3_emits_bn_partials(cin, cout, k, t) if x3 else
+                self.lib.pcs_conv_emits_bn_partials(cin, cout, k, t, dtype_code)):
             return None
         ntiles = (kmap.n_dst + t - 1) // t
         return torch.empty(ntiles * 2 * cout, dtype=torch.float64, device=device)
@@ -693,10 +677,8 @@ class HipBackend:
         partial = _dev(partial, "partial", torch.float64)
         stat = torch.empty(2 * c, dtype=torch.float64, device=partial.device)
         _check(self.lib.pcs_bn_reduce_partials_finalize(_ptr(partial), partial.numel() // (2 * c), c, n, float(eps),
-                                                        float(momentum),
-                                                        _ptr(running_mean) if running_mean is not None else None,
-                                                        _ptr(running_var) if running_var is not None else None, None,
-                                                        _ptr(stat), _stream()), "pcs_bn_reduce_partials_finalize")
+                                                        float(momentum), _ptr(running_mean), _ptr(running_var), None, _ptr(stat),
+                                                        _stream()), "pcs_bn_reduce_partials_finalize")
         return stat
 
     def conv_supports_addend(self, cin, cout, k, dtype=0):
@@ -728,6 +710,32 @@ class HipBackend:
             ep.addend = addend.data_ptr()
         return ctypes.byref(ep), (ep, addend)
 
+    def _conv_launch(self, fn, src, wbuf, k, cin, cout, kmap, bias, tile_rows, bn_sums, ordered, bn_raw, addend=None,
+                     act_slope=None, relu=False, code=0, x3=False):
+        """What the three conv entries share once their operands are checked: tile height, segment table, destination, BatchNorm
+        partial workspace, tile order, write-back extras, the C call `fn` and the reduction of the partials. code: dtype code
+        of src and dst (0 fp32). x3: the bf16x3 kernel has its own partials query and its entry takes no pcs_conv_epilogue."""
+        if k != kmap.K:
+            raise ValueError("kernel volume %d does not match the kernel map (%d)" % (k, kmap.K))
+        if bias is not None:
+            bias = _dev(bias, "bias", torch.float32)
+        t = tile_rows or self.tile_rows(cin, cout, kmap, code)   # x3: the fp32 kernels' heights (same fp32 accumulator tile)
+        seg = self._segments(kmap, t)
+        dst = torch.empty((kmap.n_dst, cout), dtype=src.dtype, device=src.device)
+        part = self._bn_partial(kmap, t, cin, cout, k, code, bn_sums, src.device, x3)
+        order = None
+        if (ordered == "force" or (ordered and self._wants_order(kmap))) and kmap.n_dst > 0:
+            # only the fp32 entry has kernels that ignore the order (conv_wave4, conv_block): it does not build one for them
+            if x3 or code or self.lib.pcs_conv_uses_tile_order(cin, cout, k, 0):
+                order = self._tile_order(kmap, t)
+        # write-back extras: addend (dgrad + skip gradient, inference residual), LeakyReLU slope, ReLU
+        ep, keep = self._epilogue(addend, kmap, cout, src.dtype, act_slope, relu)
+        _check(fn(_ptr(src), src.shape[0], cin, _ptr(wbuf), k, cout, _ptr(kmap._pairs_raw), 0, _ptr(seg), t, kmap.n_dst, _ptr(bias),
+                  *(() if x3 else (ep,)), _ptr(dst), *((code,) if code else ()), _ptr(part), _ptr(order), _stream()), fn.__name__)
+        if part is not None:
+            self._bn_reduce(part, t, kmap, cout, bn_sums, bn_raw)
+        return dst
+
     def conv_gather_gemm(self, src, weight, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True, bn_raw=False, addend=None,
                          act_slope=None, relu=False):
         """dst[d] = sum_{(s,d) in offset k} src[s] @ weight[k] (+bias); kmap dst-sorted. bn_sums: a list; when the
@@ -739,26 +747,8 @@ class HipBackend:
         k, cin, cout = weight.shape
         if src.shape[1] != cin:
             raise ValueError("Input feature size and kernel size mismatch")  # convolution_cuda.cu:57-59
-        if k != kmap.K:
-            raise ValueError("kernel volume %d does not match the kernel map (%d)" % (k, kmap.K))
-        if bias is not None:
-            bias = _dev(bias, "bias", torch.float32)
-        t = tile_rows or self.tile_rows(cin, cout, kmap)
-        seg = self._segments(kmap, t)
-        dst = torch.empty((kmap.n_dst, cout), dtype=torch.float32, device=src.device)
-        part = self._bn_partial(kmap, t, cin, cout, k, 0, bn_sums, src.device)
-        order = self._tile_order(kmap, t) if (ordered == "force" or (ordered and self._wants_order(kmap))) and kmap.n_dst > 0 and self.lib.pcs_conv_uses_tile_order(cin, cout, k, 0) else None
-        # write-back extras: addend (dgrad + skip gradient, inference residual), LeakyReLU slope, ReLU
-        ep, keep = self._epilogue(addend, kmap, cout, torch.float32, act_slope, relu)
-        _check(self.lib.pcs_conv_gather_gemm_f32_ex(_ptr(src), src.shape[0], cin, _ptr(weight), k, cout,
-                                                    _ptr(kmap._pairs_raw), 0, _ptr(seg), t, kmap.n_dst,
-                                                    _ptr(bias) if bias is not None else None, ep, _ptr(dst),
-                                                    _ptr(part) if part is not None else None,
-                                                    _ptr(order) if order is not None else None,
-                                                    _stream()), "pcs_conv_gather_gemm_f32")
-        if part is not None:
-            self._bn_reduce(part, t, kmap, cout, bn_sums, bn_raw)
-        return dst
+        return self._conv_launch(self.lib.pcs_conv_gather_gemm_f32_ex, src, weight, k, cin, cout, kmap, bias, tile_rows, bn_sums, ordered,
+                                 bn_raw, addend, act_slope, relu)
 
     # -- half-precision convolution (bf16 / fp16 MFMA) ------------------------------------------------------
     _HALF = {torch.bfloat16: 1, torch.float16: 2}
@@ -788,27 +778,11 @@ class HipBackend:
             raise TypeError("openpcseg_amd: conv_gather_gemm_h wants bfloat16 / float16 features, got %s" % src.dtype)
         src = _dev(src, "input")
         cin = src.shape[1]
-        if k != kmap.K:
-            raise ValueError("kernel volume %d does not match the kernel map (%d)" % (k, kmap.K))
         meta = getattr(wp, "_pcs_prepared", None)
         if meta is not None and meta != ("half", src.dtype, k, cin, cout):
             raise ValueError("openpcseg_amd: prepared weights %s do not match this call (%s)" % (meta, ("half", src.dtype, k, cin, cout)))
-        if bias is not None:
-            bias = _dev(bias, "bias", torch.float32)
-        t = tile_rows or self.tile_rows(cin, cout, kmap, self._HALF[src.dtype])
-        seg = self._segments(kmap, t)
-        dst = torch.empty((kmap.n_dst, cout), dtype=src.dtype, device=src.device)
-        part = self._bn_partial(kmap, t, cin, cout, k, self._HALF[src.dtype], bn_sums, src.device)
-        order = self._tile_order(kmap, t) if (ordered == "force" or (ordered and self._wants_order(kmap))) and kmap.n_dst > 0 else None
-        ep, keep = self._epilogue(addend, kmap, cout, src.dtype, act_slope, relu)
-        _check(self.lib.pcs_conv_gather_gemm_h_ex(_ptr(src), src.shape[0], cin, _ptr(wp), k, cout, _ptr(kmap._pairs_raw), 0,
-                                                  _ptr(seg), t, kmap.n_dst, _ptr(bias) if bias is not None else None, ep,
-                                                  _ptr(dst), self._HALF[src.dtype], _ptr(part) if part is not None else None,
-                                                  _ptr(order) if order is not None else None,
-                                                  _stream()), "pcs_conv_gather_gemm_h")
-        if part is not None:
-            self._bn_reduce(part, t, kmap, cout, bn_sums, bn_raw)
-        return dst
+        return self._conv_launch(self.lib.pcs_conv_gather_gemm_h_ex, src, wp, k, cin, cout, kmap, bias, tile_rows, bn_sums, ordered, bn_raw,
+                                 addend, act_slope, relu, code=self._HALF[src.dtype])
 
     # -- fp32 convolution on the 16-bit MFMAs (three bf16 planes per operand, opt-in) ------------------------------
     def conv_x3_applies(self, cin, cout, k):
@@ -833,28 +807,11 @@ class HipBackend:
         """fp32 fused conv on the bf16 MFMAs: src (n, cin) fp32, wp = prepare_weights_x3(...); fp32 out (fp32-grade)."""
         src = _dev(src, "input", torch.float32)
         cin = src.shape[1]
-        if k != kmap.K:
-            raise ValueError("kernel volume %d does not match the kernel map (%d)" % (k, kmap.K))
         meta = getattr(wp, "_pcs_prepared", None)
         if meta is not None and meta != ("x3", k, cin, cout):
             raise ValueError("openpcseg_amd: prepared weights %s do not match this call (%s)" % (meta, ("x3", k, cin, cout)))
-        if bias is not None:
-            bias = _dev(bias, "bias", torch.float32)
-        t = tile_rows or self.tile_rows(cin, cout, kmap)   # the fp32 kernels' heights (same fp32 accumulator tile, <= its width)
-        seg = self._segments(kmap, t)
-        dst = torch.empty((kmap.n_dst, cout), dtype=torch.float32, device=src.device)
-        part = None
-        if bn_sums is not None and kmap.n_dst > 0 and self.lib.pcs_conv_x3_emits_bn_partials(cin, cout, k, t):
-            part = torch.empty(((kmap.n_dst + t - 1) // t) * 2 * cout, dtype=torch.float64, device=src.device)
-        order = self._tile_order(kmap, t) if (ordered == "force" or (ordered and self._wants_order(kmap))) and kmap.n_dst > 0 else None
-        _check(self.lib.pcs_conv_gather_gemm_f32_bf16x3(_ptr(src), src.shape[0], cin, _ptr(wp), k, cout, _ptr(kmap._pairs_raw),
-                                                        0, _ptr(seg), t, kmap.n_dst, _ptr(bias) if bias is not None else None,
-                                                        _ptr(dst), _ptr(part) if part is not None else None,
-                                                        _ptr(order) if order is not None else None, _stream()),
-               "pcs_conv_gather_gemm_f32_bf16x3")
-        if part is not None:
-            self._bn_reduce(part, t, kmap, cout, bn_sums, bn_raw)
-        return dst
+        return self._conv_launch(self.lib.pcs_conv_gather_gemm_f32_bf16x3, src, wp, k, cin, cout, kmap, bias, tile_rows, bn_sums, ordered,
+                                 bn_raw, x3=True)
 
     def conv_wgrad_h(self, fa, fb, kmap, a_col):
         """Weight gradient from half operands, accumulated and returned in fp32 (K, ca, cb)."""
@@ -1077,7 +1034,7 @@ class HipBackend:
     def _feat(t, name, like=None):
         """A feature tensor of the BN passes: fp32, bf16 or fp16 on the device (and of `like`'s dtype when given)."""
         t = _dev(t, name)
-        if t.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        if t.dtype not in HipBackend._CODE:
             raise TypeError("openpcseg_amd: `%s` must be float32 / bfloat16 / float16, got %s" % (name, t.dtype))
         if like is not None and t.dtype != like.dtype:
             t = t.to(like.dtype)
@@ -1089,22 +1046,15 @@ class HipBackend:
         n, c = x.shape
         ws = torch.empty(self.lib.pcs_bn_num_partials() * 2 * c, dtype=torch.float32, device=x.device)
         sums = torch.empty(2 * c + 1, dtype=torch.float64, device=x.device)
-        if x.dtype == torch.float32:
-            _check(self.lib.pcs_bn_stats_f32(_ptr(x), n, c, _ptr(ws), _ptr(sums), _stream()), "pcs_bn_stats_f32")
-        else:
-            _check(self.lib.pcs_bn_stats_h(_ptr(x), n, c, self._HALF[x.dtype], _ptr(ws), _ptr(sums), _stream()),
-                   "pcs_bn_stats_h")
+        self._twin("pcs_bn_stats", self._CODE[x.dtype], [_ptr(x), n, c], [_ptr(ws), _ptr(sums), _stream()])
         return sums
 
     def bn_finalize(self, sums, count, eps, momentum, running_mean, running_var, count_dev=None):
         """stat = [mean | invstd]; `count_dev` (1-element float64 device tensor, e.g. sums[2c:]) replaces the host count."""
         c = sums.numel() // 2
         stat = torch.empty(2 * c, dtype=torch.float64, device=sums.device)
-        _check(self.lib.pcs_bn_finalize_f32(_ptr(sums), float(count), _ptr(count_dev) if count_dev is not None else None,
-                                            c, float(eps), float(momentum),
-                                            _ptr(running_mean) if running_mean is not None else None,
-                                            _ptr(running_var) if running_var is not None else None, _ptr(stat),
-                                            _stream()), "pcs_bn_finalize_f32")
+        _check(self.lib.pcs_bn_finalize_f32(_ptr(sums), float(count), _ptr(count_dev), c, float(eps), float(momentum),
+                                            _ptr(running_mean), _ptr(running_var), _ptr(stat), _stream()), "pcs_bn_finalize_f32")
         return stat
 
     def bn_apply(self, x, res, stat, w, b, relu, want_mask=False, tail=None):
@@ -1124,15 +1074,8 @@ class HipBackend:
             raise RuntimeError("openpcseg_amd: concat fusion needs equal row counts and channel counts that are multiples of 4")
         y = torch.empty((n, c + ct), dtype=x.dtype, device=x.device)
         mask = torch.empty((n, c // 32), dtype=torch.int32, device=x.device) if want_mask else None
-        args = [_ptr(x), _ptr(res) if res is not None else None, _ptr(stat), _ptr(w) if w is not None else None,
-                _ptr(b) if b is not None else None, n, c, int(relu)]
-        cat = [c + ct, _ptr(tail) if tail is not None else None, ct]
-        if x.dtype == torch.float32:
-            _check(self.lib.pcs_bn_apply_f32(*args, _ptr(y), _ptr(mask) if want_mask else None, *cat, _stream()),
-                   "pcs_bn_apply_f32")
-        else:
-            _check(self.lib.pcs_bn_apply_h(*args, self._HALF[x.dtype], _ptr(y), _ptr(mask) if want_mask else None, *cat,
-                                           _stream()), "pcs_bn_apply_h")
+        self._twin("pcs_bn_apply", self._CODE[x.dtype], [_ptr(x), _ptr(res), _ptr(stat), _ptr(w), _ptr(b), n, c, int(relu)],
+                   [_ptr(y), _ptr(mask), c + ct, _ptr(tail), ct, _stream()])
         return (y, mask) if want_mask else y
 
     @staticmethod
@@ -1166,12 +1109,8 @@ class HipBackend:
         sums2 = buf[:2 * c]
         sums2._pcs_f32 = buf[2 * c:].view(torch.float32)   # [sum g | sum g xhat] in fp32: db | dw without a conversion launch
         yp, mp = self._gate(gate, relu)
-        if x.dtype == torch.float32:
-            _check(self.lib.pcs_bn_bwd_stats_f32(_ptr(dy), _ptr(x), yp, mp, _ptr(stat), n, c, int(relu),
-                                                 _ptr(ws), _ptr(sums2), buf.numel(), lddy, _stream()), "pcs_bn_bwd_stats_f32")
-        else:
-            _check(self.lib.pcs_bn_bwd_stats_h(_ptr(dy), _ptr(x), yp, mp, _ptr(stat), n, c, int(relu), self._HALF[x.dtype],
-                                               _ptr(ws), _ptr(sums2), buf.numel(), lddy, _stream()), "pcs_bn_bwd_stats_h")
+        self._twin("pcs_bn_bwd_stats", self._CODE[x.dtype], [_ptr(dy), _ptr(x), yp, mp, _ptr(stat), n, c, int(relu)],
+                   [_ptr(ws), _ptr(sums2), buf.numel(), lddy, _stream()])
         return sums2
 
     def bn_bwd_apply(self, dy, x, gate, stat, sums2, count, w, relu, want_res, count_dev=None, in_slope=None):
@@ -1182,19 +1121,13 @@ class HipBackend:
         dres = torch.empty_like(x) if want_res else None
         yp, mp = self._gate(gate, relu)
         if in_slope is not None and float(in_slope) != 1.0:   # x is a LeakyReLU output: dx leaves as the gradient of the pre-activation
-            code = 0 if x.dtype == torch.float32 else self._HALF[x.dtype]
-            _check(self.lib.pcs_bn_bwd_apply_act(_ptr(dy), _ptr(x), yp, mp, _ptr(stat), _ptr(sums2), float(count),
-                                                 _ptr(count_dev) if count_dev is not None else None,
-                                                 _ptr(w) if w is not None else None, n, c, int(relu), code, float(in_slope),
-                                                 _ptr(dx), _ptr(dres) if want_res else None, lddy, _stream()), "pcs_bn_bwd_apply_act")
+            _check(self.lib.pcs_bn_bwd_apply_act(_ptr(dy), _ptr(x), yp, mp, _ptr(stat), _ptr(sums2), float(count), _ptr(count_dev),
+                                                 _ptr(w), n, c, int(relu), self._CODE[x.dtype], float(in_slope),
+                                                 _ptr(dx), _ptr(dres), lddy, _stream()), "pcs_bn_bwd_apply_act")
             return dx, dres
-        head = [_ptr(dy), _ptr(x), yp, mp, _ptr(stat), _ptr(sums2), float(count),
-                _ptr(count_dev) if count_dev is not None else None, _ptr(w) if w is not None else None, n, c, int(relu)]
-        tail = [_ptr(dx), _ptr(dres) if want_res else None, lddy, _stream()]
-        if x.dtype == torch.float32:
-            _check(self.lib.pcs_bn_bwd_apply_f32(*head, *tail), "pcs_bn_bwd_apply_f32")
-        else:
-            _check(self.lib.pcs_bn_bwd_apply_h(*head, self._HALF[x.dtype], *tail), "pcs_bn_bwd_apply_h")
+        self._twin("pcs_bn_bwd_apply", self._CODE[x.dtype],
+                   [_ptr(dy), _ptr(x), yp, mp, _ptr(stat), _ptr(sums2), float(count), _ptr(count_dev), _ptr(w), n, c, int(relu)],
+                   [_ptr(dx), _ptr(dres), lddy, _stream()])
         return dx, dres
 
     # -- ReconBlock gate of Cylinder3D (csrc/recongate.hip) ------------------------------------------------
@@ -1205,7 +1138,7 @@ class HipBackend:
         ts = [(t if t.dtype == dt else t.to(dt)).contiguous() for t in ts]
         if any(t.dim() != 2 or t.shape != ts[0].shape for t in ts):
             raise ValueError("openpcseg_amd: the recon gate takes (n, c) tensors of one shape, got %s" % [tuple(t.shape) for t in ts])
-        return ts, (0 if dt == torch.float32 else self._HALF[dt])
+        return ts, self._CODE[dt]
 
     def recon_gate(self, a3, x, stat3, gamma3, beta3):
         """out = x * ((s0 + s1) + s2), s_k = sigmoid(bn_k(a3[k])): the ReconBlock gate in one pass. stat3 (6c,) float64 =
@@ -1213,12 +1146,8 @@ class HipBackend:
         (a0, a1, a2, x), code = self._recon_rows(list(a3) + [x])
         n, c = x.shape
         out = torch.empty_like(x)
-        args = [_ptr(a0), _ptr(a1), _ptr(a2), _ptr(x), _ptr(stat3), _ptr(gamma3) if gamma3 is not None else None,
-                _ptr(beta3) if beta3 is not None else None, n, c]
-        if code:
-            _check(self.lib.pcs_recon_gate_h(*args, code, _ptr(out), _stream()), "pcs_recon_gate_h")
-        else:
-            _check(self.lib.pcs_recon_gate_f32(*args, _ptr(out), _stream()), "pcs_recon_gate_f32")
+        self._twin("pcs_recon_gate", code, [_ptr(a0), _ptr(a1), _ptr(a2), _ptr(x), _ptr(stat3), _ptr(gamma3), _ptr(beta3), n, c],
+                   [_ptr(out), _stream()])
         return out
 
     def recon_gate_bwd_stats(self, dy, x, a3, stat3, gamma3, beta3):
@@ -1230,13 +1159,9 @@ class HipBackend:
         ws = torch.empty(self.lib.pcs_bn_num_partials() * 6 * c, dtype=torch.float32, device=x.device)
         sums2 = buf[:6 * c]
         sums2._pcs_f32 = buf[6 * c:].view(torch.float32)
-        args = [_ptr(dy), _ptr(x), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(stat3), _ptr(gamma3) if gamma3 is not None else None,
-                _ptr(beta3) if beta3 is not None else None, n, c]
-        tail = [_ptr(ws), _ptr(sums2), buf.numel(), _stream()]
-        if code:
-            _check(self.lib.pcs_recon_gate_bwd_stats_h(*args, code, *tail), "pcs_recon_gate_bwd_stats_h")
-        else:
-            _check(self.lib.pcs_recon_gate_bwd_stats_f32(*args, *tail), "pcs_recon_gate_bwd_stats_f32")
+        self._twin("pcs_recon_gate_bwd_stats", code,
+                   [_ptr(dy), _ptr(x), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(stat3), _ptr(gamma3), _ptr(beta3), n, c],
+                   [_ptr(ws), _ptr(sums2), buf.numel(), _stream()])
         return sums2
 
     def recon_gate_bwd_apply(self, dy, x, a3, stat3, gamma3, beta3, sums2, count, count_dev=None):
@@ -1245,14 +1170,9 @@ class HipBackend:
         n, c = x.shape
         dx = torch.empty_like(x)
         da = [torch.empty_like(x) for _ in range(3)]
-        args = [_ptr(dy), _ptr(x), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(stat3), _ptr(gamma3) if gamma3 is not None else None,
-                _ptr(beta3) if beta3 is not None else None, _ptr(sums2), float(count),
-                _ptr(count_dev) if count_dev is not None else None, n, c]
-        tail = [_ptr(dx), _ptr(da[0]), _ptr(da[1]), _ptr(da[2]), _stream()]
-        if code:
-            _check(self.lib.pcs_recon_gate_bwd_apply_h(*args, code, *tail), "pcs_recon_gate_bwd_apply_h")
-        else:
-            _check(self.lib.pcs_recon_gate_bwd_apply_f32(*args, *tail), "pcs_recon_gate_bwd_apply_f32")
+        self._twin("pcs_recon_gate_bwd_apply", code,
+                   [_ptr(dy), _ptr(x), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(stat3), _ptr(gamma3), _ptr(beta3), _ptr(sums2), float(count),
+                    _ptr(count_dev), n, c], [_ptr(dx), _ptr(da[0]), _ptr(da[1]), _ptr(da[2]), _stream()])
         return dx, da
 
     # -- device-side sparse_quantize --------------------------------------------------------------------
@@ -1288,8 +1208,7 @@ class HipBackend:
         index = torch.empty(m, dtype=torch.int64, device=dev) if want_index else None
         inverse = torch.empty(n, dtype=torch.int64, device=dev) if want_inverse else None
         _check(self.lib.pcs_quantize_emit(_ptr(flags), _ptr(rank), _ptr(perm), _ptr(coords), n, _ptr(vox),
-                                          _ptr(index) if want_index else None,
-                                          _ptr(inverse) if want_inverse else None, _stream()), "pcs_quantize_emit")
+                                          _ptr(index), _ptr(inverse), _stream()), "pcs_quantize_emit")
         return vox, index, inverse
 
 
@@ -1364,8 +1283,8 @@ class HipBackend:
         coord = torch.empty((n, 3), dtype=torch.int32, device=dev)
         feat = torch.empty((n, 8 + stride - 3), dtype=torch.float32, device=dev) if want_feat else None
         _check(self.lib.pcs_cylinder_partition_f32(_ptr(points), n, stride, lo, hi, grid,
-                                                   _ptr(polar) if want_polar else None, _ptr(coord),
-                                                   _ptr(feat) if want_feat else None, _stream()),
+                                                   _ptr(polar), _ptr(coord),
+                                                   _ptr(feat), _stream()),
                "pcs_cylinder_partition_f32")
         return polar, coord, feat
 
@@ -1389,7 +1308,7 @@ class HipBackend:
             inverse = _dev(inverse, "inverse_map", torch.int64)
         n = inverse.numel() if inverse is not None else m
         out = torch.empty(n, dtype=torch.int64, device=logits.device)
-        _check(self.lib.pcs_rows_argmax_gather_f32(_ptr(logits), m, c, _ptr(inverse) if inverse is not None else None,
+        _check(self.lib.pcs_rows_argmax_gather_f32(_ptr(logits), m, c, _ptr(inverse),
                                                    n, _ptr(out), _stream()), "pcs_rows_argmax_gather_f32")
         return out
 
@@ -1430,12 +1349,8 @@ class HipBackend:
         if bad is None:
             bad = torch.zeros(1, dtype=torch.int32, device=dev)
         pred = torch.empty(n, dtype=torch.int64, device=dev) if want_pred else None
-        _check(self.lib.pcs_predict_points_f32(_ptr(logits), m, c, _ptr(inverse) if inverse is not None else None, n,
-                                               _ptr(point_offset) if ns else None, _ptr(row_offset) if ns else None, ns,
-                                               _ptr(labels) if labels is not None else None,
-                                               _ptr(votes) if votes is not None else None,
-                                               _ptr(pred) if pred is not None else None,
-                                               _ptr(hist) if hist is not None else None, _ptr(bad), _stream()),
+        _check(self.lib.pcs_predict_points_f32(_ptr(logits), m, c, _ptr(inverse), n, _ptr(point_offset), _ptr(row_offset), ns,
+                                               _ptr(labels), _ptr(votes), _ptr(pred), _ptr(hist), _ptr(bad), _stream()),
                "pcs_predict_points_f32")
         return pred, bad
 
@@ -1455,7 +1370,7 @@ class HipBackend:
         loss = torch.empty((), dtype=torch.float32, device=probas.device)
         grad = torch.empty_like(probas) if need_grad else None
         _check(self.lib.pcs_lovasz_softmax_f32(_ptr(probas), _ptr(labels), n, nc, has_ignore, ign, _ptr(loss),
-                                               _ptr(grad) if grad is not None else None, _ptr(ws), int(ws_bytes), _stream()),
+                                               _ptr(grad), _ptr(ws), int(ws_bytes), _stream()),
                "pcs_lovasz_softmax_f32")
         return loss, grad
 

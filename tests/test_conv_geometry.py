@@ -476,6 +476,81 @@ def counted(hip):
             delattr(hip, n)   # back to the class's methods
 
 
+ENTRY_OF = {"fp32": "conv_gather_gemm", "half": "conv_gather_gemm_h", "x3": "conv_gather_gemm_x3"}
+
+
+def test_conv3d_reaches_the_entry_the_route_names(hip, monkeypatch):
+    """functional.conv3d, forward and dgrad, calls the backend entry functional._conv_family names for that direction (the dgrad with
+    (cout, cin) swapped), once each, and an addend reaches the dgrad entry exactly when the runner reports that the kernel took it.
+    K = 27 on the smallest submanifold geometry of the case table (k3d2_l2) and the strided / transposed pair k3s3; 4 -> 32 (thin:
+    fp32 in every mode), 32 -> 32, 64 -> 64, 96 -> 96; fp32, bf16 autocast on bf16 features, the bf16x3 convolution policy; plain,
+    with_skip, and act_slope = 0.1 where conv_act_fusable says so.
+    CONDITION: over these cases each of the three entries must be the expected one at least once, forward and dgrad, and the
+    addend must both ride and not ride; otherwise the test says nothing and fails as vacuous."""
+    from openpcseg_amd import functional as F
+    from openpcseg_amd.sparse import SparseTensor
+    records = []
+    run = F._run_conv
+
+    def spy(be, fam, *a, **kw):
+        res = run(be, fam, *a, **kw)
+        records.append((fam, bool(kw.get("transpose", False)), bool(res[2])))
+        return res
+    monkeypatch.setattr(F, "_run_conv", spy)
+    fwd_seen, dgrad_seen, rode = set(), set(), set()
+    rng = np.random.default_rng(27)
+    try:
+        for name, transposed in (("k3d2_l2", False), ("k3s3", False), ("k3s3", True)):
+            c = build_case("golden", name)
+            assert c.K == 27
+            for cin, cout in ((4, 32), (32, 32), (64, 64), (96, 96)):
+                x, w, _ = operands(rng, c, cin, cout, transposed)
+                for mode in ("fp32", "autocast_bf16", "conv_bf16x3"):
+                    hd = torch.bfloat16 if mode == "autocast_bf16" else None
+                    F.set_conv_policy("bf16x3" if mode == "conv_bf16x3" else "fp32")
+                    for variant in ("plain", "with_skip", "act_slope"):
+                        dx, dw = t(x).to(hd or torch.float32).requires_grad_(True), t(w).requires_grad_(True)
+                        if transposed:   # the level and its map, as the encoder's strided convolution leaves them
+                            fine = SparseTensor(torch.zeros(c.n_in, 4, device=DEV), c.d_in, c.ts3)
+                            fine.cmaps[c.ts3] = c.d_in
+                            down = F.conv3d(fine, torch.zeros(c.K, 4, 4, device=DEV), c.ks, stride=c.st, dilation=c.dil)
+                            st = SparseTensor(dx, down.C, down.s)
+                            st.cmaps, st.kmaps = down.cmaps, down.kmaps
+                        else:
+                            st = SparseTensor(dx, c.d_in, c.ts3)
+                        del records[:]
+                        with counted(hip) as seen, torch.autocast("cuda", dtype=torch.bfloat16, enabled=hd is not None):
+                            kw = {}
+                            if variant == "act_slope":
+                                if not F.conv_act_fusable(dx, dw):
+                                    continue
+                                kw["act_slope"] = 0.1
+                            fam_f = F._conv_family(hip, hd, True, cin, cout, 27)
+                            fam_d = F._conv_family(hip, hd, True, cout, cin, 27)
+                            if variant == "with_skip":
+                                out, skip = F.conv3d(st, dw, c.ks, stride=c.st, dilation=c.dil, transposed=transposed, with_skip=True)
+                                (out.F.float().sum() + torch.tanh(skip.F.float()).sum()).backward()
+                            else:
+                                F.conv3d(st, dw, c.ks, stride=c.st, dilation=c.dil, transposed=transposed, **kw).F.float().sum().backward()
+                        what = (name, transposed, cin, cout, mode, variant)
+                        (rf, tf, took_f), (rd, td, took) = records
+                        assert (rf, tf, took_f, rd, td) == (fam_f, False, False, fam_d, True), (what, records)
+                        calls = {n: len(seen[n]) for n in ENTRY_OF.values()}
+                        want = {n: [ENTRY_OF[fam_f], ENTRY_OF[fam_d]].count(n) for n in ENTRY_OF.values()}
+                        assert calls == want, (what, calls, want)
+                        fwd_kw, dgrad_kw = seen[ENTRY_OF[fam_f]][0][1], seen[ENTRY_OF[fam_d]][-1][1]
+                        assert fwd_kw.get("addend") is None and fwd_kw.get("act_slope") == kw.get("act_slope"), (what, fwd_kw)
+                        assert (dgrad_kw.get("addend") is not None) == took and (variant == "with_skip" or not took), (what, took)
+                        assert dx.grad is not None and dw.grad is not None
+                        fwd_seen.add(fam_f)
+                        dgrad_seen.add(fam_d)
+                        if variant == "with_skip":
+                            rode.add(took)
+    finally:
+        F.set_conv_policy("fp32")
+    assert fwd_seen == dgrad_seen == set(ENTRY_OF) and rode == {True, False}, (fwd_seen, dgrad_seen, rode)   # the CONDITION above
+
+
 def assert_fp32_entries_only(seen, k):
     """K > 32: the fp32 kernel served forward and dgrad -- no 16-bit, bf16x3 or tile-order call, and (K > 32 has none of them) no
     BatchNorm partials or write-back extras were asked of it."""

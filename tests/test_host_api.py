@@ -540,3 +540,148 @@ def test_sparse_quantize_frames_host_logic(monkeypatch):
     frames = [syn.voxelize_scan(rag["points"][a:b].numpy(), seed=0) for a, b in ((0, 4000), (4000, 6500))]
     ref = sparse_collate_fn(frames)
     assert torch.equal(d["lidar"].C, ref["lidar"].C) and torch.equal(d["lidar"].F, ref["lidar"].F)
+
+
+# ---- convolution routing ("Convolution routing") --------------------------------------------------------------------------------
+class _RouteStub:
+    """A backend of which only the routing surface exists: settable answers to the shape queries, and the three conv entries
+    recording what they are handed."""
+
+    def __init__(self, served_h=False, served_x3=False, extras=False):
+        self.served_h, self.served_x3, self.extras, self.asked, self.calls = served_h, served_x3, extras, [], []
+
+    def conv_h_applies(self, cin, cout, k):
+        self.asked.append("h")
+        return self.served_h
+
+    def conv_x3_applies(self, cin, cout, k):
+        self.asked.append("x3")
+        return self.served_x3
+
+    def conv_supports_addend(self, cin, cout, k, dtype=0):
+        return self.extras
+
+    def prepare_weights_h(self, w, dtype, transpose):
+        return w
+
+    def prepare_weights_x3(self, w, transpose):
+        return w
+
+    def conv_gather_gemm(self, src, weight, kmap, **kw):
+        self.calls.append(("fp32", kw))
+        return torch.zeros((kmap.n_dst, weight.shape[2]), dtype=src.dtype)
+
+    def conv_gather_gemm_h(self, src, wp, k, cout, kmap, **kw):
+        self.calls.append(("half", kw))
+        return torch.zeros((kmap.n_dst, cout), dtype=src.dtype)
+
+    def conv_gather_gemm_x3(self, src, wp, k, cout, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True, bn_raw=False):
+        self.calls.append(("x3", {}))   # the signature of the real entry: no write-back extras
+        return torch.zeros((kmap.n_dst, cout), dtype=src.dtype)
+
+
+def _route_combinations():
+    import itertools
+    return list(itertools.product((None, torch.bfloat16), (True, False), ("fp32", "bf16x3"), (True, False), (True, False)))
+
+
+def _expected_family(hd, on_device, policy, served, x3_allowed):
+    if hd is not None and on_device and served:
+        return "half"
+    if hd is None and on_device and x3_allowed and policy == "bf16x3" and served:
+        return "x3"
+    return "fp32"
+
+
+def test_conv_family_route_table():
+    """functional._conv_family over {no half dtype, bf16} x {device, host} x {policy fp32, bf16x3} x {served, unserved} x {x3 allowed,
+    not}: the rules of DESIGN.md in their order; a host operand is fp32 and asks the backend nothing, so a backend without the two
+    shape queries serves it."""
+
+    class Bare:
+        pass
+
+    seen = set()
+    try:
+        for hd, on_device, policy, served, x3 in _route_combinations():
+            F.set_conv_policy(policy)
+            be = _RouteStub(served_h=served, served_x3=served)
+            fam = F._conv_family(be, hd, on_device, 8, 8, 27, x3=x3)
+            assert fam == _expected_family(hd, on_device, policy, served, x3), (hd, on_device, policy, served, x3, fam)
+            assert fam != "half" or on_device
+            assert fam != "x3" or hd is None
+            if not on_device:
+                assert be.asked == [] and F._conv_family(Bare(), hd, False, 8, 8, 27, x3=x3) == "fp32"
+            elif hd is not None:
+                assert be.asked == ["h"]   # a half dtype in play never asks for the split kernel
+            seen.add(fam)
+    finally:
+        F.set_conv_policy("fp32")
+    assert seen == {"half", "x3", "fp32"}   # not vacuous: every family is the answer somewhere
+
+
+def test_conv_act_fusable_agrees_with_the_route(monkeypatch):
+    """conv_act_fusable is the route's answer: over the combinations of the route table (x3 is always allowed in conv3d; the write-back
+    query answers both ways instead), it is true exactly when the routed forward hands act_slope to an entry that takes it -- the half
+    entry, or the fp32 entry of a shape with write-back extras. The bf16x3 entry is never handed one: the runner refuses. Host
+    operands never fuse (callers ask first). Host tensors stand in for device ones as in test_sparse_quantize_frames_host_logic."""
+    from types import SimpleNamespace
+    n, k, c = 12, 27, 8
+    kmap = SimpleNamespace(n_dst=n, n_src=n, K=k)
+    entry = SimpleNamespace(fwd=kmap, rev=kmap)
+    w = torch.nn.Parameter(torch.randn(k, c, c))
+    seen = set()
+    try:
+        for hd, on_device, policy, served, extras in _route_combinations():
+            F.set_conv_policy(policy)
+            be = _RouteStub(served_h=served, served_x3=served, extras=extras)
+            with monkeypatch.context() as mp:
+                mp.setattr(native, "_BACKEND", be)
+                if on_device:
+                    mp.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
+                x = torch.randn(n, c).to(hd or torch.float32)
+                fusable = F.conv_act_fusable(x, w)
+                fam = _expected_family(hd, on_device, policy, served, True)
+                try:
+                    F._SparseConv.apply(x, w, entry, False, False, False, 0.1)
+                    (name, kw), = be.calls   # one entry call per convolution
+                    assert name == fam and kw.get("act_slope") == 0.1
+                    taken = name == "half" or (name == "fp32" and extras)
+                except AssertionError as e:
+                    assert "act_slope" in str(e) and fam == "x3" and be.calls == []
+                    taken = False
+            assert all(name != "x3" or "act_slope" not in kw for name, kw in be.calls)
+            assert fusable == (taken and on_device), (hd, on_device, policy, served, extras, fusable, taken)
+            seen.add((fam, fusable))
+    finally:
+        F.set_conv_policy("fp32")
+    assert {("half", True), ("fp32", True), ("fp32", False), ("x3", False)} <= seen
+
+
+@pytest.mark.parametrize("backend", ["oracle", "torch_cpu"])
+def test_conv3d_half_host_features_forward_and_backward(monkeypatch, backend):
+    """conv3d on 16-bit HOST features runs forward and backward on a backend that has none of the device shape queries (the oracle
+    adapter): the route sends a host operand to the fp32 entry in both directions. The values are those of the same run on the fp32
+    copy of the features, rounded to bf16 where the 16-bit run rounds (output, input gradient); the weight gradient is exact."""
+    from openpcseg_amd import cpu_fallback
+    from oracle.adapter import OracleBackend
+    be = OracleBackend() if backend == "oracle" else cpu_fallback.TorchCpuBackend()
+    assert backend != "oracle" or not hasattr(be, "conv_h_applies")
+    monkeypatch.setattr(native, "_BACKEND", be)
+    g = torch.Generator().manual_seed(5)
+    box = torch.stack(torch.meshgrid(*[torch.arange(6)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    keep = torch.randperm(box.shape[0], generator=g)[:130].sort().values
+    coords = torch.cat([box[keep], torch.zeros(130, 1, dtype=torch.long)], 1).int()
+    feats = torch.randn(130, 8, generator=g).bfloat16()
+    w0 = torch.randn(27, 8, 8, generator=g) * 0.2
+    res = {}
+    for dtype in (torch.bfloat16, torch.float32):
+        x = feats.to(dtype).clone().requires_grad_(True)
+        w = w0.clone().requires_grad_(True)
+        y = F.conv3d(SparseTensor(x, coords), w, 3)
+        y.F.float().sum().backward()
+        assert y.F.dtype == dtype and x.grad.dtype == dtype and w.grad.dtype == torch.float32
+        res[dtype] = (y.F.detach(), x.grad, w.grad)
+    (yh, gxh, gwh), (y32, gx32, gw32) = res[torch.bfloat16], res[torch.float32]
+    assert torch.equal(yh, y32.bfloat16()) and torch.equal(gxh, gx32.bfloat16()) and torch.equal(gwh, gw32)
+    assert float(y32.abs().max()) > 0 and float(gx32.abs().max()) > 0 and float(gw32.abs().max()) > 0
