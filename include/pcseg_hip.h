@@ -149,6 +149,30 @@ int pcs_point_merge_f32(const float *vox, const int32_t *idx8, const float *w8, 
 int pcs_point_merge_h(const void *vox, const int32_t *idx8, const float *w8, const void *lin, const double *stat,
                       const float *gamma, const float *beta, int64_t n, int32_t c, int32_t dtype, void *out,
                       uint32_t *mask, void *stream);
+/* K9 merged with the range and point branches of RPVNet (additive, still ABI v12):
+ *   R:pcseg/model/segmentor/fusion/rpvnet/rpvnet.py:648-651, 665-668, 683-686, 701-704
+ *   `z_next.F = voxel_to_point(x, z).F + range_to_point(r, pxpy) + ReLU(BatchNorm(Linear(z.F)))`:
+ *     out[i,j] = ( ( sum_{k<8, idx8[i,k] >= 0} w8[i,k] * vox[idx8[i,k], j] ) + sample(img[b_i, j], x_i, y_i) ) + third[i,j]
+ *   vox (m, c), lin / out (n, c) in the row dtype; img (B, c, H, W) ALWAYS fp32; pxpy (n, 3) fp32 rows (frame, x, y) as
+ *   pcs_range_sample_fwd_f32 takes them (bilinear, zero padding, align_corners = False; corners outside the image and frames
+ *   that are no integer in [0, B) contribute 0); idx8 / w8 as pcs_point_merge_* takes them.
+ *   bn mode  (stat != NULL; c % 32 == 0, mask != NULL): third = max(0, bn(lin)), and the ReLU bit mask is written with the
+ *             layout and meaning of pcs_point_merge_* / pcs_bn_apply_* (bit = [bn rounded to the storage type > 0]).
+ *   add mode (stat == NULL; gamma, beta, mask must be NULL, else PCS_EINVAL): third = lin, the finished term (widths that are
+ *             no multiple of 32).
+ *   All arithmetic in fp32 registers: the corners from zero in k = 0..7 order, the sample from zero in nw, ne, sw, se order,
+ *   acc += sample, the third term last, one rounding on the store: the fp32 result equals pcs_devoxelize_fwd_f32,
+ *   pcs_range_sample_fwd_f32, an fp32 add, pcs_bn_apply_f32 (relu), an fp32 add bit for bit. No backward entry: the gradient
+ *   of `out` is the dy of the BatchNorm backward passes, the gout of pcs_devoxelize_bwd_csr_* and (in fp32) of
+ *   pcs_range_sample_bwd_csr_f32.
+ *   c % 4 == 0 (fp32) / c % 8 == 0 (16 bits), bn mode c % 32 == 0, 16-byte-aligned vox / lin / out, else PCS_EUNSUPPORTED with
+ *   nothing launched; n == 0 is a no-op. _h: vox, lin, out in bf16 (dtype 1) or fp16 (dtype 2), any other dtype is PCS_EINVAL. */
+int pcs_range_point_merge_f32(const float *vox, const int32_t *idx8, const float *w8, const float *img, const float *pxpy,
+                              int32_t B, int32_t H, int32_t W, const float *lin, const double *stat, const float *gamma,
+                              const float *beta, int64_t n, int32_t c, float *out, uint32_t *mask, void *stream);
+int pcs_range_point_merge_h(const void *vox, const int32_t *idx8, const float *w8, const float *img, const float *pxpy,
+                            int32_t B, int32_t H, int32_t W, const void *lin, const double *stat, const float *gamma,
+                            const float *beta, int64_t n, int32_t c, int32_t dtype, void *out, uint32_t *mask, void *stream);
 
 /* voxel_to_point map in one pass (R:pcseg/model/segmentor/voxel/minkunet/utils.py:69-105: floor, cat, kernel_hash
  * over the 8 cell corners, hashquery, calc_ti_weights, two transposes): coords (n, coord_ld >= 4) float = x,y,z,..,batch

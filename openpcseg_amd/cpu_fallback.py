@@ -346,6 +346,49 @@ class TorchCpuBackend:
         y, mask = self.bn_apply(_cpu(lin, "input").float(), None, stat, gamma, beta, True, want_mask=True)
         return self.devoxelize_fwd(vox, idx8, w8) + y, mask
 
+    # -- range image -> points (csrc/rangesample.hip) and RPVNet's merge (csrc/rangemerge.hip), the same formulas in plain torch
+    @staticmethod
+    def _bilinear(img, pxpy):
+        """(n, c) samples of img (B, c, H, W) at pxpy (n, 3) = (frame, x, y): grid_sample(bilinear, zeros, align_corners=False)
+        arithmetic for every frame at once; a frame that is no integer in [0, B) samples nothing."""
+        b, c, h, w = img.shape
+        f = pxpy[:, 0]
+        fb = torch.nan_to_num(f, nan=-1.0).clamp(-1, b).long()
+        okf = (f >= 0) & (fb < b) & (fb.to(f.dtype) == f)
+        ix = ((pxpy[:, 1] + 1) * w - 1) / 2
+        iy = ((pxpy[:, 2] + 1) * h - 1) / 2
+        x0, y0 = torch.floor(ix), torch.floor(iy)
+        rows = img.permute(0, 2, 3, 1).reshape(b * h * w, c)
+        out = torch.zeros((pxpy.shape[0], c), dtype=img.dtype)
+        for dx, dy in ((0, 0), (1, 0), (0, 1), (1, 1)):   # nw, ne, sw, se
+            xx, yy = x0 + dx, y0 + dy
+            wt = ((x0 + 1 - ix) if dx == 0 else (ix - x0)) * ((y0 + 1 - iy) if dy == 0 else (iy - y0))
+            ok = okf & (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+            flat = torch.where(ok, (fb * h + yy.long()) * w + xx.long(), torch.zeros_like(fb))
+            out = out + torch.where(ok.unsqueeze(1), rows[flat] * wt.unsqueeze(1), torch.zeros((), dtype=img.dtype))
+        return out
+
+    def range_sample_fwd(self, img, pxpy):
+        return self._bilinear(_cpu(img, "feature_map").float(), _cpu(pxpy, "pxpy").float())
+
+    def range_sample_bwd(self, gout, pxpy, b, h, w):
+        g = _cpu(gout, "grad_output").float()
+        with torch.enable_grad():
+            img = torch.zeros((b, g.shape[1], h, w), dtype=torch.float32, requires_grad=True)
+            (gimg,) = torch.autograd.grad(self._bilinear(img, _cpu(pxpy, "pxpy").float()), img, g)
+        return gimg
+
+    def range_point_merge(self, vox, idx8, w8, img, pxpy, lin, stat, gamma, beta):
+        """(devoxelize(vox) + range_sample(img, pxpy)) + third, third = relu(bn(lin)) with its ReLU gate as bit-mask words (stat
+        given) or lin as it is (stat None) -> (out, mask or None)."""
+        a = self.devoxelize_fwd(vox, idx8, w8) + self.range_sample_fwd(img, pxpy)
+        if stat is None:
+            if gamma is not None or beta is not None:
+                raise ValueError("openpcseg_amd.cpu_fallback: range_point_merge in add mode (stat None) takes no gamma / beta")
+            return a + _cpu(lin, "input").float(), None
+        y, mask = self.bn_apply(_cpu(lin, "input").float(), None, stat, gamma, beta, True, want_mask=True)
+        return a + y, mask
+
     # -- ReconBlock gate of Cylinder3D (csrc/recongate.hip), the same formulas in plain torch
     @staticmethod
     def _recon_terms(a3, stat3, gamma3, beta3):

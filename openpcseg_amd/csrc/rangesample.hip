@@ -15,37 +15,13 @@
 //             scatter.hip); a workgroup owns 64 consecutive pixels of one image row x CH channels, sums w * gout[point] over each
 //             pixel's entries with 16-byte row loads into an LDS tile and writes it transposed -- every NCHW store a full 256-byte
 //             line, every element written exactly once (no memset).
-#include "pcs_common.h"
+#include "range_corners.h"   // Corners, frame_of, corners_of, sample_plane: shared with rangemerge.hip
 
 using namespace pcs;
 
 namespace {
 
 constexpr int RS_PT = 64;   // points (forward) / pixels (backward) per workgroup
-
-struct Corners {
-  int64_t off[4];   // offset of the corner inside one (H, W) plane, -1 = outside the image
-  float w[4];
-};
-
-// grid_sampler_compute_source_index + the four bilinear weights of torch's grid_sampler_2d (GridSampler.cuh), fp32 like there
-__device__ __forceinline__ Corners corners_of(float x, float y, int H, int W) {
-  const float ix = ((x + 1.f) * (float)W - 1.f) / 2.f;
-  const float iy = ((y + 1.f) * (float)H - 1.f) / 2.f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-  Corners c;
-  c.w[0] = ((float)x1 - ix) * ((float)y1 - iy);   // nw
-  c.w[1] = (ix - (float)x0) * ((float)y1 - iy);   // ne
-  c.w[2] = ((float)x1 - ix) * (iy - (float)y0);   // sw
-  c.w[3] = (ix - (float)x0) * (iy - (float)y0);   // se
-  const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-  c.off[0] = (vx0 && vy0) ? (int64_t)y0 * W + x0 : -1;
-  c.off[1] = (vx1 && vy0) ? (int64_t)y0 * W + x1 : -1;
-  c.off[2] = (vx0 && vy1) ? (int64_t)y1 * W + x0 : -1;
-  c.off[3] = (vx1 && vy1) ? (int64_t)y1 * W + x1 : -1;
-  return c;
-}
 
 template <int CH>
 __global__ void __launch_bounds__(256) range_sample_fwd_kernel(const float *__restrict__ img, const float *__restrict__ pxpy,
@@ -58,20 +34,14 @@ __global__ void __launch_bounds__(256) range_sample_fwd_kernel(const float *__re
   Corners cn;
   int b = -1;
   if (p < n) {
-    const float fb = pxpy[3 * p];
-    b = (int)fb;
-    if (!(fb >= 0.f) || b >= B || (float)b != fb) b = -1;   // a point of no frame samples nothing
+    b = frame_of(pxpy[3 * p], B);
     cn = corners_of(pxpy[3 * p + 1], pxpy[3 * p + 2], H, W);
   }
   const int64_t plane = (int64_t)H * W;
   for (int j = wid; j < CH; j += 4) {
     float v = 0.f;
-    if (b >= 0 && c0 + j < C) {
-      const float *pl = img + ((int64_t)b * C + c0 + j) * plane;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (cn.off[k] >= 0) v += pl[cn.off[k]] * cn.w[k];   // nw, ne, sw, se: torch's order of accumulation
-    }
+    if (b >= 0 && c0 + j < C)
+      v = sample_plane(img + ((int64_t)b * C + c0 + j) * plane, cn);
     tile[lane][j] = v;
   }
   __syncthreads();
@@ -87,9 +57,7 @@ __global__ void __launch_bounds__(256) range_sample_fwd_kernel(const float *__re
 __global__ void __launch_bounds__(256) range_corners_kernel(const float *__restrict__ pxpy, int64_t n, int B, int H, int W,
                                                             int64_t *__restrict__ keys, float *__restrict__ wts) {
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-    const float fb = pxpy[3 * p];
-    int b = (int)fb;
-    if (!(fb >= 0.f) || b >= B || (float)b != fb) b = -1;
+    const int b = frame_of(pxpy[3 * p], B);
     const Corners cn = corners_of(pxpy[3 * p + 1], pxpy[3 * p + 2], H, W);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

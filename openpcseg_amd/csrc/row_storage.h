@@ -1,7 +1,8 @@
 // Row storage of the memory-bound kernels: how a feature row sits in memory (fp32, bf16 or fp16), how a piece of it is
 // widened to fp32 registers and rounded ONCE on the store, and the row-tiled launch shape those kernels share. The only
 // definition of the bf16 rounding and of "the value as stored, read back" (the ReLU gate of the bit masks) in the tree:
-// the conv kernels (conv_common.h), norm.hip, pointvoxel.hip, pointmerge.hip, recongate.hip and scatter.hip include it.
+// the conv kernels (conv_common.h), norm.hip, pointvoxel.hip, pointmerge.hip, rangemerge.hip, recongate.hip and scatter.hip
+// include it.
 #pragma once
 #include "pcs_common.h"
 

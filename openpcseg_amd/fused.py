@@ -465,6 +465,134 @@ def point_merge(bn, lin_out, vox_feats, idx8, w8):
     return F_.spdevoxelize(vox_feats, idx8, w8) + be.bn_apply(lin_out.contiguous(), None, stat, bn.weight, bn.bias, True)
 
 
+# ---- RPVNet's range-point-voxel merge ------------------------------------------------------------------------------------
+_ROW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _range_merge_enabled():
+    import os
+    return os.environ.get("PCS_RANGE_MERGE", "1") != "0"   # A/B switch: 0 = the literal sequence of the existing passes
+
+
+def _grid_sample_rows(feature_map, pxpy, grid_sample_mode="bilinear"):
+    """range_to_point for inputs the kernels do not serve (host tensors, other sampling modes): torch's grid_sample frame by
+    frame, rows grouped by ascending frame (what R:pcseg/model/segmentor/fusion/rpvnet/rpvnet.py:31-51 computes)."""
+    rows = []
+    for b in range(feature_map.shape[0]):
+        grid = pxpy[pxpy[:, 0] == b][:, 1:].to(feature_map.dtype).reshape(1, 1, -1, 2)
+        s = torch.nn.functional.grid_sample(feature_map[b:b + 1], grid, mode=grid_sample_mode, padding_mode="zeros", align_corners=False)
+        rows.append(s.reshape(feature_map.shape[1], -1).t())
+    return torch.cat(rows, dim=0)
+
+
+class _RangePointMerge(Function):
+    """out = (devoxelize(vox) + range_sample(img, pxpy)) + third in ONE kernel (csrc/rangemerge.hip;
+    R:pcseg/model/segmentor/fusion/rpvnet/rpvnet.py:648-651, 665-668, 683-686, 701-704). bn_mode: third = relu(bn(lin)) with
+    training-mode statistics -- statistics, all-reduce and running statistics as `_FusedBN`, the gate the bit mask the kernel
+    wrote; otherwise third = lin (the finished term). No backward kernel: the gradient of `out` is the dy of the BatchNorm
+    backward passes (bn mode; else lin's gradient itself), the gout of the devoxelize backward through the CSR cached on the
+    corner map, and the gout of the range_sample backward through the pixel CSR cached on pxpy."""
+
+    @staticmethod
+    def forward(ctx, lin, vox, idx8, w8, img, pxpy, weight, bias, running_mean, running_var, eps, momentum, sync, bn_mode):
+        be = native.backend()
+        lin, vox = lin.contiguous(), vox.contiguous()
+        idx8, w8 = idx8.contiguous().int(), w8.contiguous().float()
+        img32, pxpy = img.float().contiguous(), pxpy.float().contiguous()   # the image is sampled in fp32 (rangelib._RangeToPoint)
+        if bn_mode:
+            stat, count, count_dev = _train_stat(be, lin, None, sync, eps, momentum, running_mean, running_var)
+            out, mask = be.range_point_merge(vox, idx8, w8, img32, pxpy, lin, stat, weight, bias)
+            ctx.save_for_backward(lin, mask, stat, weight, count_dev)
+            ctx.cfg = (count, sync)
+        else:
+            out, _ = be.range_point_merge(vox, idx8, w8, img32, pxpy, lin, None, None, None)
+        ctx.bn_mode = bn_mode
+        ctx.maps = (idx8, w8, vox.shape[0], vox.dtype, pxpy, tuple(img.shape), img.dtype, lin.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import rangelib
+        be = native.backend()
+        g = g.contiguous()
+        idx8, w8, m, vox_dtype, pxpy, (b, c, h, w), img_dtype, lin_dtype = ctx.maps
+        dlin = dvox = dimg = dw = db = None
+        if ctx.bn_mode:
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[6] or ctx.needs_input_grad[7]:
+                dlin, dw, db = _bn_backward(ctx.cfg, ctx.saved_tensors, g)
+        elif ctx.needs_input_grad[0]:
+            dlin = g if g.dtype == lin_dtype else g.to(lin_dtype)
+        if ctx.needs_input_grad[1]:
+            dvox = be.devoxelize_bwd(g, idx8, w8, m)
+            if dvox.dtype != vox_dtype:
+                dvox = dvox.to(vox_dtype)
+        if ctx.needs_input_grad[4]:
+            if rangelib._PENDING:
+                rangelib.verify_pending()
+            dimg = be.range_sample_bwd(g.float().contiguous(), pxpy, b, h, w)
+            if dimg.dtype != img_dtype:
+                dimg = dimg.to(img_dtype)
+        return dlin, dvox, None, None, dimg, None, dw, db, None, None, None, None, None, None
+
+
+def _range_merge_kernel_serves(be, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode):
+    """The inputs csrc/rangemerge.hip (or the backend's restatement of it) takes; everything else is the literal sequence."""
+    if not (_range_merge_enabled() and hasattr(be, "range_point_merge") and grid_sample_mode == "bilinear"):
+        return False
+    cpu = getattr(be, "name", "") == "torch-cpu"
+    tensors = (lin_out, vox_feats, idx8, w8, feature_map, pxpy)
+    if not (all(not t.is_cuda for t in tensors) if cpu else all(t.is_cuda for t in tensors)):
+        return False   # host tensors on the HIP backend, or a mixture
+    if lin_out.dim() != 2 or vox_feats.dim() != 2 or feature_map.dim() != 4 or pxpy.dim() != 2 or pxpy.shape[1] != 3:
+        return False
+    n, c = lin_out.shape
+    if n == 0 or vox_feats.shape[1] != c or feature_map.shape[1] != c or pxpy.shape[0] != n or not pxpy.is_floating_point():
+        return False
+    if lin_out.dtype not in _ROW_DTYPES or lin_out.dtype != vox_feats.dtype or feature_map.dtype not in _ROW_DTYPES:
+        return False   # row dtypes that differ: the literal sequence promotes them as torch does
+    if c % (4 if lin_out.dtype == torch.float32 else 8):
+        return False   # the widths the kernel refuses (rows move in 16-byte pieces)
+    from . import rangelib
+    return rangelib._frames_in_order(pxpy, feature_map.shape[0])
+
+
+def range_point_merge(bn, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode="bilinear"):
+    """`spdevoxelize(vox_feats, idx8, w8) + range_to_point(feature_map, pxpy) + relu(bn(lin_out))`: RPVNet's merge of its voxel,
+    range and point branches. bn: a FusedBatchNorm (or any BatchNorm1d-shaped module); lin_out (N, C) the point Linear's output;
+    vox_feats (M, C); idx8 / w8 (N, 8) the points' corner map; feature_map (B, C, H, W); pxpy (N, 3) = (frame, x, y), the frames
+    non-decreasing integers in [0, B) (`rangelib.range_to_point`'s contract, verified the same way). One kernel when the backend
+    has `range_point_merge` and serves the inputs: BatchNorm apply, ReLU and mask inside it when C % 32 == 0, otherwise the
+    fused BatchNorm pass first and the kernel adds its output. PCS_RANGE_MERGE=0, a backend without the op, host tensors on the
+    HIP backend, other sampling modes, differing row dtypes and refused widths take the literal sequence of the existing
+    passes -- same function, and in fp32 the same bits. Eval mode: the running statistics."""
+    from . import functional as F_
+    from . import rangelib
+    be = native.backend()
+    c = lin_out.shape[1]
+    sync = _bn_sync(bn)
+    fused = _range_merge_kernel_serves(be, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode)
+    bn_mode = fused and c % 32 == 0
+    if bn.training:
+        if not getattr(bn, "counted_by_parent", False):
+            bn.num_batches_tracked += 1
+        if bn_mode:
+            return _RangePointMerge.apply(lin_out, vox_feats, idx8, w8, feature_map, pxpy, bn.weight, bn.bias, bn.running_mean,
+                                          bn.running_var, bn.eps, bn.momentum, sync, True)
+        y = _FusedBN.apply(lin_out, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, True,
+                           sync, None, None, None, None)
+    else:
+        stat = _running_stat(bn)
+        if bn_mode:
+            return be.range_point_merge(vox_feats.contiguous(), idx8.contiguous().int(), w8.contiguous().float(),
+                                        feature_map.float().contiguous(), pxpy.float().contiguous(), lin_out.contiguous(),
+                                        stat, bn.weight, bn.bias)[0]
+        y = be.bn_apply(lin_out.contiguous(), None, stat, bn.weight, bn.bias, True)
+    if fused:
+        return _RangePointMerge.apply(y, vox_feats, idx8, w8, feature_map, pxpy, None, None, None, None, None, None, False, False)
+    r = rangelib.range_to_point(feature_map, pxpy, grid_sample_mode, fallback=_grid_sample_rows)
+    return F_.spdevoxelize(vox_feats, idx8, w8) + r + y
+
+
 # ---- Cylinder3D's ReconBlock gate ------------------------------------------------------------------------------------------
 def _gate_enabled():
     import os

@@ -169,12 +169,11 @@ class _SequentialForward:
 
 
 def freeze(model):
-    """Fold every BatchNorm of the package's own blocks (workloads.minkunet and workloads.spvcnn: the stem, ConvBlock, ResBlock
+    """Fold every BatchNorm of the package's own blocks (workloads.minkunet, workloads.spvcnn and workloads.rpvnet: the stem, ConvBlock, ResBlock
     incl. its 1x1x1 downsample) and of plain `nn.Sequential(Conv3d, BatchNorm [, ReLU], ...)` chains into its convolution. Anything else is
     left alone. -> {"folded": number of conv + BatchNorm pairs, "skipped": [names of BatchNorm modules that keep running]}.
     Changes no parameter, buffer or state_dict entry; takes effect only in eval mode with grad mode off."""
     from .workloads.minkunet import ConvBlock, MinkUNet, ResBlock
-    from .workloads.spvcnn import SPVCNN
     unfreeze(model)
     claimed, folded = set(), 0
 
@@ -202,9 +201,10 @@ def freeze(model):
         elif isinstance(m, MinkUNet):
             st = m.stem
             if _foldable(st[0], st[1]) and _foldable(st[3], st[4]):
-                # SPVCNN (the same trunk): its classifier reads the merged point features, not devoxelised voxel scores, and the
-                # BatchNorms of its point MLPs keep running (fused.point_merge with the running statistics): they end up in `skipped`
-                commuted = isinstance(m.classifier[0], FusedLinear) and not isinstance(m, SPVCNN)
+                # SPVCNN and RPVNet (the same trunk, `point_branch`): the classifier reads the merged point features, not devoxelised
+                # voxel scores, and the BatchNorms of the point MLPs keep running (fused.point_merge / fused.range_point_merge with
+                # the running statistics): they end up in `skipped`
+                commuted = isinstance(m.classifier[0], FusedLinear) and not m.point_branch
                 rec = {"stem": [FoldedConv(st[0], st[1], True), FoldedConv(st[3], st[4], True)],
                        "classifier": FoldedLinear(m.classifier[0]) if commuted else None}
                 claim(m, rec, [(st[0], st[1]), (st[3], st[4])])

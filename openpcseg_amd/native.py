@@ -38,6 +38,9 @@ SIGNATURES = {
     "pcs_devoxelize_bwd_csr_h": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
     "pcs_point_merge_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P]),
     "pcs_point_merge_h": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P]),
+    "pcs_range_point_merge_f32": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P]),
+    "pcs_range_point_merge_h": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int64, c_int32, c_int32,
+                                          _P, _P, _P]),
     "pcs_recon_gate_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P]),
     "pcs_recon_gate_h": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P]),
     "pcs_recon_gate_bwd_stats_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, c_int64, _P]),
@@ -472,6 +475,34 @@ class HipBackend:
         mask = torch.empty((n, c // 32), dtype=torch.int32, device=lin.device)
         self._twin("pcs_point_merge", vcode, [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(lin), _ptr(stat), _ptr(gamma), _ptr(beta), n, c],
                    [_ptr(out), _ptr(mask), _stream()])
+        return out, mask
+
+    def range_point_merge(self, vox, idx8, w8, img, pxpy, lin, stat, gamma, beta):
+        """RPVNet's range-point-voxel merge in one pass (csrc/rangemerge.hip): out = (devoxelize(vox) + range_sample(img, pxpy)) +
+        third -> (out (n, c), mask). stat given (bn mode, c % 32 == 0): third = relu(bn(lin)) and mask (n, c / 32) int32 is its
+        ReLU gate as bn_apply's bit mask. stat None (add mode; gamma and beta must be None): third = lin as it is, mask None.
+        vox and lin in one row dtype (fp32, bf16 or fp16), out in it; img (B, c, H, W) and pxpy (n, 3) fp32."""
+        vox, vcode = self._pv_feats(vox, "feats")
+        lin, lcode = self._pv_feats(lin, "input")
+        if vcode != lcode:
+            raise TypeError("openpcseg_amd: range_point_merge takes vox and lin in one dtype, got %s and %s" % (vox.dtype, lin.dtype))
+        idx8 = _dev(idx8, "coords", torch.int32)
+        w8 = _dev(w8, "weights", torch.float32)
+        img = _dev(img, "feature_map", torch.float32)
+        pxpy = _dev(pxpy, "pxpy", torch.float32)
+        n, c = lin.shape
+        if (vox.dim() != 2 or vox.shape[1] != c or idx8.shape != (n, 8) or w8.shape != (n, 8) or img.dim() != 4 or
+                img.shape[1] != c or pxpy.shape != (n, 3)):
+            raise ValueError("openpcseg_amd: range_point_merge takes vox (m, c), lin (n, c), idx8 / w8 (n, 8), img (B, c, H, W), "
+                             "pxpy (n, 3); got %s %s %s %s %s %s" % (tuple(vox.shape), tuple(lin.shape), tuple(idx8.shape),
+                                                                    tuple(w8.shape), tuple(img.shape), tuple(pxpy.shape)))
+        if stat is None and (gamma is not None or beta is not None):
+            raise ValueError("openpcseg_amd: range_point_merge in add mode (stat None) takes no gamma / beta")
+        b, _, h, w = img.shape
+        out = torch.empty((n, c), dtype=lin.dtype, device=lin.device)
+        mask = torch.empty((n, c // 32), dtype=torch.int32, device=lin.device) if stat is not None else None
+        self._twin("pcs_range_point_merge", vcode, [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(img), _ptr(pxpy), b, h, w, _ptr(lin),
+                                                    _ptr(stat), _ptr(gamma), _ptr(beta), n, c], [_ptr(out), _ptr(mask), _stream()])
         return out, mask
 
     def devoxelize_bwd(self, gout, idx8, w8, m):

@@ -122,6 +122,10 @@ def _res_stack(cin, cout, n, dist):
 
 
 class MinkUNet(nn.Module):
+    # True in the workloads whose classifier reads point features that a point branch merged (SPVCNN, RPVNet): the classifier
+    # then does not commute with the devoxelisation (openpcseg_amd.freeze prepares no voxel-side classifier for them)
+    point_branch = False
+
     def __init__(self, num_class=20, in_dim=4, num_layer=MK34_LAYERS, planes=PLANES, cr=1.0,
                  pres=0.05, vres=0.05, dist=False, ignore_label=0, label_smoothing=0.1, dropout=0.0):
         super().__init__()

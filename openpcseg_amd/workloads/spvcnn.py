@@ -24,6 +24,8 @@ from .pointvoxel import initial_voxelize, point_maps, point_to_voxel, voxel_to_p
 
 
 class SPVCNN(MinkUNet):
+    point_branch = True
+
     def __init__(self, num_class=20, in_dim=4, num_layer=MK18_LAYERS, planes=PLANES, cr=1.0,
                  pres=0.05, vres=0.05, dist=False, ignore_label=0, label_smoothing=0.1, dropout=0.0):
         super().__init__(num_class=num_class, in_dim=in_dim, num_layer=num_layer, planes=planes, cr=cr, pres=pres,
