@@ -70,7 +70,7 @@ from torch import nn
 
 from . import modules as spnn
 from . import native
-from .fused import _FusedBN
+from .fused import bn_forward, bn_rows
 from .sparse import SparseTensor
 
 __all__ = ["fuse", "unfuse", "restore_glue", "install_auto_fuse", "uninstall_auto_fuse", "PendingBatchNorm"]
@@ -109,37 +109,6 @@ def _quiet(m):
 def _backend_fuses(feats):
     be = native.backend()
     return hasattr(be, "bn_apply") and feats.dim() == 2 and feats.dtype in (torch.float32, torch.bfloat16, torch.float16)
-
-
-def bn_forward(bn, input, residual=None, relu=False, cat_with=None, in_slope=None):
-    """`relu(bn(input) + residual)` [concatenated with cat_with] as one fused pass, on the parameters / buffers of the
-    caller's own BatchNorm module (nn.BatchNorm1d semantics in train and eval mode; nn.SyncBatchNorm: the statistics are
-    all-reduced over the default process group)."""
-    x = input.feats
-    r = residual.feats if isinstance(residual, SparseTensor) else residual
-    tail = cat_with.feats if isinstance(cat_with, SparseTensor) else cat_with
-    if tail is not None and (x.shape[1] % 4 or tail.shape[1] % 4 or tail.shape[0] != x.shape[0] or tail.dtype != x.dtype):
-        y = bn_forward(bn, input, residual=residual, relu=relu)
-        return y._like(torch.cat([y.feats, tail.to(y.feats.dtype)], dim=1))
-    if r is not None and r.dtype != x.dtype:
-        r = r.to(x.dtype)
-    if bn.training:
-        if bn.__dict__.get("_pcs_bumped", False):
-            bn.__dict__["_pcs_bumped"] = False   # the root model's pre-forward hook already counted this step (one _foreach_add_)
-        else:
-            bn.num_batches_tracked.add_(1)
-        pre = getattr(input, "bn_sums", None)
-        if pre is not None:
-            sums, of, ver = pre
-            pre = sums if (of is x and x._version == ver) else None
-        y = _FusedBN.apply(x, r, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu,
-                           isinstance(bn, nn.SyncBatchNorm), input.cmaps, input.stride, pre, tail, in_slope)
-    else:
-        inv = torch.rsqrt(bn.running_var.double() + bn.eps)
-        stat = torch.cat([bn.running_mean.double(), inv]).contiguous()
-        y = native.backend().bn_apply(x.contiguous(), r.contiguous() if r is not None else None, stat, bn.weight, bn.bias, relu,
-                                      tail=tail.contiguous() if tail is not None else None)
-    return input._like(y)
 
 
 class PendingBatchNorm(SparseTensor):
@@ -277,16 +246,7 @@ def _dense_step(lin, bn, act, x):
 
 
 def _dense_bn_apply(bn, h, relu):
-    if bn.training:
-        if bn.__dict__.get("_pcs_bumped", False):
-            bn.__dict__["_pcs_bumped"] = False
-        else:
-            bn.num_batches_tracked.add_(1)
-        return _FusedBN.apply(h, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu,
-                              isinstance(bn, nn.SyncBatchNorm), None, None, None, None)
-    inv = torch.rsqrt(bn.running_var.double() + bn.eps)
-    stat = torch.cat([bn.running_mean.double(), inv]).contiguous()
-    return native.backend().bn_apply(h.contiguous(), None, stat, bn.weight, bn.bias, relu)
+    return bn_rows(bn, h, relu=relu)
 
 
 def _rows_ok(x):

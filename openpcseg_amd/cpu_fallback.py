@@ -341,9 +341,13 @@ class TorchCpuBackend:
             y = torch.cat([y, tail], dim=1)
         return (y, mask) if want_mask else y
 
+    def _bn_term(self, lin, stat, gamma, beta):
+        """relu(bn(lin)) in fp32 and its ReLU gate as bit-mask words: the BatchNorm term of the two merges."""
+        return self.bn_apply(_cpu(lin, "input").float(), None, stat, gamma, beta, True, want_mask=True)
+
     def point_merge(self, vox, idx8, w8, lin, stat, gamma, beta):
         """devoxelize(vox) + relu(bn(lin)) and the ReLU gate of the BatchNorm term as bit-mask words (csrc/pointmerge.hip)."""
-        y, mask = self.bn_apply(_cpu(lin, "input").float(), None, stat, gamma, beta, True, want_mask=True)
+        y, mask = self._bn_term(lin, stat, gamma, beta)
         return self.devoxelize_fwd(vox, idx8, w8) + y, mask
 
     # -- range image -> points (csrc/rangesample.hip) and RPVNet's merge (csrc/rangemerge.hip), the same formulas in plain torch
@@ -386,7 +390,7 @@ class TorchCpuBackend:
             if gamma is not None or beta is not None:
                 raise ValueError("openpcseg_amd.cpu_fallback: range_point_merge in add mode (stat None) takes no gamma / beta")
             return a + _cpu(lin, "input").float(), None
-        y, mask = self.bn_apply(_cpu(lin, "input").float(), None, stat, gamma, beta, True, want_mask=True)
+        y, mask = self._bn_term(lin, stat, gamma, beta)
         return a + y, mask
 
     # -- ReconBlock gate of Cylinder3D (csrc/recongate.hip), the same formulas in plain torch

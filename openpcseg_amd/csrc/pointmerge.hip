@@ -5,13 +5,14 @@
 // Here the Linear output is read once and the merged rows are written once; the voxel rows are gathered as K9 gathers them.
 //     out[i, j]       = ( sum over k = 0..7 with idx8[i, k] >= 0 of w8[i, k] * vox[idx8[i, k], j] ) + max(0, bn(lin[i, j]))
 //     mask bit (i, j) = [ bn(lin[i, j]) rounded to the storage type > 0 ]          word i * (c / 32) + j / 32, bit j % 32 (bn_apply_kernel's layout)
-// Order of the arithmetic: the corners in fp32 registers from zero in k = 0..7 order (devoxelize_fwd_kernel), bn(x) with
-// the expression of bn_apply_kernel (norm.hip), the BatchNorm term added last, ONE rounding on the store. In fp32 that is
-// bit for bit what the three separate kernels give; in 16 bits it is one rounding where they have three.
+// Order of the arithmetic (the pieces: bn_piece.h): the corners in fp32 registers from zero in k = 0..7 order
+// (devoxelize_fwd_kernel), bn(x) with the expression of bn_apply_kernel (norm.hip), the BatchNorm term added last, ONE
+// rounding on the store. In fp32 that is bit for bit what the three separate kernels give; in 16 bits it is one rounding
+// where they have three.
 // Launch shape of the K9 kernels: a 256-thread workgroup covers 256/TX points, TX lanes x 16 bytes per row, grid-stride
 // over the points; the corner indices and weights of a point are loaded once per pass of the lane row (one pass up to
 // c = 256 in fp32, 512 in 16 bits). No LDS, no atomics; every output row and mask word is written exactly once.
-#include "row_storage.h"
+#include "bn_piece.h"
 
 using namespace pcs;
 
@@ -27,46 +28,19 @@ __global__ void __launch_bounds__(256) point_merge_kernel(const uint4 *__restric
   constexpr int V = Piece<ET>::V;
   constexpr int LPW = 32 / V;  // lanes per mask word: 8 (fp32) or 4 (16 bits); cv % LPW == 0 because c % 32 == 0
   for (int j = threadIdx.x; j < cv; j += blockDim.x) {
-    float sc[V], sh[V];  // bn(x) = fma(x, sc, sh), as bn_apply_kernel forms it
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      const int ch = j * V + q;
-      const float invstd = (float)stat[c + ch], mean = (float)stat[ch];
-      sc[q] = invstd * (gamma ? gamma[ch] : 1.f);
-      sh[q] = (beta ? beta[ch] : 0.f) - mean * sc[q];
-    }
+    float sc[V], sh[V];
+    bn_coeffs<V>(stat, gamma, beta, c, j * V, sc, sh);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.y + threadIdx.y; i < n; i += (int64_t)gridDim.x * blockDim.y) {
       const uint4 lr = lin[i * cv + j];  // streamed row first: in flight while the corners are gathered
-      int32_t id[8];
-      float w[8];
+      Acc<V> acc = gather_corners<ET>(vox, idx8, w8, i, cv, j);
+      Acc<V> t = widen(ET{}, lr);
+      const unsigned bits = bn_relu_gate<ET>(t, sc, sh);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) { id[k] = idx8[i * 8 + k]; w[k] = w8[i * 8 + k]; }
-      Acc<V> acc;
-#pragma unroll
-      for (int q = 0; q < V; ++q) acc.f[q] = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (id[k] >= 0) {
-          const Acc<V> f = widen(ET{}, vox[(int64_t)id[k] * cv + j]);
-#pragma unroll
-          for (int q = 0; q < V; ++q) acc.f[q] = fmaf(w[k], f.f[q], acc.f[q]);
-        }
-      }
-      const Acc<V> x = widen(ET{}, lr);
-      unsigned bits = 0;
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        float t = fmaf(x.f[q], sc[q], sh[q]);
-        if (t < 0.f) t = 0.f;
-        bits |= (stored(ET{}, t) > 0.f ? 1u : 0u) << q;  // pcs_bn_apply_*'s bit; the sum below keeps its one rounding
-        acc.f[q] += t;
-      }
+      for (int q = 0; q < V; ++q) acc.f[q] += t.f[q];
       out[i * cv + j] = narrow(ET{}, acc);
       // LPW consecutive lanes of one row make one mask word. The groups are aligned in the wave (blockDim.x is a power
       // of two >= LPW) and all their lanes take the same trips of both loops (cv % LPW == 0).
-      unsigned m = bits << (V * (j & (LPW - 1)));
-#pragma unroll
-      for (int o = 1; o < LPW; o <<= 1) m |= __shfl_xor(m, o, 64);
+      const unsigned m = mask_word<V>(bits, j);
       if ((j & (LPW - 1)) == 0) mask[i * (c >> 5) + j / LPW] = m;
     }
   }

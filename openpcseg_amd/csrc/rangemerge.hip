@@ -8,10 +8,11 @@
 //     third (bn mode)  = max(0, bn(lin[i, j]))     stat != NULL; mask bit (i, j) = [ bn rounded to the storage type > 0 ],
 //                                                  word i * (c / 32) + j / 32, bit j % 32 (bn_apply_kernel's layout)
 //     third (add mode) = lin[i, j]                 stat == NULL: lin already holds the finished term (widths that are no multiple of 32)
-// Order of the arithmetic, all in fp32 registers: the corners from zero in k = 0..7 order by fmaf (devoxelize_fwd_kernel), the
-// bilinear sample from zero in nw, ne, sw, se order (sample_plane of range_corners.h, the expression range_sample_fwd_kernel
-// compiles), acc += sample, bn(x) with the expression of bn_apply_kernel (norm.hip), the third term added last, ONE rounding
-// on the store. In fp32 that is bit for bit pcs_devoxelize_fwd_f32, pcs_range_sample_fwd_f32, an add, pcs_bn_apply_f32, an add.
+// Order of the arithmetic (the pieces: bn_piece.h), all in fp32 registers: the corners from zero in k = 0..7 order by fmaf
+// (devoxelize_fwd_kernel), the bilinear sample from zero in nw, ne, sw, se order (sample_plane of range_corners.h, the expression
+// range_sample_fwd_kernel compiles), acc += sample, bn(x) with the expression of bn_apply_kernel (norm.hip), the third term added
+// last, ONE rounding on the store. In fp32 that is bit for bit pcs_devoxelize_fwd_f32, pcs_range_sample_fwd_f32, an add,
+// pcs_bn_apply_f32, an add.
 // Launch shape: the two kernels composed. A 256-thread workgroup owns 64 consecutive points x a chunk of CH channels.
 //   phase 1: wave w samples channels w, w + 4, ... of the chunk with the lanes over the points (corner offsets and weights in
 //            registers, every plane read a 4-byte gather out of L2) into a padded LDS tile [point][CH + 4];
@@ -20,7 +21,7 @@
 //            word by __shfl_xor; the shuffles sit outside every `ch < c` branch (a chunk's tail has inactive pieces).
 // No atomics; every output element and mask word is written exactly once.
 #include "range_corners.h"
-#include "row_storage.h"
+#include "bn_piece.h"
 
 using namespace pcs;
 
@@ -64,15 +65,8 @@ __global__ void __launch_bounds__(256) range_point_merge_kernel(const uint4 *__r
   const int pl = threadIdx.x % PV;   // the same piece in every trip (256 % PV == 0)
   const int ch = c0 + V * pl;        // c % V == 0: a piece lies inside the row or outside it, never across its end
   const int j = ch / V;              // piece of the whole row
-  float sc[V], sh[V];                // bn(x) = fma(x, sc, sh), as bn_apply_kernel forms it
-  if (BN && ch < c) {
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      const float invstd = (float)stat[c + ch + q], mean = (float)stat[ch + q];
-      sc[q] = invstd * (gamma ? gamma[ch + q] : 1.f);
-      sh[q] = (beta ? beta[ch + q] : 0.f) - mean * sc[q];
-    }
-  }
+  float sc[V], sh[V];
+  if (BN && ch < c) bn_coeffs<V>(stat, gamma, beta, c, ch, sc, sh);
   for (int t = threadIdx.x; t < RM_PT * PV; t += 256) {
     const int r = t / PV;
     const int64_t i = p0 + r;
@@ -80,36 +74,19 @@ __global__ void __launch_bounds__(256) range_point_merge_kernel(const uint4 *__r
     unsigned bits = 0;
     if (live) {
       const uint4 lr = lin[i * cv + j];  // streamed row first: in flight while the corners are gathered
-      int32_t id[8];
-      float w[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { id[k] = idx8[i * 8 + k]; w[k] = w8[i * 8 + k]; }
-      Acc<V> acc;
-      azero(acc);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (id[k] >= 0) add_mul(acc, w[k], widen(ET{}, vox[(int64_t)id[k] * cv + j]));
-      }
+      Acc<V> acc = gather_corners<ET>(vox, idx8, w8, i, cv, j);
 #pragma unroll
       for (int q = 0; q < V; ++q) acc.f[q] += tile[r][V * pl + q];
-      const Acc<V> x = widen(ET{}, lr);
+      Acc<V> y = widen(ET{}, lr);
+      if (BN) bits = bn_relu_gate<ET>(y, sc, sh);
 #pragma unroll
-      for (int q = 0; q < V; ++q) {
-        float y = x.f[q];
-        if (BN) {
-          y = fmaf(x.f[q], sc[q], sh[q]);
-          if (y < 0.f) y = 0.f;
-          bits |= (stored(ET{}, y) > 0.f ? 1u : 0u) << q;  // pcs_bn_apply_*'s bit; the sum below keeps its one rounding
-        }
-        acc.f[q] += y;
-      }
+      for (int q = 0; q < V; ++q) acc.f[q] += y.f[q];
       out[i * cv + j] = narrow(ET{}, acc);
     }
     if (BN) {
-      // LPW consecutive lanes of one row make one mask word; a lane outside the row or past n contributes no bit
-      unsigned m = bits << (V * (pl & (LPW - 1)));
-#pragma unroll
-      for (int o = 1; o < LPW; o <<= 1) m |= __shfl_xor(m, o, 64);
+      // LPW consecutive lanes of one row make one mask word; a lane outside the row or past n contributes no bit. The call
+      // shuffles: it stays here, outside `live`
+      const unsigned m = mask_word<V>(bits, pl);
       if (live && (pl & (LPW - 1)) == 0) mask[i * (c >> 5) + (ch >> 5)] = m;   // c % 32 == 0: a word of the row is whole
     }
   }

@@ -94,17 +94,82 @@ def _train_stat(be, x, pre, sync, eps, momentum, running_mean, running_var):
     return stat, count, count_dev
 
 
+def _bn_sync(bn):
+    return bool(getattr(bn, "sync", isinstance(bn, nn.SyncBatchNorm)))
+
+
+def _running_stat(bn):
+    """Eval mode's [mean | invstd] double vector, as the apply kernels read it."""
+    inv = torch.rsqrt(bn.running_var.double() + bn.eps)
+    return torch.cat([bn.running_mean.double(), inv]).contiguous()
+
+
+def _handed_over(t):
+    """(features, statistics the producing convolution handed over for exactly this tensor or None) of a SparseTensor / tensor.
+    The statistics are used only for the very tensor they describe (same object, untouched since): `x.F = dropout(x.F)`,
+    `x.feats += b` in between fall back to the statistics pass."""
+    if not isinstance(t, SparseTensor):
+        return t, None
+    x, pre = t.feats, getattr(t, "bn_sums", None)
+    if pre is not None:
+        sums, of, ver = pre
+        pre = sums if (of is x and x._version == ver) else None
+    return x, pre
+
+
+def _count_step(bn):
+    """One training step on bn's num_batches_tracked, unless somebody counted it already: a model that bumps all its counters
+    with one _foreach_add_ per step marks its layers `counted_by_parent` for good; block_fusion's root pre-forward hook marks
+    the layers it counted `_pcs_bumped` for this one step, and the mark is taken off here."""
+    if bn.__dict__.get("_pcs_bumped", False):
+        bn.__dict__["_pcs_bumped"] = False
+    elif not getattr(bn, "counted_by_parent", False):
+        bn.num_batches_tracked.add_(1)
+
+
+def _reduced(local, sync):
+    """The backward sums the apply pass divides by the global count: the local ones, or in sync mode a copy all-reduced
+    (the local ones stay as they are: DDP averages the parameter gradients formed from them)."""
+    if not _syncing(sync):
+        return local
+    sums = local.clone()
+    dist.all_reduce(sums, group=_stats_group())
+    return sums
+
+
+def _param_sums(local, dtype):
+    """The local backward sums in the parameters' dtype (the HIP reduction leaves them in fp32 as well; else one cast)."""
+    lw = getattr(local, "_pcs_f32", None)
+    return lw if lw is not None and lw.dtype == dtype else local.to(dtype)
+
+
+def _bn_backward(cfg, saved, dy, relu=True, has_res=False, in_slope=None):
+    """The two backward passes of a BatchNorm [+ residual] [+ ReLU] -> (dx, dres, dweight, dbias). cfg = (count, sync);
+    saved = (x, gate, stat, weight, count_dev); dy contiguous, or the left columns of a wider buffer (read through its row stride)."""
+    be = native.backend()
+    x, gate, stat, weight, count_dev = saved
+    count, sync = cfg
+    c = x.shape[1]
+    local = be.bn_bwd_stats(dy, x, gate, stat, relu)
+    kw = {} if in_slope is None else {"in_slope": in_slope}
+    dx, dres = be.bn_bwd_apply(dy, x, gate, stat, _reduced(local, sync), count, weight, relu, has_res, count_dev=count_dev, **kw)
+    dw = db = None
+    if weight is not None:
+        lw = _param_sums(local, weight.dtype)
+        dw, db = lw[c:], lw[:c]
+    return dx, dres, dw, db
+
+
 class _FusedBN(Function):
     """Feature tensors may be fp32, bf16 or fp16 (mixed precision: the half convolutions hand on halfs); statistics,
     scale / shift and running stats are fp32 / double whatever the storage format."""
 
     @staticmethod
-    def forward(ctx, x, res, weight, bias, running_mean, running_var, eps, momentum, relu, sync, cache, level, pre=None,
-                tail=None, in_slope=None):
+    def forward(ctx, x, res, weight, bias, running_mean, running_var, eps, momentum, relu, sync, pre=None, tail=None, in_slope=None):
         """in_slope: x is the output of a LeakyReLU that the producing convolution applied in its write-back; the gradient this
         node returns for x is then the gradient of the PRE-activation (the derivative rides in the backward apply pass), which is
-        what that convolution's backward expects (functional._SparseConv, act_slope)."""
-        """tail (n, ct): concat fusion -- the output is cat([bn(x), tail], 1), the BN result written straight into the left
+        what that convolution's backward expects (functional._SparseConv, act_slope).
+        tail (n, ct): concat fusion -- the output is cat([bn(x), tail], 1), the BN result written straight into the left
         columns and `tail` copied to the right ones by the apply launch (no torch.cat pass); backward reads its dy out of
         the gradient of that buffer through a row stride and hands the right columns on as tail's gradient."""
         be = native.backend()
@@ -119,43 +184,59 @@ class _FusedBN(Function):
             y = be.bn_apply(x, res, stat, weight, bias, relu, tail=tail)
             gate = (y if tail is None else y[:, :c].contiguous()) if relu else None
         ctx.save_for_backward(x, gate, stat, weight, count_dev)
-        ctx.cfg = (count, relu, sync, res is not None, tail is not None)
-        ctx.in_slope = in_slope
+        ctx.cfg = (count, sync)
+        ctx.flags = (relu, res is not None, tail is not None, in_slope)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        be = native.backend()
-        x, gate, stat, weight, count_dev = ctx.saved_tensors
-        count, relu, sync, has_res, has_tail = ctx.cfg
-        c = x.shape[1]
+        relu, has_res, has_tail, in_slope = ctx.flags
         dtail = None
         if has_tail:
+            c = ctx.saved_tensors[0].shape[1]
             dtail = dy[:, c:]   # the skip tensor's gradient: a view, summed into its other gradients by autograd
             dy = dy[:, :c]      # read in place through the row stride
         else:
             dy = dy.contiguous()
-        local = be.bn_bwd_stats(dy, x, gate, stat, relu)
-        sums2 = local
-        if _syncing(sync):
-            sums2 = local.clone()
-            dist.all_reduce(sums2, group=_stats_group())
-        if ctx.in_slope is not None:
-            dx, dres = be.bn_bwd_apply(dy, x, gate, stat, sums2, count, weight, relu, has_res, count_dev=count_dev, in_slope=ctx.in_slope)
-        else:
-            dx, dres = be.bn_bwd_apply(dy, x, gate, stat, sums2, count, weight, relu, has_res, count_dev=count_dev)
-        dw = db = None
-        if weight is not None:  # local sums: DDP averages parameter grads
-            lw = getattr(local, "_pcs_f32", None)   # the HIP reduction leaves them in fp32 as well
-            if lw is None or lw.dtype != weight.dtype:
-                lw = local.to(weight.dtype)         # one cast for both halves
-            dw, db = lw[c:], lw[:c]
-        return dx, dres, dw, db, None, None, None, None, None, None, None, None, None, dtail, None
+        dx, dres, dw, db = _bn_backward(ctx.cfg, ctx.saved_tensors, dy, relu, has_res, in_slope)
+        return dx, dres, dw, db, None, None, None, None, None, None, None, dtail, None
+
+
+def bn_rows(bn, x, residual=None, relu=False, tail=None, pre=None, in_slope=None):
+    """`relu(bn(x) + residual)` [with `tail` concatenated on the right] over plain (N, C) tensors, on the parameters / buffers of
+    any BatchNorm1d-shaped module: the ONE way into the fused passes. Training mode counts the step (`_count_step`) and uses
+    the batch statistics -- `pre`: what the producing convolution handed over for x -- all-reduced for a sync layer (`_bn_sync`);
+    eval mode applies the running statistics. in_slope, tail: `_FusedBN.forward`."""
+    if bn.training:
+        _count_step(bn)
+        return _FusedBN.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu,
+                              _bn_sync(bn), pre, tail, in_slope)
+    return native.backend().bn_apply(x.contiguous(), residual.contiguous() if residual is not None else None, _running_stat(bn),
+                                     bn.weight, bn.bias, relu, tail=tail.contiguous() if tail is not None else None)
+
+
+def bn_forward(bn, input, residual=None, relu=False, cat_with=None, in_slope=None):
+    """`relu(bn(input) + residual)` [concatenated with cat_with] over SparseTensor features as one fused pass, on the parameters /
+    buffers of `bn`: a FusedBatchNorm (whose forward this is) or the caller's own nn.BatchNorm1d / nn.SyncBatchNorm
+    (block_fusion; BatchNorm1d semantics in train and eval mode, SyncBatchNorm: the statistics are all-reduced over the whole job).
+    cat_with: a SparseTensor / tensor on the same coordinates; the result then carries cat([bn(x), cat_with], 1) (torchsparse.cat
+    of the reference's decoder, fused into the apply pass). in_slope: the input is the output of a LeakyReLU that the producing
+    convolution applied in its write-back (`_FusedBN.forward`). A residual of another dtype is cast to the features'."""
+    x, pre = _handed_over(input)
+    r = residual.feats if isinstance(residual, SparseTensor) else residual
+    tail = cat_with.feats if isinstance(cat_with, SparseTensor) else cat_with
+    if tail is not None and (x.shape[1] % 4 or tail.shape[1] % 4 or tail.shape[0] != x.shape[0] or tail.dtype != x.dtype):
+        # the concat-fused apply pass moves 16-byte pieces of one dtype: other widths (the cr 1.6 configs: 409 + 204 ...) concatenate with torch
+        y = bn_forward(bn, input, residual=residual, relu=relu)
+        return y._like(torch.cat([y.feats, tail.to(y.feats.dtype)], dim=1))
+    if r is not None and r.dtype != x.dtype:
+        r = r.to(x.dtype)
+    return input._like(bn_rows(bn, x, r, relu, tail, pre, in_slope))
 
 
 class FusedBatchNorm(nn.Module):
     """BatchNorm over SparseTensor features with optional fused residual add and ReLU:
-    `bn(x)`, `bn(x, relu=True)`, `bn(x, residual=r, relu=True)`."""
+    `bn(x)`, `bn(x, relu=True)`, `bn(x, residual=r, relu=True)`, `bn(x, cat_with=skip)` (`bn_forward`)."""
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, sync=False):
         super().__init__()
@@ -165,39 +246,12 @@ class FusedBatchNorm(nn.Module):
         self.register_buffer("running_mean", torch.zeros(num_features))
         self.register_buffer("running_var", torch.ones(num_features))
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
-        self.counted_by_parent = False
+        self.counted_by_parent = False   # a model may bump all its counters with one _foreach_add_ per step
 
     def extra_repr(self):
         return "%d, eps=%g, momentum=%g, sync=%s" % (self.num_features, self.eps, self.momentum, self.sync)
 
-    def forward(self, input, residual=None, relu=False, cat_with=None, in_slope=None):
-        """cat_with: a SparseTensor / tensor on the same coordinates; the result then carries cat([bn(x), cat_with], 1)
-        (torchsparse.cat of the reference's decoder, fused into the apply pass). in_slope: the input is the output of a
-        LeakyReLU that the producing convolution applied in its write-back (`_FusedBN.forward`)."""
-        x = input.feats
-        r = residual.feats if isinstance(residual, SparseTensor) else residual
-        tail = cat_with.feats if isinstance(cat_with, SparseTensor) else cat_with
-        if tail is not None and (x.shape[1] % 4 or tail.shape[1] % 4 or tail.shape[0] != x.shape[0]):
-            # the concat-fused apply pass moves 16-byte pieces: other widths (the cr 1.6 configs: 409 + 204 ...) concatenate with torch
-            y = self.forward(input, residual=residual, relu=relu)
-            return input._like(torch.cat([y.feats, tail.to(y.feats.dtype)], dim=1))
-        if self.training:
-            if not self.counted_by_parent:  # a model may bump all its counters with one _foreach_add_ per step
-                self.num_batches_tracked += 1
-            # statistics handed over by the producing convolution are used only for the very tensor they describe
-            # (same object, untouched since): `x.F = dropout(x.F)`, `x.feats += b` in between fall back to the stats pass
-            pre = getattr(input, "bn_sums", None)
-            if pre is not None:
-                sums, of, ver = pre
-                pre = sums if (of is x and x._version == ver) else None
-            y = _FusedBN.apply(x, r, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
-                               self.momentum, relu, self.sync, input.cmaps, input.stride, pre, tail, in_slope)
-        else:
-            inv = torch.rsqrt(self.running_var.double() + self.eps)
-            stat = torch.cat([self.running_mean.double(), inv]).contiguous()
-            y = native.backend().bn_apply(x.contiguous(), r.contiguous() if r is not None else None, stat,
-                                          self.weight, self.bias, relu, tail=tail.contiguous() if tail is not None else None)
-        return input._like(y)
+    forward = bn_forward
 
 
 class _SkinnyLinear(Function):
@@ -367,106 +421,13 @@ class FusedLinear(nn.Linear):
         return _SkinnyLinearParts.apply(self.weight, self.bias, self._maps, hd, *parts)
 
 
-# ---- SPVCNN's point-branch merge -----------------------------------------------------------------------------------------
+# ---- the point-branch merges: SPVCNN's (voxel + point) and RPVNet's (voxel + range + point) ---------------------------------
+_ROW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
 def _merge_enabled():
     import os
     return os.environ.get("PCS_POINT_MERGE", "1") != "0"   # A/B switch: 0 = the literal three-op sequence
-
-
-def _bn_backward(ctx_cfg, saved, dy):
-    """The two backward passes of a BatchNorm + ReLU whose gate is the bit mask (no residual): -> (dx, dweight, dbias)."""
-    be = native.backend()
-    x, gate, stat, weight, count_dev = saved
-    count, sync = ctx_cfg
-    c = x.shape[1]
-    local = be.bn_bwd_stats(dy, x, gate, stat, True)
-    sums2 = local
-    if _syncing(sync):
-        sums2 = local.clone()
-        dist.all_reduce(sums2, group=_stats_group())
-    dx, _ = be.bn_bwd_apply(dy, x, gate, stat, sums2, count, weight, True, False, count_dev=count_dev)
-    dw = db = None
-    if weight is not None:  # local sums: DDP averages parameter grads
-        lw = getattr(local, "_pcs_f32", None)
-        if lw is None or lw.dtype != weight.dtype:
-            lw = local.to(weight.dtype)
-        dw, db = lw[c:], lw[:c]
-    return dx, dw, db
-
-
-class _PointMerge(Function):
-    """out = devoxelize(vox) + relu(bn(lin)) with training-mode statistics (R:pcseg/model/segmentor/fusion/spvcnn/spvcnn.py:417-418,
-    430-431, 443-444), the apply pass, the gather and the add in ONE kernel (csrc/pointmerge.hip). Statistics, all-reduce and
-    running statistics as `_FusedBN`. The gradient of `out` is both the dy of the BatchNorm backward passes (gate = the bit
-    mask the kernel wrote) and the gout of the devoxelize backward, through the CSR cached on the corner map."""
-
-    @staticmethod
-    def forward(ctx, lin, vox, idx8, w8, weight, bias, running_mean, running_var, eps, momentum, sync):
-        be = native.backend()
-        lin, vox = lin.contiguous(), vox.contiguous()
-        idx8, w8 = idx8.contiguous().int(), w8.contiguous().float()
-        n, c = lin.shape
-        sums = be.bn_stats(lin)
-        count_dev = None
-        if _syncing(sync):
-            dist.all_reduce(sums, group=_stats_group())
-            count_dev = sums[2 * c:]
-        stat = be.bn_finalize(sums, float(n), eps, momentum, running_mean, running_var, count_dev=count_dev)
-        out, mask = be.point_merge(vox, idx8, w8, lin, stat, weight, bias)
-        ctx.save_for_backward(lin, mask, stat, weight, count_dev)
-        ctx.cfg = (float(n), sync)
-        ctx.maps = (idx8, w8, vox.shape[0], vox.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        be = native.backend()
-        g = g.contiguous()
-        idx8, w8, m, vox_dtype = ctx.maps
-        dlin = dvox = dw = db = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
-            dlin, dw, db = _bn_backward(ctx.cfg, ctx.saved_tensors, g)
-        if ctx.needs_input_grad[1]:
-            dvox = be.devoxelize_bwd(g, idx8, w8, m)
-            if dvox.dtype != vox_dtype:
-                dvox = dvox.to(vox_dtype)
-        return dlin, dvox, None, None, dw, db, None, None, None, None, None
-
-
-def point_merge(bn, lin_out, vox_feats, idx8, w8):
-    """`spdevoxelize(vox_feats, idx8, w8) + relu(bn(lin_out))`: SPVCNN's point-branch merge. bn: a FusedBatchNorm (or any
-    BatchNorm1d-shaped module: weight, bias, running statistics, eps, momentum); lin_out (N, C) the point Linear's output;
-    vox_feats (M, C); idx8 / w8 (N, 8) the points' corner map. One kernel when the backend has `point_merge`, C % 32 == 0 and
-    the tensors are on the device (PCS_POINT_MERGE=0 switches it off); otherwise the literal sequence through the existing
-    fused passes -- same function, and in fp32 the same bits. Eval mode: the running statistics."""
-    from . import functional as F_
-    be = native.backend()
-    c = lin_out.shape[1]
-    sync = bool(getattr(bn, "sync", isinstance(bn, nn.SyncBatchNorm)))
-    fused = (_merge_enabled() and hasattr(be, "point_merge") and c % 32 == 0 and lin_out.dim() == 2 and
-             vox_feats.dim() == 2 and vox_feats.shape[1] == c and
-             (lin_out.is_cuda and vox_feats.is_cuda and idx8.is_cuda and w8.is_cuda or getattr(be, "name", "") == "torch-cpu") and
-             lin_out.dtype in (torch.float32, torch.bfloat16, torch.float16) and
-             vox_feats.dtype in (torch.float32, torch.bfloat16, torch.float16))
-    if bn.training:
-        if not getattr(bn, "counted_by_parent", False):
-            bn.num_batches_tracked += 1
-        if fused:
-            return _PointMerge.apply(lin_out, vox_feats, idx8, w8, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                     bn.eps, bn.momentum, sync)
-        y = _FusedBN.apply(lin_out, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, True,
-                           sync, None, None, None, None)
-        return F_.spdevoxelize(vox_feats, idx8, w8) + y
-    inv = torch.rsqrt(bn.running_var.double() + bn.eps)
-    stat = torch.cat([bn.running_mean.double(), inv]).contiguous()
-    if fused:
-        return be.point_merge(vox_feats.contiguous(), idx8.contiguous().int(), w8.contiguous().float(), lin_out.contiguous(),
-                              stat, bn.weight, bn.bias)[0]
-    return F_.spdevoxelize(vox_feats, idx8, w8) + be.bn_apply(lin_out.contiguous(), None, stat, bn.weight, bn.bias, True)
-
-
-# ---- RPVNet's range-point-voxel merge ------------------------------------------------------------------------------------
-_ROW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
 def _range_merge_enabled():
@@ -485,41 +446,46 @@ def _grid_sample_rows(feature_map, pxpy, grid_sample_mode="bilinear"):
     return torch.cat(rows, dim=0)
 
 
-class _RangePointMerge(Function):
-    """out = (devoxelize(vox) + range_sample(img, pxpy)) + third in ONE kernel (csrc/rangemerge.hip;
+class _Merge(Function):
+    """out = devoxelize(vox) [+ range_sample(img, pxpy)] + third in ONE kernel: csrc/pointmerge.hip without an image (SPVCNN,
+    R:pcseg/model/segmentor/fusion/spvcnn/spvcnn.py:417-418, 430-431, 443-444), csrc/rangemerge.hip with one (RPVNet,
     R:pcseg/model/segmentor/fusion/rpvnet/rpvnet.py:648-651, 665-668, 683-686, 701-704). bn_mode: third = relu(bn(lin)) with
     training-mode statistics -- statistics, all-reduce and running statistics as `_FusedBN`, the gate the bit mask the kernel
-    wrote; otherwise third = lin (the finished term). No backward kernel: the gradient of `out` is the dy of the BatchNorm
-    backward passes (bn mode; else lin's gradient itself), the gout of the devoxelize backward through the CSR cached on the
-    corner map, and the gout of the range_sample backward through the pixel CSR cached on pxpy."""
+    wrote; otherwise (range kernel only) third = lin, the finished term. No backward kernel: the gradient of `out` is the dy of
+    the BatchNorm backward passes (bn mode; else lin's gradient itself), the gout of the devoxelize backward through the CSR
+    cached on the corner map, and the gout of the range_sample backward through the pixel CSR cached on pxpy."""
 
     @staticmethod
     def forward(ctx, lin, vox, idx8, w8, img, pxpy, weight, bias, running_mean, running_var, eps, momentum, sync, bn_mode):
         be = native.backend()
         lin, vox = lin.contiguous(), vox.contiguous()
         idx8, w8 = idx8.contiguous().int(), w8.contiguous().float()
-        img32, pxpy = img.float().contiguous(), pxpy.float().contiguous()   # the image is sampled in fp32 (rangelib._RangeToPoint)
+        stat = None
         if bn_mode:
             stat, count, count_dev = _train_stat(be, lin, None, sync, eps, momentum, running_mean, running_var)
-            out, mask = be.range_point_merge(vox, idx8, w8, img32, pxpy, lin, stat, weight, bias)
-            ctx.save_for_backward(lin, mask, stat, weight, count_dev)
             ctx.cfg = (count, sync)
+        if img is None:
+            out, mask = be.point_merge(vox, idx8, w8, lin, stat, weight, bias)
+            ctx.maps = (idx8, w8, vox.shape[0], vox.dtype, None, None, None, lin.dtype)
         else:
-            out, _ = be.range_point_merge(vox, idx8, w8, img32, pxpy, lin, None, None, None)
+            pxpy = pxpy.float().contiguous()
+            # the image is sampled in fp32 (rangelib._RangeToPoint)
+            out, mask = be.range_point_merge(vox, idx8, w8, img.float().contiguous(), pxpy, lin, stat, weight, bias)
+            ctx.maps = (idx8, w8, vox.shape[0], vox.dtype, pxpy, tuple(img.shape), img.dtype, lin.dtype)
+        if bn_mode:
+            ctx.save_for_backward(lin, mask, stat, weight, count_dev)
         ctx.bn_mode = bn_mode
-        ctx.maps = (idx8, w8, vox.shape[0], vox.dtype, pxpy, tuple(img.shape), img.dtype, lin.dtype)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        from . import rangelib
         be = native.backend()
         g = g.contiguous()
-        idx8, w8, m, vox_dtype, pxpy, (b, c, h, w), img_dtype, lin_dtype = ctx.maps
+        idx8, w8, m, vox_dtype, pxpy, img_shape, img_dtype, lin_dtype = ctx.maps
         dlin = dvox = dimg = dw = db = None
         if ctx.bn_mode:
             if ctx.needs_input_grad[0] or ctx.needs_input_grad[6] or ctx.needs_input_grad[7]:
-                dlin, dw, db = _bn_backward(ctx.cfg, ctx.saved_tensors, g)
+                dlin, _, dw, db = _bn_backward(ctx.cfg, ctx.saved_tensors, g)
         elif ctx.needs_input_grad[0]:
             dlin = g if g.dtype == lin_dtype else g.to(lin_dtype)
         if ctx.needs_input_grad[1]:
@@ -527,33 +493,88 @@ class _RangePointMerge(Function):
             if dvox.dtype != vox_dtype:
                 dvox = dvox.to(vox_dtype)
         if ctx.needs_input_grad[4]:
+            from . import rangelib
             if rangelib._PENDING:
                 rangelib.verify_pending()
-            dimg = be.range_sample_bwd(g.float().contiguous(), pxpy, b, h, w)
+            dimg = be.range_sample_bwd(g.float().contiguous(), pxpy, img_shape[0], img_shape[2], img_shape[3])
             if dimg.dtype != img_dtype:
                 dimg = dimg.to(img_dtype)
         return dlin, dvox, None, None, dimg, None, dw, db, None, None, None, None, None, None
 
 
-def _range_merge_kernel_serves(be, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode):
-    """The inputs csrc/rangemerge.hip (or the backend's restatement of it) takes; everything else is the literal sequence."""
-    if not (_range_merge_enabled() and hasattr(be, "range_point_merge") and grid_sample_mode == "bilinear"):
+def _merge_kernel_serves(be, lin_out, vox_feats, idx8, w8, feature_map=None, pxpy=None, grid_sample_mode="bilinear"):
+    """The inputs csrc/pointmerge.hip (feature_map None) or csrc/rangemerge.hip (or the backend's restatement of them) takes;
+    everything else is the literal sequence. The two kernels differ, and the differences are stated here and nowhere else:
+      * each has its own switch (PCS_POINT_MERGE, PCS_RANGE_MERGE);
+      * the point kernel has no add mode: it needs c % 32 == 0 (the ReLU mask is made of whole words), where the range kernel
+        takes any width of whole 16-byte pieces and `_merge` runs the BatchNorm pass first when c % 32 != 0;
+      * the point kernel takes vox and lin in differing row dtypes (the backend casts up to fp32); the range kernel refuses them,
+        and the literal sequence promotes as torch does.
+    Both take host tensors on the CPU backend and device tensors on the HIP backend, never a mixture, and no empty input (the
+    literal sequence reads an empty shard's count as 1, `_train_stat`)."""
+    ranged = feature_map is not None
+    if ranged:
+        if not (_range_merge_enabled() and hasattr(be, "range_point_merge") and grid_sample_mode == "bilinear"):
+            return False
+    elif not (_merge_enabled() and hasattr(be, "point_merge")):
         return False
     cpu = getattr(be, "name", "") == "torch-cpu"
-    tensors = (lin_out, vox_feats, idx8, w8, feature_map, pxpy)
+    tensors = (lin_out, vox_feats, idx8, w8) + ((feature_map, pxpy) if ranged else ())
     if not (all(not t.is_cuda for t in tensors) if cpu else all(t.is_cuda for t in tensors)):
         return False   # host tensors on the HIP backend, or a mixture
-    if lin_out.dim() != 2 or vox_feats.dim() != 2 or feature_map.dim() != 4 or pxpy.dim() != 2 or pxpy.shape[1] != 3:
+    if lin_out.dim() != 2 or vox_feats.dim() != 2:
         return False
     n, c = lin_out.shape
-    if n == 0 or vox_feats.shape[1] != c or feature_map.shape[1] != c or pxpy.shape[0] != n or not pxpy.is_floating_point():
+    if n == 0 or vox_feats.shape[1] != c or lin_out.dtype not in _ROW_DTYPES or vox_feats.dtype not in _ROW_DTYPES:
         return False
-    if lin_out.dtype not in _ROW_DTYPES or lin_out.dtype != vox_feats.dtype or feature_map.dtype not in _ROW_DTYPES:
+    if not ranged:
+        return c % 32 == 0
+    if feature_map.dim() != 4 or pxpy.dim() != 2 or pxpy.shape[1] != 3:
+        return False
+    if feature_map.shape[1] != c or pxpy.shape[0] != n or not pxpy.is_floating_point():
+        return False
+    if lin_out.dtype != vox_feats.dtype or feature_map.dtype not in _ROW_DTYPES:
         return False   # row dtypes that differ: the literal sequence promotes them as torch does
     if c % (4 if lin_out.dtype == torch.float32 else 8):
         return False   # the widths the kernel refuses (rows move in 16-byte pieces)
     from . import rangelib
     return rangelib._frames_in_order(pxpy, feature_map.shape[0])
+
+
+def _merge(bn, lin_out, vox_feats, idx8, w8, feature_map=None, pxpy=None, grid_sample_mode="bilinear"):
+    """`point_merge` (feature_map None) and `range_point_merge`."""
+    from . import functional as F_
+    be = native.backend()
+    fused = _merge_kernel_serves(be, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode)
+    if fused and lin_out.shape[1] % 32 == 0:   # BatchNorm apply, ReLU and mask inside the kernel
+        if bn.training:
+            _count_step(bn)
+            return _Merge.apply(lin_out, vox_feats, idx8, w8, feature_map, pxpy, bn.weight, bn.bias, bn.running_mean,
+                                bn.running_var, bn.eps, bn.momentum, _bn_sync(bn), True)
+        maps = (vox_feats.contiguous(), idx8.contiguous().int(), w8.contiguous().float())
+        if feature_map is None:
+            return be.point_merge(*maps, lin_out.contiguous(), _running_stat(bn), bn.weight, bn.bias)[0]
+        return be.range_point_merge(*maps, feature_map.float().contiguous(), pxpy.float().contiguous(), lin_out.contiguous(),
+                                    _running_stat(bn), bn.weight, bn.bias)[0]
+    if feature_map is None and not fused and not bn.training:   # this route has always gathered first in eval mode
+        return F_.spdevoxelize(vox_feats, idx8, w8) + bn_rows(bn, lin_out, relu=True)
+    y = bn_rows(bn, lin_out, relu=True)
+    if fused:   # the range kernel's add mode
+        return _Merge.apply(y, vox_feats, idx8, w8, feature_map, pxpy, None, None, None, None, None, None, False, False)
+    if feature_map is None:
+        return F_.spdevoxelize(vox_feats, idx8, w8) + y
+    from . import rangelib
+    r = rangelib.range_to_point(feature_map, pxpy, grid_sample_mode, fallback=_grid_sample_rows)
+    return F_.spdevoxelize(vox_feats, idx8, w8) + r + y
+
+
+def point_merge(bn, lin_out, vox_feats, idx8, w8):
+    """`spdevoxelize(vox_feats, idx8, w8) + relu(bn(lin_out))`: SPVCNN's point-branch merge. bn: a FusedBatchNorm (or any
+    BatchNorm1d-shaped module: weight, bias, running statistics, eps, momentum); lin_out (N, C) the point Linear's output;
+    vox_feats (M, C); idx8 / w8 (N, 8) the points' corner map. One kernel when the backend has `point_merge`, C % 32 == 0 and
+    the tensors are on the device (PCS_POINT_MERGE=0 switches it off); otherwise the literal sequence through the existing
+    fused passes -- same function, and in fp32 the same bits. Eval mode: the running statistics."""
+    return _merge(bn, lin_out, vox_feats, idx8, w8)
 
 
 def range_point_merge(bn, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode="bilinear"):
@@ -565,58 +586,13 @@ def range_point_merge(bn, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_
     fused BatchNorm pass first and the kernel adds its output. PCS_RANGE_MERGE=0, a backend without the op, host tensors on the
     HIP backend, other sampling modes, differing row dtypes and refused widths take the literal sequence of the existing
     passes -- same function, and in fp32 the same bits. Eval mode: the running statistics."""
-    from . import functional as F_
-    from . import rangelib
-    be = native.backend()
-    c = lin_out.shape[1]
-    sync = _bn_sync(bn)
-    fused = _range_merge_kernel_serves(be, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode)
-    bn_mode = fused and c % 32 == 0
-    if bn.training:
-        if not getattr(bn, "counted_by_parent", False):
-            bn.num_batches_tracked += 1
-        if bn_mode:
-            return _RangePointMerge.apply(lin_out, vox_feats, idx8, w8, feature_map, pxpy, bn.weight, bn.bias, bn.running_mean,
-                                          bn.running_var, bn.eps, bn.momentum, sync, True)
-        y = _FusedBN.apply(lin_out, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, True,
-                           sync, None, None, None, None)
-    else:
-        stat = _running_stat(bn)
-        if bn_mode:
-            return be.range_point_merge(vox_feats.contiguous(), idx8.contiguous().int(), w8.contiguous().float(),
-                                        feature_map.float().contiguous(), pxpy.float().contiguous(), lin_out.contiguous(),
-                                        stat, bn.weight, bn.bias)[0]
-        y = be.bn_apply(lin_out.contiguous(), None, stat, bn.weight, bn.bias, True)
-    if fused:
-        return _RangePointMerge.apply(y, vox_feats, idx8, w8, feature_map, pxpy, None, None, None, None, None, None, False, False)
-    r = rangelib.range_to_point(feature_map, pxpy, grid_sample_mode, fallback=_grid_sample_rows)
-    return F_.spdevoxelize(vox_feats, idx8, w8) + r + y
+    return _merge(bn, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode)
 
 
 # ---- Cylinder3D's ReconBlock gate ------------------------------------------------------------------------------------------
 def _gate_enabled():
     import os
     return os.environ.get("PCS_RECON_GATE", "1") != "0"   # A/B switch: 0 = the literal sequence
-
-
-def _feats_pre(t):
-    """(features, statistics the producing convolution handed over for exactly this tensor or None) of a SparseTensor / tensor."""
-    if not isinstance(t, SparseTensor):
-        return t, None
-    x, pre = t.feats, getattr(t, "bn_sums", None)
-    if pre is not None:
-        sums, of, ver = pre
-        pre = sums if (of is x and x._version == ver) else None
-    return x, pre
-
-
-def _bn_sync(bn):
-    return bool(getattr(bn, "sync", isinstance(bn, nn.SyncBatchNorm)))
-
-
-def _running_stat(bn):
-    inv = torch.rsqrt(bn.running_var.double() + bn.eps)
-    return torch.cat([bn.running_mean.double(), inv]).contiguous()
 
 
 class _ReconGate(Function):
@@ -652,14 +628,9 @@ class _ReconGate(Function):
         a3 = [a0, a1, a2]
         dy = dy.contiguous()
         local = be.recon_gate_bwd_stats(dy, x, a3, stat3, gamma3, beta3)
-        sums2 = local
-        if _syncing(sync):
-            sums2 = local.clone()
-            dist.all_reduce(sums2, group=_stats_group())   # ONE collective for the three BatchNorms
+        sums2 = _reduced(local, sync)   # ONE collective for the three BatchNorms
         dx, da = be.recon_gate_bwd_apply(dy, x, a3, stat3, gamma3, beta3, sums2, count, count_dev=count_dev)
-        lw = getattr(local, "_pcs_f32", None)   # local sums: DDP averages parameter grads
-        if lw is None or lw.dtype != wdtype:
-            lw = local.to(wdtype)
+        lw = _param_sums(local, wdtype)
         wb = []
         for k in range(3):
             wb += [lw[(2 * k + 1) * c:(2 * k + 2) * c], lw[2 * k * c:(2 * k + 1) * c]]
@@ -676,7 +647,7 @@ def recon_gate(bns, conv_outs, x):
     torch.sigmoid, adds, multiply. Eval mode: the running statistics, same kernel."""
     be = native.backend()
     xf = x.feats if isinstance(x, SparseTensor) else x
-    got = [_feats_pre(t) for t in conv_outs]
+    got = [_handed_over(t) for t in conv_outs]
     feats = [xf] + [a for a, _ in got]
     halfs = (torch.bfloat16, torch.float16)
     dt = xf.dtype if all(t.dtype == xf.dtype for t in feats) else torch.float32
@@ -687,11 +658,9 @@ def recon_gate(bns, conv_outs, x):
              all(t.data_ptr() % 16 == 0 or not t.is_contiguous() for t in feats) and
              all(bn.weight is not None and bn.bias is not None for bn in bns) and
              all(bn.training == bns[0].training for bn in bns))
-    if any(bn.training for bn in bns):
-        for bn in bns:
-            if bn.training and not getattr(bn, "counted_by_parent", False):
-                bn.num_batches_tracked += 1
     if fused and bns[0].training:
+        for bn in bns:
+            _count_step(bn)
         return _ReconGate.apply(xf, got[0][0], got[1][0], got[2][0], bns[0].weight, bns[0].bias, bns[1].weight, bns[1].bias,
                                 bns[2].weight, bns[2].bias, list(bns), [pre for _, pre in got])
     if fused:
@@ -700,11 +669,6 @@ def recon_gate(bns, conv_outs, x):
                              torch.cat([bn.weight for bn in bns]).float(), torch.cat([bn.bias for bn in bns]).float())
     gate = None
     for bn, (a, pre) in zip(bns, got):
-        if bn.training:
-            y = _FusedBN.apply(a, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, False,
-                               _bn_sync(bn), None, None, pre, None)
-        else:
-            y = be.bn_apply(a.contiguous(), None, _running_stat(bn), bn.weight, bn.bias, False)
-        s = torch.sigmoid(y)
+        s = torch.sigmoid(bn_rows(bn, a, pre=pre))
         gate = s if gate is None else gate + s
     return gate * xf

@@ -456,24 +456,39 @@ class HipBackend:
         self._twin("pcs_devoxelize_fwd", code, [_ptr(feats), _ptr(idx8), _ptr(w8), n, c], [_ptr(out), _stream()])
         return out
 
+    def _merge_operands(self, what, vox, idx8, w8, lin, stat, img=None, pxpy=None):
+        """The operands of the two merge entries, checked and converted -> (dtype code, vox, idx8, w8, lin, img, pxpy, out, mask).
+        vox / lin of differing dtypes: cast up to fp32 without an image (point_merge), refused with one. mask only when stat is given."""
+        vox, vcode = self._pv_feats(vox, "feats")
+        lin, lcode = self._pv_feats(lin, "input")
+        if vcode != lcode:
+            if img is not None:
+                raise TypeError("openpcseg_amd: %s takes vox and lin in one dtype, got %s and %s" % (what, vox.dtype, lin.dtype))
+            vox, lin, vcode = vox.float(), lin.float(), 0
+        idx8 = _dev(idx8, "coords", torch.int32)
+        w8 = _dev(w8, "weights", torch.float32)
+        n, c = lin.shape
+        takes, got = "vox (m, c), lin (n, c), idx8 / w8 (n, 8)", [vox, lin, idx8, w8]
+        ok = vox.dim() == 2 and vox.shape[1] == c and idx8.shape == (n, 8) and w8.shape == (n, 8)
+        if img is not None:
+            img = _dev(img, "feature_map", torch.float32)
+            pxpy = _dev(pxpy, "pxpy", torch.float32)
+            takes, got = takes + ", img (B, c, H, W), pxpy (n, 3)", got + [img, pxpy]
+            ok = ok and img.dim() == 4 and img.shape[1] == c and pxpy.shape == (n, 3)
+        if not ok:
+            raise ValueError("openpcseg_amd: %s takes %s; got %s" % (what, takes, " ".join(str(tuple(t.shape)) for t in got)))
+        out = torch.empty((n, c), dtype=lin.dtype, device=lin.device)
+        mask = torch.empty((n, c // 32), dtype=torch.int32, device=lin.device) if stat is not None else None
+        return vcode, vox, idx8, w8, lin, img, pxpy, out, mask
+
     def point_merge(self, vox, idx8, w8, lin, stat, gamma, beta):
         """SPVCNN's point-branch merge in one pass (csrc/pointmerge.hip): out = devoxelize(vox) + relu(bn(lin)) and the ReLU
         gate of the BatchNorm term as bn_apply's bit mask -> (out (n, c), mask (n, c / 32) int32). vox and lin both bf16 or
         both fp16: the 16-bit entry, out in that dtype; otherwise fp32 (a 16-bit operand beside an fp32 one is cast up).
         c % 32 == 0; stat / gamma / beta as bn_apply takes them."""
-        vox, vcode = self._pv_feats(vox, "feats")
-        lin, lcode = self._pv_feats(lin, "input")
-        if vcode != lcode:
-            vox, lin, vcode = vox.float(), lin.float(), 0
-        idx8 = _dev(idx8, "coords", torch.int32)
-        w8 = _dev(w8, "weights", torch.float32)
+        code, vox, idx8, w8, lin, _, _, out, mask = self._merge_operands("point_merge", vox, idx8, w8, lin, stat)
         n, c = lin.shape
-        if vox.dim() != 2 or vox.shape[1] != c or idx8.shape != (n, 8) or w8.shape != (n, 8):
-            raise ValueError("openpcseg_amd: point_merge takes vox (m, c), lin (n, c), idx8 / w8 (n, 8); got %s %s %s %s"
-                             % (tuple(vox.shape), tuple(lin.shape), tuple(idx8.shape), tuple(w8.shape)))
-        out = torch.empty((n, c), dtype=lin.dtype, device=lin.device)
-        mask = torch.empty((n, c // 32), dtype=torch.int32, device=lin.device)
-        self._twin("pcs_point_merge", vcode, [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(lin), _ptr(stat), _ptr(gamma), _ptr(beta), n, c],
+        self._twin("pcs_point_merge", code, [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(lin), _ptr(stat), _ptr(gamma), _ptr(beta), n, c],
                    [_ptr(out), _ptr(mask), _stream()])
         return out, mask
 
@@ -482,27 +497,12 @@ class HipBackend:
         third -> (out (n, c), mask). stat given (bn mode, c % 32 == 0): third = relu(bn(lin)) and mask (n, c / 32) int32 is its
         ReLU gate as bn_apply's bit mask. stat None (add mode; gamma and beta must be None): third = lin as it is, mask None.
         vox and lin in one row dtype (fp32, bf16 or fp16), out in it; img (B, c, H, W) and pxpy (n, 3) fp32."""
-        vox, vcode = self._pv_feats(vox, "feats")
-        lin, lcode = self._pv_feats(lin, "input")
-        if vcode != lcode:
-            raise TypeError("openpcseg_amd: range_point_merge takes vox and lin in one dtype, got %s and %s" % (vox.dtype, lin.dtype))
-        idx8 = _dev(idx8, "coords", torch.int32)
-        w8 = _dev(w8, "weights", torch.float32)
-        img = _dev(img, "feature_map", torch.float32)
-        pxpy = _dev(pxpy, "pxpy", torch.float32)
-        n, c = lin.shape
-        if (vox.dim() != 2 or vox.shape[1] != c or idx8.shape != (n, 8) or w8.shape != (n, 8) or img.dim() != 4 or
-                img.shape[1] != c or pxpy.shape != (n, 3)):
-            raise ValueError("openpcseg_amd: range_point_merge takes vox (m, c), lin (n, c), idx8 / w8 (n, 8), img (B, c, H, W), "
-                             "pxpy (n, 3); got %s %s %s %s %s %s" % (tuple(vox.shape), tuple(lin.shape), tuple(idx8.shape),
-                                                                    tuple(w8.shape), tuple(img.shape), tuple(pxpy.shape)))
+        code, vox, idx8, w8, lin, img, pxpy, out, mask = self._merge_operands("range_point_merge", vox, idx8, w8, lin, stat, img, pxpy)
         if stat is None and (gamma is not None or beta is not None):
             raise ValueError("openpcseg_amd: range_point_merge in add mode (stat None) takes no gamma / beta")
-        b, _, h, w = img.shape
-        out = torch.empty((n, c), dtype=lin.dtype, device=lin.device)
-        mask = torch.empty((n, c // 32), dtype=torch.int32, device=lin.device) if stat is not None else None
-        self._twin("pcs_range_point_merge", vcode, [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(img), _ptr(pxpy), b, h, w, _ptr(lin),
-                                                    _ptr(stat), _ptr(gamma), _ptr(beta), n, c], [_ptr(out), _ptr(mask), _stream()])
+        (n, c), (b, _, h, w) = lin.shape, img.shape
+        self._twin("pcs_range_point_merge", code, [_ptr(vox), _ptr(idx8), _ptr(w8), _ptr(img), _ptr(pxpy), b, h, w, _ptr(lin),
+                                                   _ptr(stat), _ptr(gamma), _ptr(beta), n, c], [_ptr(out), _ptr(mask), _stream()])
         return out, mask
 
     def devoxelize_bwd(self, gout, idx8, w8, m):

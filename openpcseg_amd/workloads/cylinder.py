@@ -24,7 +24,7 @@ from .. import functional as F
 from .. import fused, native
 from .. import modules as spnn
 from ..block_fusion import _PointLinear
-from ..fused import FusedBatchNorm, _FusedBN
+from ..fused import FusedBatchNorm
 from ..scatter import scatter_max
 from ..sparse import SparseTensor
 from .losses import SegLoss
@@ -43,12 +43,7 @@ def _linear(lin, x):
 
 def _dense_bn(bn, h, relu=False):
     """A FusedBatchNorm over plain (N, C) rows (the point MLPs): the fused statistics / apply passes."""
-    if bn.training:
-        if not bn.counted_by_parent:
-            bn.num_batches_tracked += 1
-        return _FusedBN.apply(h, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, relu, bn.sync,
-                              None, None, None, None)
-    return native.backend().bn_apply(h.contiguous(), None, fused._running_stat(bn), bn.weight, bn.bias, relu)
+    return fused.bn_rows(bn, h, relu=relu)
 
 
 def _cab(conv, bn, x, residual=None, want_skip=False):

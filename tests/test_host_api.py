@@ -685,3 +685,135 @@ def test_conv3d_half_host_features_forward_and_backward(monkeypatch, backend):
     (yh, gxh, gwh), (y32, gx32, gw32) = res[torch.bfloat16], res[torch.float32]
     assert torch.equal(yh, y32.bfloat16()) and torch.equal(gxh, gx32.bfloat16()) and torch.equal(gwh, gw32)
     assert float(y32.abs().max()) > 0 and float(gx32.abs().max()) > 0 and float(gw32.abs().max()) > 0
+
+
+# ---- one BatchNorm entry for every fused caller (fused.bn_rows) ----------------------------------------------------------------
+# the smallest shapes at which the routes differ: c = 32 serves both merge kernels' BatchNorm mode, c = 24 the range merge's add mode
+_BN_N, _BN_M = 8, 5
+
+
+def _bn_case(c, n=_BN_N):
+    g = torch.Generator().manual_seed(c + n)
+    r = lambda *s: torch.randn(*s, generator=g)
+    idx8 = torch.randint(-1, _BN_M, (n, 8), generator=g).int()
+    pxpy = torch.cat([torch.zeros(n, 1), torch.rand(n, 2, generator=g) * 2 - 1], 1)
+    coords = torch.cat([torch.arange(n).reshape(-1, 1).repeat(1, 3), torch.zeros(n, 1, dtype=torch.long)], 1).int()
+    return {"lin": r(n, c), "vox": r(_BN_M, c), "idx8": idx8, "w8": torch.rand(n, 8, generator=g), "img": r(1, c, 4, 8), "pxpy": pxpy,
+            "a3": [r(n, c), r(n, c), r(n, c)], "coords": coords}
+
+
+def _bn_entries():
+    """name -> (modules, call, switch variable or None): every way into the fused BatchNorm passes."""
+    from openpcseg_amd import block_fusion, fused
+    from openpcseg_amd.workloads import cylinder
+    sp = lambda k: SparseTensor(k["lin"].clone(), k["coords"])
+    own, stock = (lambda c: [fused.FusedBatchNorm(c)]), (lambda c: [torch.nn.BatchNorm1d(c)])
+    return {
+        "FusedBatchNorm": (own, lambda b, k: b[0](sp(k), relu=True), None),
+        "bn_forward": (stock, lambda b, k: block_fusion.bn_forward(b[0], sp(k), relu=True), None),
+        "_dense_bn_apply": (stock, lambda b, k: block_fusion._dense_bn_apply(b[0], k["lin"], True), None),
+        "cylinder._dense_bn": (own, lambda b, k: cylinder._dense_bn(b[0], k["lin"], relu=True), None),
+        "point_merge": (own, lambda b, k: fused.point_merge(b[0], k["lin"], k["vox"], k["idx8"], k["w8"]), "PCS_POINT_MERGE"),
+        "range_point_merge": (own, lambda b, k: fused.range_point_merge(b[0], k["lin"], k["vox"], k["idx8"], k["w8"], k["img"], k["pxpy"]),
+                              "PCS_RANGE_MERGE"),
+        "recon_gate": (lambda c: [fused.FusedBatchNorm(c) for _ in range(3)], lambda b, k: fused.recon_gate(b, k["a3"], k["lin"]),
+                       "PCS_RECON_GATE"),
+    }
+
+
+_SWITCHED = [("point_merge", 32), ("range_point_merge", 32), ("range_point_merge", 24), ("recon_gate", 32)]
+
+
+@pytest.mark.parametrize("entry,c,switch", [(e, 32, None) for e in ("FusedBatchNorm", "bn_forward", "_dense_bn_apply", "cylinder._dense_bn")] +
+                         [(e, c, s) for e, c in _SWITCHED for s in ("1", "0")])
+def test_every_batchnorm_entry_counts_a_training_step_once(monkeypatch, entry, c, switch):
+    """A training call raises num_batches_tracked by exactly one, an eval call by none; a layer somebody else counted -- for good
+    (`counted_by_parent`) or for this step (`_pcs_bumped`, cleared by the call) -- is not counted again. The entries that have a
+    switch: with the fused kernel (1) and through the literal sequence (0)."""
+    from openpcseg_amd import cpu_fallback
+    make, call, var = _bn_entries()[entry]
+    assert (var is None) == (switch is None)
+    if var is not None:
+        monkeypatch.setenv(var, switch)
+    k = _bn_case(c)
+    count = lambda bns: [int(b.num_batches_tracked) for b in bns]
+    rows = lambda y: (y.feats if isinstance(y, SparseTensor) else y).shape[0]
+    with cpu_fallback.enabled():
+        bns = [b.train() for b in make(c)]
+        assert rows(call(bns, k)) == _BN_N and count(bns) == [1] * len(bns)
+        for b in bns:
+            b.eval()
+        with torch.no_grad():
+            call(bns, k)
+        assert count(bns) == [1] * len(bns)
+        for b in bns:
+            b.train().counted_by_parent = True
+        call(bns, k)
+        assert count(bns) == [1] * len(bns)
+        for b in bns:
+            b.counted_by_parent = False
+            b.__dict__["_pcs_bumped"] = True
+        call(bns, k)
+        assert count(bns) == [1] * len(bns) and not any(b.__dict__["_pcs_bumped"] for b in bns)
+        call(bns, k)   # the mark was for one step
+        assert count(bns) == [2] * len(bns)
+
+
+def test_point_merge_of_an_empty_shard_counts_one_row_like_every_other_path():
+    """n = 0 rows in training mode (a rank without points): point_merge takes the literal sequence, whose statistics read an
+    empty shard's count as 1 -- finite running statistics, the ones FusedBatchNorm leaves on the same empty input -- and returns a
+    (0, c) tensor whose backward runs."""
+    from openpcseg_amd import cpu_fallback, fused
+    c = 32
+    k = _bn_case(c, n=0)
+    with cpu_fallback.enabled():
+        ref = fused.FusedBatchNorm(c).train()
+        ref(SparseTensor(k["lin"].clone(), k["coords"]), relu=True)
+        bn = fused.FusedBatchNorm(c).train()
+        lin, vox = k["lin"].clone().requires_grad_(True), k["vox"].clone().requires_grad_(True)
+        out = fused.point_merge(bn, lin, vox, k["idx8"], k["w8"])
+        assert out.shape == (0, c)
+        out.sum().backward()
+    assert torch.isfinite(bn.running_mean).all() and torch.isfinite(bn.running_var).all()
+    assert torch.equal(bn.running_mean, ref.running_mean) and torch.equal(bn.running_var, ref.running_var)
+    assert int(bn.num_batches_tracked) == 1
+    assert lin.grad.shape == (0, c) and vox.grad.shape == (_BN_M, c) and not vox.grad.any()
+    assert bn.weight.grad is not None and torch.isfinite(bn.weight.grad).all() and torch.isfinite(bn.bias.grad).all()
+
+
+@pytest.mark.parametrize("training", [True, False], ids=["train", "eval"])
+def test_fused_batchnorm_has_the_dtype_rules_of_bn_forward(training):
+    """A residual of another dtype is cast to the features' dtype, a cat_with of another dtype is concatenated by torch: FusedBatchNorm
+    and block_fusion.bn_forward on a stock BatchNorm with the same state both give what torch's own BatchNorm1d gives on the fp32
+    rows with the bf16 operand widened exactly (+ other.float(), ReLU, or cat). Tolerance: fp32 rounding of a handful of operations
+    on values of a few units: 1e-5 absolute; a bf16 detour of the features would miss it by 1e-2."""
+    from openpcseg_amd import block_fusion, cpu_fallback, fused
+    c = 32
+    k = _bn_case(c)
+    other = torch.randn(_BN_N, c, generator=torch.Generator().manual_seed(7)).bfloat16()
+
+    def seeded(bn):
+        with torch.no_grad():
+            bn.weight.copy_(torch.linspace(0.5, 1.5, c))
+            bn.bias.copy_(torch.linspace(-0.5, 0.5, c))
+            bn.running_mean.copy_(torch.linspace(-1, 1, c))
+            bn.running_var.copy_(torch.linspace(0.5, 2, c))
+        return bn.train(training)
+
+    with cpu_fallback.enabled():
+        for kw in ({"residual": other, "relu": True}, {"cat_with": other}, {"cat_with": SparseTensor(other, k["coords"]), "relu": True}):
+            own, stock, ref = seeded(fused.FusedBatchNorm(c)), seeded(torch.nn.BatchNorm1d(c)), seeded(torch.nn.BatchNorm1d(c))
+            with torch.no_grad():
+                want = ref(k["lin"].clone())
+            if "residual" in kw:
+                want = want + other.float()
+            if kw.get("relu"):
+                want = torch.relu(want)
+            if "cat_with" in kw:
+                want = torch.cat([want, other.float()], 1)
+            a = own(SparseTensor(k["lin"].clone(), k["coords"]), **kw)
+            b = block_fusion.bn_forward(stock, SparseTensor(k["lin"].clone(), k["coords"]), **kw)
+            for got, bn in ((a.feats, own), (b.feats, stock)):
+                assert got.dtype == torch.float32 and got.shape == want.shape == (_BN_N, 2 * c if "cat_with" in kw else c)
+                assert float((got.detach() - want).abs().max()) <= 1e-5, sorted(kw)
+                assert torch.allclose(bn.running_mean, ref.running_mean, atol=1e-6) and torch.allclose(bn.running_var, ref.running_var, atol=1e-6)
