@@ -34,8 +34,9 @@ extern "C" {
 #define PCS_ELAUNCH (-3)  /* hipLaunch / hipMemsetAsync failed (pcs_last_error has text) */
 #define PCS_EUNSUPPORTED (-4)
 
-/* Still 12 after two additive changes: the `reserved` word of pcs_conv_epilogue became `flags` (PCS_EP_RELU; a zeroed struct
- * means what it meant) and the prediction-tail export was added. A caller built against the earlier v12 header runs unchanged. */
+/* Still 12 after three additive changes: the `reserved` word of pcs_conv_epilogue became `flags` (PCS_EP_RELU; a zeroed struct
+ * means what it meant), the prediction-tail export was added, and pcs_conv_epilogue grew two trailing fields that are read only
+ * when the new flag PCS_EP_POST_AFFINE is set. A caller built against the earlier v12 header runs unchanged. */
 #define PCS_ABI_VERSION 12
 
 int pcs_abi_version(void);
@@ -325,17 +326,29 @@ int pcs_conv_gather_gemm_f32(const float *src, int64_t n_src, int32_t cin, const
  * Shapes the wave kernels do not serve (pcs_conv_supports_epilogue() == 0) return PCS_EUNSUPPORTED when any extra is set.
  * ABI v12: the struct no longer carries the BatchNorm backward-statistics inputs between addend and act_slope.
  * Still v12 (additive): the former `reserved` word is `flags`, same offset and size; a zero-initialised struct means
- * what it meant. Order of the write-back: bias, then addend, then the activation. */
+ * what it meant. Order of the write-back: bias, then addend, then the activation.
+ * Still v12 (additive): PCS_EP_POST_AFFINE and the trailing fields post_scale / post_shift. The kernels read the two fields
+ * ONLY when the flag is set, so a caller built against the shorter struct (which cannot set bit 16: it was PCS_EINVAL) and a
+ * zeroed struct mean what they meant. With the flag the order of the write-back is
+ *     v = conv + bias;  v = act(v);  v = v * post_scale[c] + post_shift[c] (fp32);  v = v + addend;  store
+ * -- inference of conv -> LeakyReLU -> BatchNorm (+ residual) (R:pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:88-334)
+ * with the BatchNorm's running statistics as the affine map: gamma may be negative, so the map does not commute with the
+ * activation into the weights. The half kernels round once, on the store. Not together with bn_partial (PCS_EINVAL: statistics
+ * of an affine-mapped tensor have no consumer); a null or not 16-byte-aligned post_scale / post_shift is PCS_EINVAL; shapes
+ * with pcs_conv_supports_epilogue() == 0 return PCS_EUNSUPPORTED as for the other extras. The bf16x3 entry takes no epilogue. */
 #define PCS_EP_RELU 1   /* flags: the activation is ReLU, whatever act_slope holds */
+#define PCS_EP_POST_AFFINE 16   /* flags: post_scale / post_shift are read and applied behind the activation, the addend behind them */
 typedef struct pcs_conv_epilogue {
   const void *addend;
   float act_slope;   /* LeakyReLU fused into the write-back: dst = v < 0 ? v * act_slope : v, applied before the store and before the
                       * forward BatchNorm statistics (R:pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:88-190: conv -> LeakyReLU
                       * -> BatchNorm1d). 0 is read as 1 (no activation), so a zero-initialised struct is the plain call. */
-  int32_t flags;     /* 0 or PCS_EP_RELU; any other bit is PCS_EINVAL. PCS_EP_RELU: the kernels run their LeakyReLU branch with slope
+  int32_t flags;     /* PCS_EP_RELU | PCS_EP_POST_AFFINE; any other bit (2, 4, 8, 32 ...) is PCS_EINVAL. PCS_EP_RELU: the kernels run their LeakyReLU branch with slope
                       * 0 (inference with BatchNorm folded into the weights: conv + bias + residual + ReLU in one launch). A negative
                       * pre-activation therefore gives a zero of either sign (v * 0 = -0.0), and non-finite pre-activations are not
                       * flushed (-inf * 0 = NaN); -0.0 == 0 in every comparison a consumer makes. */
+  const float *post_scale;   /* fp32 (cout), 16-byte aligned; read only with PCS_EP_POST_AFFINE */
+  const float *post_shift;   /* fp32 (cout), 16-byte aligned; read only with PCS_EP_POST_AFFINE */
 } pcs_conv_epilogue;
 int pcs_conv_gather_gemm_f32_ex(const float *src, int64_t n_src, int32_t cin, const float *W,
                                 int32_t K, int32_t cout, const int32_t *pairs, int32_t src_col,

@@ -189,13 +189,17 @@ class TorchCpuBackend:
 
     # -- convolution (TS:torchsparse/nn/functional/conv.py:67-79 semantics)
     conv_epilogue_relu = True   # conv_gather_gemm takes the write-back extras of the HIP entry (addend, act_slope, relu)
+    conv_epilogue_post_affine = True   # ... and post_scale / post_shift (PCS_EP_POST_AFFINE)
 
     def conv_supports_addend(self, cin, cout, k, dtype=0):
         return dtype == 0
 
     def conv_gather_gemm(self, src, weight, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True, addend=None,
-                         act_slope=None, relu=False):
-        """Write-back extras in the order of pcs_conv_epilogue: bias, then addend, then the activation (relu wins over act_slope)."""
+                         act_slope=None, relu=False, post_scale=None, post_shift=None):
+        """Write-back extras in the order of pcs_conv_epilogue: bias, then addend, then the activation (relu wins over act_slope);
+        with post_scale / post_shift (PCS_EP_POST_AFFINE): bias, activation, the per-column affine map, then the addend."""
+        if (post_scale is None) != (post_shift is None):
+            raise ValueError("post_scale and post_shift come together")
         src, weight = _cpu(src, "input").float(), _cpu(weight, "weight").float()
         if src.shape[1] != weight.shape[1]:
             raise ValueError("Input feature size and kernel size mismatch")
@@ -210,11 +214,17 @@ class TorchCpuBackend:
         if addend is not None:
             if tuple(addend.shape) != tuple(out.shape):
                 raise ValueError("addend %s does not match the output %s" % (tuple(addend.shape), tuple(out.shape)))
-            out = out + _cpu(addend, "addend").float()
+            addend = _cpu(addend, "addend").float()
+        if addend is not None and post_scale is None:
+            out = out + addend
         if relu:
             out = torch.relu(out)
         elif act_slope is not None and act_slope not in (0.0, 1.0):
             out = torch.where(out < 0, out * float(act_slope), out)
+        if post_scale is not None:
+            out = out * _cpu(post_scale, "post_scale").float() + _cpu(post_shift, "post_shift").float()
+            if addend is not None:
+                out = out + addend
         return out
 
     def conv_wgrad(self, fa, fb, kmap, a_col, split=False):

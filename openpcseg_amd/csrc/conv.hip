@@ -205,7 +205,8 @@ extern "C" int pcs_conv_gather_gemm_f32_ex(const float *src, int64_t n_src, int3
   a.cin = cin; a.cout = cout; a.K = K; a.src_col = src_col; a.ncoltiles = 1; a.stats = bn_partial;
   a.order = tile_order;
   const void *addend = nullptr;
-  if (conv_decode_epilogue(ep, "pcs_conv_gather_gemm_f32_ex", 16, addend, a.act_slope) != PCS_OK) return PCS_EINVAL;
+  if (conv_decode_epilogue(ep, "pcs_conv_gather_gemm_f32_ex", 16, bn_partial != nullptr, addend, a.act_slope, a.post_scale, a.post_shift) != PCS_OK)
+    return PCS_EINVAL;
   a.addend = reinterpret_cast<const float *>(addend);
   if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, 0)) {
     set_error("pcs_conv_gather_gemm_f32: this shape / tile height does not produce BatchNorm partials (ask pcs_conv_emits_bn_partials)");
@@ -217,7 +218,7 @@ extern "C" int pcs_conv_gather_gemm_f32_ex(const float *src, int64_t n_src, int3
     set_error("pcs_conv_gather_gemm_f32: BatchNorm partials need the 16-byte-granular wave kernels");
     return PCS_EUNSUPPORTED;
   }
-  if ((addend || a.act_slope != 1.f) && !(vec && K <= 32)) {
+  if ((addend || a.act_slope != 1.f || a.post_scale) && !(vec && K <= 32)) {
     set_error("pcs_conv_gather_gemm_f32_ex: this shape runs on the generic kernel, which takes no write-back extras (pcs_conv_supports_epilogue)");
     return PCS_EUNSUPPORTED;
   }

@@ -48,6 +48,8 @@ struct ConvArgs {
   const float *addend = nullptr;  // optional (n_dst, cout): added to the output rows in the write-back (the wave kernels only):
                                   // the skip gradient of a residual block riding in the dgrad of its first convolution
   float act_slope = 1.f;  // LeakyReLU in the write-back: v < 0 -> v * act_slope (1 = none), before the store and the statistics
+  // PCS_EP_POST_AFFINE: fp32 (cout) each, both or neither. Set: bias, activation, v * post_scale[c] + post_shift[c], then the addend
+  const float *post_scale = nullptr, *post_shift = nullptr;
 };
 
 // the storage-format tags Bf16 / Fp16 / Fp32 of the half-precision kernels (features / prepared weights / outputs) and

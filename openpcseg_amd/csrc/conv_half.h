@@ -29,6 +29,7 @@ struct ConvArgsH {
   const int32_t *order;  // optional [ntiles]: workgroup slot -> row tile (heaviest first), as ConvArgs::order
   const uint16_t *addend = nullptr;  // optional (n_dst, cout) halfs: added (in fp32, before the rounding) to the output rows
   float act_slope = 1.f;             // LeakyReLU in the write-back, as ConvArgs::act_slope
+  const float *post_scale = nullptr, *post_shift = nullptr;  // PCS_EP_POST_AFFINE, as ConvArgs::post_scale (fp32; ONE rounding, on the store)
 };
 
 }  // namespace pcs

@@ -269,7 +269,8 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os4_kernel(ConvArgs a) {
   float *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
-                                   ConvStoreF32{drow, a.addend, row0, n0, ldd, a.act_slope});
+                                   ConvStoreF32{drow, a.addend, row0, n0, ldd, a.act_slope, a.post_scale,
+                                                conv_post_quad<C::CT>(a.post_scale, a.post_shift, n0, a.cout, tid)});
 }
 
 template <int NCTT, int T, int NW, int MINW>

@@ -339,7 +339,8 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5_kernel(ConvArgs a) {
   float *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
-                                   ConvStoreF32{drow, a.addend, row0, n0, ldd, a.act_slope});
+                                   ConvStoreF32{drow, a.addend, row0, n0, ldd, a.act_slope, a.post_scale,
+                                                conv_post_quad<C::CT>(a.post_scale, a.post_shift, n0, a.cout, tid)});
 #if PCS_TRACE
   if (lane == 0 && blockIdx.x < kTraceBlocks && g_conv_trace) {
     long long *t = g_conv_trace + ((int64_t)blockIdx.x * 8 + wid) * 8;

@@ -57,7 +57,10 @@ __global__ void __launch_bounds__(256) prepare_weights_kernel(const float *__res
   }
 }
 
-template <typename HT, int NCTT, int NW, int MINW, int R, bool TAIL>
+// POST: the PCS_EP_POST_AFFINE write-back (a.post_scale set) as instances of their own -- as a run-time branch the R = 4 instances
+// at 128 columns gained 48 bytes of scratch (profiles/conv_post_affine_resources.md), so the instances without the mode compile
+// to the code they had. Instantiated for R = 2 (the default and the TAIL instances) only: launch_h.
+template <typename HT, int NCTT, int NW, int MINW, int R, bool TAIL, bool POST = false>
 __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
   using C = ConvWaveCfg<NCTT, NW, R>;
   const int T = a.tile_rows;
@@ -360,15 +363,22 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5h_kernel(ConvArgsH a) {
   const int rows = (int)((a.n_dst - row0) < (int64_t)T ? (a.n_dst - row0) : (int64_t)T);
   uint16_t *drow = a.dst + row0 * a.cout + n0;
   const int ldd = a.cout;
+  // PCS_EP_POST_AFFINE (the order of ConvStoreHalf, conv_wave_common.h): this thread's scale / shift quads, loaded once
+  ConvPostQuad post;
+  if (POST) post = conv_post_quad<C::CT>(a.post_scale, a.post_shift, n0, a.cout, tid);
   conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, a.stats ? a.stats + tile * 2 * a.cout : nullptr, tid,
                                    [&](int r, int cq, const float4 &v0) {
                                      float4 v = v0;
+                                     if (POST) {  // bias, activation, affine map, then the addend
+                                       if (a.act_slope != 1.f) conv_leaky(v, a.act_slope);
+                                       conv_affine(v, post);
+                                     }
                                      if (a.addend) {  // kernel argument: uniform
                                        const uint2 ad = *reinterpret_cast<const uint2 *>(a.addend + (row0 + r) * (int64_t)ldd + n0 + cq);
                                        v.x += h2f(HT{}, (uint16_t)(ad.x & 0xFFFFu)); v.y += h2f(HT{}, (uint16_t)(ad.x >> 16));
                                        v.z += h2f(HT{}, (uint16_t)(ad.y & 0xFFFFu)); v.w += h2f(HT{}, (uint16_t)(ad.y >> 16));
                                      }
-                                     if (a.act_slope != 1.f) {
+                                     if (!POST && a.act_slope != 1.f) {
                                        v.x = v.x < 0.f ? v.x * a.act_slope : v.x; v.y = v.y < 0.f ? v.y * a.act_slope : v.y;
                                        v.z = v.z < 0.f ? v.z * a.act_slope : v.z; v.w = v.w < 0.f ? v.w * a.act_slope : v.w;
                                      }
@@ -399,10 +409,10 @@ void traceh_prepare(hipStream_t st) {
 }
 #endif
 
-template <typename HT, int NCTT, int NW, int MINW, int R, bool TAIL>
+template <typename HT, int NCTT, int NW, int MINW, int R, bool TAIL, bool POST = false>
 int launch_conv5h(const ConvArgsH &a, hipStream_t st) {
   using C = ConvWaveCfg<NCTT, NW, R>;
-  return conv_wave_launch<conv_os5h_kernel<HT, NCTT, NW, MINW, R, TAIL>>(a, a.order != nullptr, C::NT, C::lds_bytes(a.tile_rows), st, "pcs_conv_h",
+  return conv_wave_launch<conv_os5h_kernel<HT, NCTT, NW, MINW, R, TAIL, POST>>(a, a.order != nullptr, C::NT, C::lds_bytes(a.tile_rows), st, "pcs_conv_h",
                                                                           "pcs_conv_gather_gemm_h(wave5h)", [&](int64_t) { PCS_T(traceh_prepare(st);) });
 }
 
@@ -427,6 +437,8 @@ int launch_h(ConvArgsH a, hipStream_t st) {
   const int rsel = tail ? 2 : (force_r >= 2 && force_r <= 4 ? force_r : convh_group_rows(nctt));
 #define PCS_CONV5H_CASE(N)                                                                          \
   case N:                                                                                           \
+    if (a.post_scale && tail) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, true, true>(a, st) : launch_conv5h<HT, N, 4, 2, 2, true, true>(a, st);  \
+    if (a.post_scale) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, false, true>(a, st) : launch_conv5h<HT, N, 4, 2, 2, false, true>(a, st);  \
     if (tail) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, true>(a, st) : launch_conv5h<HT, N, 4, 2, 2, true>(a, st);  \
     if (rsel == 4) return nw8 ? launch_conv5h<HT, N, 8, 2, 4, false>(a, st) : launch_conv5h<HT, N, 4, 2, 4, false>(a, st);  \
     if (rsel == 3) return nw8 ? launch_conv5h<HT, N, 8, 2, 3, false>(a, st) : launch_conv5h<HT, N, 4, 2, 3, false>(a, st);  \
@@ -506,7 +518,8 @@ extern "C" int pcs_conv_gather_gemm_h_ex(const void *src, int64_t n_src, int32_t
   a.n_dst = n_dst; a.ntiles = ceil_div(n_dst, tile_rows); a.tile_rows = tile_rows;
   a.cin = cin; a.cout = cout; a.K = K; a.src_col = src_col; a.ncoltiles = 1; a.stats = bn_partial; a.order = tile_order;
   const void *addend = nullptr;
-  if (conv_decode_epilogue(ep, "pcs_conv_gather_gemm_h_ex", 8, addend, a.act_slope) != PCS_OK) return PCS_EINVAL;
+  if (conv_decode_epilogue(ep, "pcs_conv_gather_gemm_h_ex", 8, bn_partial != nullptr, addend, a.act_slope, a.post_scale, a.post_shift) != PCS_OK)
+    return PCS_EINVAL;
   a.addend = reinterpret_cast<const uint16_t *>(addend);
   if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, dtype)) {
     set_error("pcs_conv_gather_gemm_h: this shape / tile height does not produce BatchNorm partials");

@@ -62,13 +62,25 @@ struct Conv6hCfg : ConvWaveCfg<NCTT, NW_> {   // no offset tables in LDS: the sl
 // the row groups in a fixed order through the free tile, un-shifted in double. Needs T >= 2 NRG + 1 rows of scratch for stats.
 template <typename HT, int CT, int NT>
 __device__ __forceinline__ void half_tile_epilogue8(float *acc_l, int ACS, int rows, int n0, int cout, const float *bias, double *stats,
-                                                    int tid, uint16_t *drow, int ldd, const uint16_t *arow, float act_slope) {
+                                                    int tid, uint16_t *drow, int ldd, const uint16_t *arow, float act_slope,
+                                                    const float *post_scale, const float *post_shift) {
   constexpr int Q = CT / 8, NRG = NT / Q;
   const int q = tid % Q, rg = tid / Q, c8 = 8 * q;
   const bool on = rg < NRG && n0 + c8 < cout;   // cout % 8 == 0: a piece is inside or outside as a whole
   float b[8], piv[8], s0[8], s1[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) b[j] = piv[j] = s0[j] = s1[j] = 0.f;
+  // PCS_EP_POST_AFFINE (post_scale: a kernel argument, uniform): bias, activation, * ps + pt, then the addend, ONE rounding on the
+  // store; this thread's eight scales / shifts are loaded here, once, and never without the mode
+  float ps[8], pt[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { ps[j] = 1.f; pt[j] = 0.f; }
+  if (on && post_scale) {
+    const float4 a0 = *reinterpret_cast<const float4 *>(post_scale + n0 + c8), a1 = *reinterpret_cast<const float4 *>(post_scale + n0 + c8 + 4);
+    const float4 t0 = *reinterpret_cast<const float4 *>(post_shift + n0 + c8), t1 = *reinterpret_cast<const float4 *>(post_shift + n0 + c8 + 4);
+    ps[0] = a0.x; ps[1] = a0.y; ps[2] = a0.z; ps[3] = a0.w; ps[4] = a1.x; ps[5] = a1.y; ps[6] = a1.z; ps[7] = a1.w;
+    pt[0] = t0.x; pt[1] = t0.y; pt[2] = t0.z; pt[3] = t0.w; pt[4] = t1.x; pt[5] = t1.y; pt[6] = t1.z; pt[7] = t1.w;
+  }
   if (on) {
     if (bias) {
       const float4 b0 = *reinterpret_cast<const float4 *>(bias + n0 + c8), b1 = *reinterpret_cast<const float4 *>(bias + n0 + c8 + 4);
@@ -82,6 +94,13 @@ __device__ __forceinline__ void half_tile_epilogue8(float *acc_l, int ACS, int r
     for (int r = rg; r < rows; r += NRG) {
       const float4 v0 = *reinterpret_cast<const float4 *>(acc_l + r * ACS + c8), v1 = *reinterpret_cast<const float4 *>(acc_l + r * ACS + c8 + 4);
       float v[8] = {v0.x + b[0], v0.y + b[1], v0.z + b[2], v0.w + b[3], v1.x + b[4], v1.y + b[5], v1.z + b[6], v1.w + b[7]};
+      if (post_scale) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float u = (act_slope != 1.f && v[j] < 0.f) ? v[j] * act_slope : v[j];
+          v[j] = u * ps[j] + pt[j];
+        }
+      }
       if (arow) {  // the addend's rows of this tile (kernel argument: uniform)
         const uint4 ad = *reinterpret_cast<const uint4 *>(arow + (int64_t)r * ldd + c8);
         v[0] += h2f(HT{}, (uint16_t)(ad.x & 0xFFFFu)); v[1] += h2f(HT{}, (uint16_t)(ad.x >> 16));
@@ -89,7 +108,7 @@ __device__ __forceinline__ void half_tile_epilogue8(float *acc_l, int ACS, int r
         v[4] += h2f(HT{}, (uint16_t)(ad.z & 0xFFFFu)); v[5] += h2f(HT{}, (uint16_t)(ad.z >> 16));
         v[6] += h2f(HT{}, (uint16_t)(ad.w & 0xFFFFu)); v[7] += h2f(HT{}, (uint16_t)(ad.w >> 16));
       }
-      if (act_slope != 1.f) {
+      if (!post_scale && act_slope != 1.f) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = v[j] < 0.f ? v[j] * act_slope : v[j];
       }
@@ -433,10 +452,11 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
   double *stats = a.stats ? a.stats + tile * 2 * a.cout : nullptr;
   if ((a.cout & 7) == 0 && (((uintptr_t)a.dst | (uintptr_t)a.addend) & 15) == 0 && (!stats || T + C::SINK >= 2 * C::NRG8 + 1)) {
     half_tile_epilogue8<HT, C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, stats, tid, drow, ldd,
-                                          a.addend ? a.addend + row0 * a.cout + n0 : nullptr, a.act_slope);
+                                          a.addend ? a.addend + row0 * a.cout + n0 : nullptr, a.act_slope, a.post_scale, a.post_shift);
   } else {
     conv_tile_epilogue<C::CT, C::NT>(acc_l, C::ACS, rows, n0, a.cout, a.bias, stats, tid,
-                                     ConvStoreHalf<HT>{drow, a.addend, row0, n0, ldd, a.act_slope});
+                                     ConvStoreHalf<HT>{drow, a.addend, row0, n0, ldd, a.act_slope, a.post_scale,
+                                                       conv_post_quad<C::CT>(a.post_scale, a.post_shift, n0, a.cout, tid)});
   }
 #if PCS_TRACE
   if (lane == 0 && g_ws_trace && (int)blockIdx.x < g_ws_trace_blocks) {

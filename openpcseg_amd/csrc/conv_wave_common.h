@@ -98,14 +98,25 @@ int conv_wave_launch(const Args &a, bool pad8, int nt, size_t lds, hipStream_t s
 }
 
 // pcs_conv_epilogue of the _ex entry points -> addend / act_slope of the kernels (ReLU = their LeakyReLU branch with slope 0;
-// act_slope 0 reads as 1: a zeroed struct is the plain call). `who` heads the error texts.
-inline int conv_decode_epilogue(const pcs_conv_epilogue *ep, const char *who, uintptr_t addend_align, const void *&addend,
-                                float &act_slope) {
+// act_slope 0 reads as 1: a zeroed struct is the plain call). post_scale / post_shift: the struct's trailing fields, touched only
+// under PCS_EP_POST_AFFINE (a caller built against the shorter struct never sets the bit); has_stats: the call asks for BatchNorm
+// partials, which the post-affine mode does not produce. `who` heads the error texts.
+inline int conv_decode_epilogue(const pcs_conv_epilogue *ep, const char *who, uintptr_t addend_align, bool has_stats,
+                                const void *&addend, float &act_slope, const float *&post_scale, const float *&post_shift) {
   addend = ep ? ep->addend : nullptr;
+  post_scale = post_shift = nullptr;
   if (addend && ((uintptr_t)addend & (addend_align - 1))) { set_error("%s: misaligned addend", who); return PCS_EINVAL; }
   if (ep && ep->act_slope != 0.f && ep->act_slope != 1.f) act_slope = ep->act_slope;
-  if (ep && (ep->flags & ~PCS_EP_RELU)) { set_error("%s: unknown pcs_conv_epilogue.flags bits", who); return PCS_EINVAL; }
+  if (ep && (ep->flags & ~(PCS_EP_RELU | PCS_EP_POST_AFFINE))) { set_error("%s: unknown pcs_conv_epilogue.flags bits", who); return PCS_EINVAL; }
   if (ep && (ep->flags & PCS_EP_RELU)) act_slope = 0.f;
+  if (ep && (ep->flags & PCS_EP_POST_AFFINE)) {
+    if (!ep->post_scale || !ep->post_shift || (((uintptr_t)ep->post_scale | (uintptr_t)ep->post_shift) & 15)) {
+      set_error("%s: PCS_EP_POST_AFFINE needs 16-byte-aligned post_scale and post_shift", who);
+      return PCS_EINVAL;
+    }
+    if (has_stats) { set_error("%s: PCS_EP_POST_AFFINE does not go with bn_partial", who); return PCS_EINVAL; }
+    post_scale = ep->post_scale; post_shift = ep->post_shift;
+  }
   return PCS_OK;
 }
 
@@ -360,22 +371,48 @@ __device__ __forceinline__ void conv_commit_rows(const unsigned (&dq)[RN][4], co
 }
 
 // ---- write-back functors for conv_tile_epilogue: + addend, LeakyReLU / ReLU, store; they return the value AS STORED --------
+// PCS_EP_POST_AFFINE (post_scale != nullptr, a kernel argument: wave-uniform): LeakyReLU / ReLU, * scale + shift, + addend, store.
+// The quads of this thread's four columns are loaded once, in front of the row loop (conv_post_quad: a thread of
+// conv_tile_epilogue keeps its column quad cq = 4 (tid % (CT / 4)) for all its rows); without the mode they are never read.
+struct ConvPostQuad { float4 s, t; };
+template <int CT>
+__device__ __forceinline__ ConvPostQuad conv_post_quad(const float *post_scale, const float *post_shift, int n0, int cout, int tid) {
+  ConvPostQuad p;
+  p.s = make_float4(1.f, 1.f, 1.f, 1.f);
+  p.t = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int c = n0 + 4 * (tid % (CT / 4));
+  if (post_scale && c < cout) {  // cout % 4 == 0: a quad is inside or outside as a whole
+    p.s = *reinterpret_cast<const float4 *>(post_scale + c);
+    p.t = *reinterpret_cast<const float4 *>(post_shift + c);
+  }
+  return p;
+}
+__device__ __forceinline__ void conv_leaky(float4 &v, float act_slope) {
+  v.x = v.x < 0.f ? v.x * act_slope : v.x; v.y = v.y < 0.f ? v.y * act_slope : v.y;
+  v.z = v.z < 0.f ? v.z * act_slope : v.z; v.w = v.w < 0.f ? v.w * act_slope : v.w;
+}
+__device__ __forceinline__ void conv_affine(float4 &v, const ConvPostQuad &p) {
+  v.x = v.x * p.s.x + p.t.x; v.y = v.y * p.s.y + p.t.y; v.z = v.z * p.s.z + p.t.z; v.w = v.w * p.s.w + p.t.w;
+}
 struct ConvStoreF32 {
   float *drow;          // dst row 0 of the tile, first column of the column tile
   const float *addend;  // (n_dst, ldd) or nullptr
   int64_t row0;
   int n0, ldd;
   float act_slope;
+  const float *post_scale;  // nullptr: bias, addend, activation (the order of every call before PCS_EP_POST_AFFINE)
+  ConvPostQuad post;
   __device__ __forceinline__ float4 operator()(int r, int cq, const float4 &v0) const {
     float4 v = v0;
+    if (post_scale) {  // kernel argument: uniform
+      if (act_slope != 1.f) conv_leaky(v, act_slope);
+      conv_affine(v, post);
+    }
     if (addend) {  // kernel argument: uniform
       const float4 ad = *reinterpret_cast<const float4 *>(addend + (row0 + r) * (int64_t)ldd + n0 + cq);
       v.x += ad.x; v.y += ad.y; v.z += ad.z; v.w += ad.w;
     }
-    if (act_slope != 1.f) {
-      v.x = v.x < 0.f ? v.x * act_slope : v.x; v.y = v.y < 0.f ? v.y * act_slope : v.y;
-      v.z = v.z < 0.f ? v.z * act_slope : v.z; v.w = v.w < 0.f ? v.w * act_slope : v.w;
-    }
+    if (!post_scale && act_slope != 1.f) conv_leaky(v, act_slope);
     *reinterpret_cast<float4 *>(drow + (int64_t)r * ldd + cq) = v;
     return v;
   }
@@ -389,17 +426,20 @@ struct ConvStoreHalf {
   int64_t row0;
   int n0, ldd;
   float act_slope;
+  const float *post_scale;  // as ConvStoreF32: the post-affine order, everything in fp32, one rounding below
+  ConvPostQuad post;
   __device__ __forceinline__ float4 operator()(int r, int cq, const float4 &v0) const {
     float4 v = v0;
+    if (post_scale) {  // kernel argument: uniform
+      if (act_slope != 1.f) conv_leaky(v, act_slope);
+      conv_affine(v, post);
+    }
     if (addend) {  // kernel argument: uniform
       const uint2 ad = *reinterpret_cast<const uint2 *>(addend + (row0 + r) * (int64_t)ldd + n0 + cq);
       v.x += h2f(HT{}, (uint16_t)(ad.x & 0xFFFFu)); v.y += h2f(HT{}, (uint16_t)(ad.x >> 16));
       v.z += h2f(HT{}, (uint16_t)(ad.y & 0xFFFFu)); v.w += h2f(HT{}, (uint16_t)(ad.y >> 16));
     }
-    if (act_slope != 1.f) {
-      v.x = v.x < 0.f ? v.x * act_slope : v.x; v.y = v.y < 0.f ? v.y * act_slope : v.y;
-      v.z = v.z < 0.f ? v.z * act_slope : v.z; v.w = v.w < 0.f ? v.w * act_slope : v.w;
-    }
+    if (!post_scale && act_slope != 1.f) conv_leaky(v, act_slope);
     const uint16_t hx = f2h(HT{}, v.x), hy = f2h(HT{}, v.y), hz = f2h(HT{}, v.z), hw = f2h(HT{}, v.w);
     uint2 o;
     o.x = hx | ((uint32_t)hy << 16);

@@ -405,13 +405,16 @@ def _weight_copy(be, w3, key, kept):
 
 
 def _run_conv(be, fam, x, w3, kmap, hd, kept, transpose=False, bias=None, stats=None, addend=None, cast_addend=False,
-              act_slope=None, relu=False, rounded=True):
+              act_slope=None, relu=False, rounded=True, post_scale=None, post_shift=None, act_optional=False):
     """One routed convolution: x over kmap with the fp32 master weights w3 (K, A, B) on the family `fam` names -- the operand cast,
     the weight copy from `kept`, the backend entry, and (rounded) an fp32 result rounded to hd -> (out, the cast operand, took).
     transpose: contract over B (dgrad). stats: a list for the write-back's BatchNorm statistics; emptied again when the result is
     rounded (they describe the fp32 values). addend / relu: write-back extras the kernel takes where it can; `took` says whether
     it did, the caller does them itself otherwise. An addend rides as it is, in a kernel whose output is final in the addend's
-    dtype, or (cast_addend) cast to the kernel's. act_slope is not negotiable: the caller asked conv_act_fusable() first."""
+    dtype, or (cast_addend) cast to the kernel's. act_slope is not negotiable: the caller asked conv_act_fusable() first --
+    unless act_optional (the inference path), where the slope is one more extra of the same all-or-nothing `took`.
+    post_scale / post_shift: fp32 (cout), the per-column affine map BEHIND the activation, the addend behind that
+    (PCS_EP_POST_AFFINE); taken only by a backend with `conv_epilogue_post_affine`, together with the other extras or not at all."""
     k, a, b = w3.shape
     cin, cout = (b, a) if transpose else (a, b)
     kdt = hd if fam == "half" else torch.float32   # what the kernel reads and writes
@@ -427,12 +430,14 @@ def _run_conv(be, fam, x, w3, kmap, hd, kept, transpose=False, bias=None, stats=
         kw["bn_sums"] = stats
         if getattr(be, "supports_bn_raw", False):
             kw["bn_raw"] = True   # the per-tile partials themselves: the BatchNorm reduces and finalizes them in ONE launch
-    if act_slope is not None:
+    post = post_scale is not None
+    if act_slope is not None and not act_optional:
         assert fam != "x3", "act_slope: the bf16x3 entry has no write-back extras (conv_act_fusable)"
         kw["act_slope"] = float(act_slope)
     took = False
-    if (addend is not None or relu) and fam != "x3" and hasattr(be, "conv_supports_addend") and \
-            (not relu or getattr(be, "conv_epilogue_relu", False)) and \
+    if (addend is not None or relu or post or (act_optional and act_slope is not None)) and fam != "x3" and \
+            hasattr(be, "conv_supports_addend") and (not relu or getattr(be, "conv_epilogue_relu", False)) and \
+            (not post or getattr(be, "conv_epilogue_post_affine", False)) and \
             (addend is None or cast_addend or (addend.is_cuda and addend.dtype == kdt == (hd or torch.float32))):
         code = native.HipBackend._HALF[hd] if fam == "half" else 0
         took = kept(("epilogue?", code, transpose), lambda: be.conv_supports_addend(cin, cout, k, code))
@@ -440,6 +445,10 @@ def _run_conv(be, fam, x, w3, kmap, hd, kept, transpose=False, bias=None, stats=
         kw["addend"] = addend.to(hd) if fam == "half" else addend.float()
     if took and relu:
         kw["relu"] = True
+    if took and act_optional and act_slope is not None:
+        kw["act_slope"] = float(act_slope)
+    if took and post:
+        kw["post_scale"], kw["post_shift"] = post_scale, post_shift
     if fam == "fp32":
         out = be.conv_gather_gemm(x, wp, kmap, **kw)
     else:
@@ -722,7 +731,7 @@ def conv3d(input, weight, kernel_size, bias=None, stride=1, dilation=1, transpos
 
 
 def conv3d_inference(input, weight, bias, kernel_size, stride=1, dilation=1, transposed=False, addend=None, relu=False,
-                     prepared=None):
+                     prepared=None, act_slope=None, post_scale=None, post_shift=None):
     """Forward-only convolution of the inference path (openpcseg_amd.inference): act(conv(x, weight) + bias [+ addend]) in ONE
     launch -- the write-back of the fused gather-GEMM applies bias, addend and ReLU (pcs_conv_epilogue, PCS_EP_RELU). No autograd.
     weight: fp32 (K, cin, cout) or (cin, cout), typically a convolution's kernel with the BatchNorm that follows folded in; bias
@@ -731,6 +740,10 @@ def conv3d_inference(input, weight, bias, kernel_size, stride=1, dilation=1, tra
     (rounded to the autocast dtype); a 1x1x1 convolution runs on the gather-GEMM over the identity map like fused._SkinnyLinear.
     Where the kernel takes no write-back extras (generic shapes, the bf16x3 policy, zero-padded odd widths, a backend without
     `conv_epilogue_relu`), the kernel adds the bias and torch adds / clamps in place: still no BatchNorm launch.
+    act_slope: LeakyReLU instead of ReLU (relu wins). post_scale / post_shift: fp32 (cout); with them the order becomes
+    act(conv + bias) * post_scale + post_shift [+ addend] -- Cylinder3D's conv -> LeakyReLU -> BatchNorm (+ residual) with the
+    BatchNorm's running statistics as the affine map (PCS_EP_POST_AFFINE), one launch where the backend has
+    `conv_epilogue_post_affine` and the shape's kernel takes extras, else leaky_relu_, mul_, add_, add_ in place behind the kernel.
     prepared: a dict owned by the caller that keeps the derived weight copies (fragment-ordered half weights per dtype) and the
     shape queries' answers for as long as `weight` is current; with it a forward after the first prepares nothing."""
     be = _be()
@@ -754,7 +767,9 @@ def conv3d_inference(input, weight, bias, kernel_size, stride=1, dilation=1, tra
         if bias is not None:
             out = out + bias
     else:
-        x, extras, kept = feats, {"addend": addend, "relu": relu, "cast_addend": True}, _kept_in(prepared, (pin, pout))
+        extras = {"addend": addend, "relu": relu, "cast_addend": True, "act_slope": act_slope, "act_optional": True,
+                  "post_scale": post_scale, "post_shift": post_shift}
+        x, kept = feats, _kept_in(prepared, (pin, pout))
         if pin or pout:   # zero-padded widths: no bf16x3 kernel, no write-back extras
             x, extras = torch.nn.functional.pad(feats, (0, pin)) if pin else feats, {}
             w3 = kept(("pad",), lambda: torch.nn.functional.pad(w3.float(), (0, pout, 0, pin)).contiguous())
@@ -764,10 +779,16 @@ def conv3d_inference(input, weight, bias, kernel_size, stride=1, dilation=1, tra
         out, _, fused = _run_conv(be, fam, x, w3, kmap, hd, kept, bias=bias, rounded=False, **extras)
         out = out[:, :cout].contiguous() if pout else out
     if not fused:
-        if addend is not None:
+        if addend is not None and post_scale is None:
             out = out.add_(addend.to(out.dtype))
         if relu:
             out = out.relu_()
+        elif act_slope is not None and act_slope not in (0.0, 1.0):
+            out = torch.nn.functional.leaky_relu_(out, float(act_slope))
+        if post_scale is not None:
+            out = out.mul_(post_scale).add_(post_shift)
+            if addend is not None:
+                out = out.add_(addend.to(out.dtype))
     if hd is not None and out.dtype != hd:
         out = out.to(hd)
     output = SparseTensor(coords=output_coords, feats=out, stride=output_stride)

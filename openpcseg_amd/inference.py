@@ -20,6 +20,11 @@ needs no `unfreeze`. A record remembers the version counters (and storage addres
 BatchNorm's weight / bias / running statistics and re-folds lazily when any of them changed (`load_state_dict`, an optimizer
 step between two evaluations). The half kernels' fragment-ordered copies of W' live in the same record, so a frozen forward
 after the first launches no weight preparation.
+
+Cylinder3D's blocks run conv -> LeakyReLU -> BatchNorm (+ residual): the scale sits BEHIND the activation and gamma may be negative,
+so it does not commute into the weights (and a fold into the next sparse convolution would carry the shift only to the neighbours
+that exist). There the BatchNorm rides in the same launch as a per-column affine map behind the activation (`PostAffineConv`,
+PCS_EP_POST_AFFINE): W stays what it is, the write-back computes leaky(conv + bias) * s + t (+ residual), one rounding on the store.
 """
 import numpy as np
 import torch
@@ -31,7 +36,7 @@ from . import native
 from .fused import FusedBatchNorm, FusedLinear
 from .sparse import SparseTensor
 
-__all__ = ["freeze", "unfreeze", "FoldedConv", "SegEvaluator", "point_predict"]
+__all__ = ["freeze", "unfreeze", "FoldedConv", "PostAffineConv", "FoldedDense", "SegEvaluator", "point_predict"]
 
 _NORMS = (FusedBatchNorm, nn.BatchNorm1d)   # spnn.BatchNorm and the workloads' _BN / _SyncBN are BatchNorm1d / SyncBatchNorm
 _ATTR = "_pcs_folds"
@@ -44,6 +49,36 @@ def _is_norm(m):
 def _foldable(conv, bn):
     return (isinstance(conv, spnn.Conv3d) and _is_norm(bn) and getattr(bn, "running_mean", None) is not None and
             getattr(bn, "running_var", None) is not None and conv.out_channels == bn.num_features)
+
+
+def _stamp_of(tensors):
+    """(version, address, device, dtype) of every source tensor, or None where one of them tracks no version counter."""
+    stamp = []
+    for t in tensors:
+        if t is None:
+            stamp.append(None)
+            continue
+        try:
+            stamp.append((t._version, t.data_ptr(), t.device, t.dtype))
+        except RuntimeError:   # inference tensors track no version counter: fold on every call
+            return None
+    return tuple(stamp)
+
+
+def _bn_sources(bn):
+    return [getattr(bn, "weight", None), getattr(bn, "bias", None), bn.running_mean, bn.running_var]
+
+
+def _bn_affine(bn):
+    """The eval-mode BatchNorm as y = x * s + t: (s, t) in float64 on the device of the running statistics."""
+    gamma, beta, mean, var = _bn_sources(bn)
+    s = torch.rsqrt(var.detach().double() + bn.eps)
+    if gamma is not None:
+        s = gamma.detach().double() * s
+    t = -mean.detach().double() * s
+    if beta is not None:
+        t = t + beta.detach().double()
+    return s, t
 
 
 class FoldedConv:
@@ -61,16 +96,7 @@ class FoldedConv:
         return [c.kernel, c.bias, getattr(b, "weight", None), getattr(b, "bias", None), b.running_mean, b.running_var]
 
     def _current(self):
-        stamp = []
-        for t in self._sources():
-            if t is None:
-                stamp.append(None)
-                continue
-            try:
-                stamp.append((t._version, t.data_ptr(), t.device, t.dtype))
-            except RuntimeError:   # inference tensors track no version counter: fold on every call
-                return None
-        return tuple(stamp)
+        return _stamp_of(self._sources())
 
     def folded(self):
         """-> (W' fp32, b' fp32, the dict of derived copies), re-folded when a source tensor changed."""
@@ -98,6 +124,79 @@ class FoldedConv:
         c = self.conv
         return F.conv3d_inference(x, w, b, c.kernel_size, stride=c.stride, dilation=c.dilation, transposed=c.transposed,
                                   addend=residual, relu=self.relu, prepared=prepared)
+
+
+class PostAffineConv:
+    """conv -> LeakyReLU(slope) -> BatchNorm (+ residual) as one launch with the BatchNorm as the affine map behind the activation:
+    scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, float64 arithmetic stored as fp32; the kernel
+    `W` is used as it is. bn None (UpBlock.up_subm): a plain convolution whose record only keeps the derived weight copies; the
+    `residual` of such a record is the ordinary addend. Re-folded per source-tensor version like FoldedConv."""
+
+    def __init__(self, conv, bn=None, slope=None):
+        self.conv, self.bn, self.slope = conv, bn, (float(slope) if slope is not None else None)
+        self._stamp = None
+        self.scale = self.shift = None
+        self.prepared = {}   # derived copies of the kernel (functional.conv3d_inference), dropped when it changes
+        self.folds = 0       # how often the arithmetic ran (tests)
+
+    def _sources(self):
+        return [self.conv.kernel, self.conv.bias] + (_bn_sources(self.bn) if self.bn is not None else [])
+
+    def folded(self):
+        """-> (scale fp32, shift fp32, the dict of derived copies), re-folded when a source tensor changed."""
+        stamp = _stamp_of(self._sources())
+        if stamp is None or stamp != self._stamp:
+            if self.bn is not None:
+                with torch.no_grad():
+                    s, t = _bn_affine(self.bn)
+                    self.scale, self.shift = s.float().contiguous(), t.float().contiguous()
+            self.prepared = {}
+            self._stamp = stamp
+            self.folds += 1
+        return self.scale, self.shift, self.prepared
+
+    def __call__(self, x, residual=None):
+        scale, shift, prepared = self.folded()
+        c = self.conv
+        return F.conv3d_inference(x, c.kernel.detach(), c.bias.detach() if c.bias is not None else None, c.kernel_size, stride=c.stride,
+                                  dilation=c.dilation, transposed=c.transposed, addend=residual, prepared=prepared,
+                                  act_slope=self.slope, post_scale=scale, post_shift=shift)
+
+
+class FoldedDense:
+    """nn.Linear with the BatchNorm in front of it (`bn_in`: W diag(s), b + W t) and / or behind it (`bn_out`: diag(s) W, s b + t)
+    folded in, float64 arithmetic stored as fp32, kept per version of the source tensors: the point MLPs of Cylinder3D."""
+
+    def __init__(self, lin, bn_in=None, bn_out=None):
+        self.lin, self.bn_in, self.bn_out = lin, bn_in, bn_out
+        self._stamp = None
+        self.weight = self.bias = None
+        self.folds = 0
+
+    def _sources(self):
+        return [self.lin.weight, self.lin.bias] + [t for bn in (self.bn_in, self.bn_out) if bn is not None for t in _bn_sources(bn)]
+
+    def folded(self):
+        stamp = _stamp_of(self._sources())
+        if stamp is None or stamp != self._stamp:
+            with torch.no_grad():
+                w = self.lin.weight.detach().double()   # (out, in)
+                b = self.lin.bias.detach().double() if self.lin.bias is not None else torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)
+                if self.bn_in is not None:
+                    s, t = _bn_affine(self.bn_in)
+                    b = b + w @ t
+                    w = w * s[None, :]
+                if self.bn_out is not None:
+                    s, t = _bn_affine(self.bn_out)
+                    w, b = w * s[:, None], b * s + t
+                self.weight, self.bias = w.float().contiguous(), b.float().contiguous()
+            self._stamp = stamp
+            self.folds += 1
+        return self.weight, self.bias
+
+    def __call__(self, x):
+        w, b = self.folded()
+        return torch.nn.functional.linear(x, w, b)
 
 
 class FoldedLinear:
@@ -170,9 +269,12 @@ class _SequentialForward:
 
 def freeze(model):
     """Fold every BatchNorm of the package's own blocks (workloads.minkunet, workloads.spvcnn and workloads.rpvnet: the stem, ConvBlock, ResBlock
-    incl. its 1x1x1 downsample) and of plain `nn.Sequential(Conv3d, BatchNorm [, ReLU], ...)` chains into its convolution. Anything else is
-    left alone. -> {"folded": number of conv + BatchNorm pairs, "skipped": [names of BatchNorm modules that keep running]}.
+    incl. its 1x1x1 downsample) and of plain `nn.Sequential(Conv3d, BatchNorm [, ReLU], ...)` chains into its convolution. Of
+    workloads.cylinder: the conv -> LeakyReLU -> BatchNorm triples of ResContextBlock / ResBlock / UpBlock become one launch each
+    (PostAffineConv), the BatchNorms of the point MLPs fold into their Linear (FoldedDense); ReconNet's three keep running inside
+    the gate kernel on the running statistics and are reported as skipped. Anything else is left alone. -> {"folded": number of BatchNorm modules that stop launching, "skipped": [names of BatchNorm modules that keep running]}.
     Changes no parameter, buffer or state_dict entry; takes effect only in eval mode with grad mode off."""
+    from .workloads import cylinder as cyl
     from .workloads.minkunet import ConvBlock, MinkUNet, ResBlock
     unfreeze(model)
     claimed, folded = set(), 0
@@ -209,6 +311,33 @@ def freeze(model):
                        "classifier": FoldedLinear(m.classifier[0]) if commuted else None}
                 claim(m, rec, [(st[0], st[1]), (st[3], st[4])])
                 claimed.add(id(st))
+    for m in model.modules():   # Cylinder3D (workloads.cylinder): conv -> LeakyReLU -> BatchNorm triples, the point MLPs
+        if isinstance(m, (cyl.ResContextBlock, cyl.UpBlock)):
+            rec = {}
+            for cname, aname, bname in m.TRIPLES:
+                conv, act, bn = getattr(m, cname), getattr(m, aname), getattr(m, bname)
+                slope = float(act.negative_slope) if isinstance(act, nn.LeakyReLU) else float("nan")
+                # the ABI reads a slope of 0 as "no activation": only finite slopes > 0 are claimed
+                if _foldable(conv, bn) and np.isfinite(slope) and slope > 0:
+                    rec[cname] = PostAffineConv(conv, bn, slope)
+            if isinstance(m, cyl.UpBlock) and isinstance(m.up_subm, spnn.Conv3d):
+                rec["up_subm"] = PostAffineConv(m.up_subm)   # + skip.F rides as the addend
+            if rec:
+                claim(m, rec, [(f.conv, f.bn) for f in rec.values() if f.bn is not None])
+        elif isinstance(m, cyl.CylinderTS):
+            pp, rec, pairs = m.PPmodel, {}, []
+            shape = [type(l) for l in pp] == [FusedBatchNorm, nn.Linear, FusedBatchNorm, nn.ReLU, nn.Linear, FusedBatchNorm, nn.ReLU,
+                                              nn.Linear, FusedBatchNorm, nn.ReLU, nn.Linear]
+            if shape and all(getattr(pp[i], "running_mean", None) is not None for i in (0, 2, 5, 8)):
+                rec["pp"] = [FoldedDense(pp[1], bn_in=pp[0], bn_out=pp[2]), FoldedDense(pp[4], bn_out=pp[5]), FoldedDense(pp[7], bn_out=pp[8])]
+                pairs += [(pp[1], pp[0]), (pp[1], pp[2]), (pp[4], pp[5]), (pp[7], pp[8])]
+            cd = getattr(m, "change_dim", None)
+            if cd is not None and len(cd) == 3 and isinstance(cd[0], nn.Linear) and _is_norm(cd[1]) and isinstance(cd[2], nn.LeakyReLU) \
+                    and getattr(cd[1], "running_mean", None) is not None:
+                rec["cd"] = FoldedDense(cd[0], bn_out=cd[1])
+                pairs.append((cd[0], cd[1]))
+            if rec:
+                claim(m, rec, pairs)
     for m in model.modules():
         if isinstance(m, nn.Sequential) and type(m).forward is nn.Sequential.forward and id(m) not in claimed:
             groups = _groups(m)

@@ -724,25 +724,36 @@ class HipBackend:
         return bool(self.lib.pcs_conv_emits_bn_partials(cin, cout, k, self.tile_rows(cin, cout, kmap, code), code))
 
     class _Epilogue(ctypes.Structure):   # include/pcseg_hip.h: pcs_conv_epilogue
-        _fields_ = [("addend", ctypes.c_void_p), ("act_slope", ctypes.c_float), ("flags", ctypes.c_int32)]
+        _fields_ = [("addend", ctypes.c_void_p), ("act_slope", ctypes.c_float), ("flags", ctypes.c_int32),
+                    ("post_scale", ctypes.c_void_p), ("post_shift", ctypes.c_void_p)]   # read only with EP_POST_AFFINE
 
     EP_RELU = 1                 # include/pcseg_hip.h: PCS_EP_RELU
+    EP_POST_AFFINE = 16         # include/pcseg_hip.h: PCS_EP_POST_AFFINE
     conv_epilogue_relu = True   # the conv entries take relu=True (ReLU in the write-back); the inference path asks for it
+    conv_epilogue_post_affine = True   # ... and post_scale= / post_shift= (a per-column affine map behind the activation)
 
-    def _epilogue(self, addend, kmap, cout, dtype, act_slope=None, relu=False):
+    def _epilogue(self, addend, kmap, cout, dtype, act_slope=None, relu=False, post_scale=None, post_shift=None):
         """-> (ctypes pointer or None, keep-alive tuple) for the _ex entries."""
-        if addend is None and act_slope is None and not relu:
+        if (post_scale is None) != (post_shift is None):
+            raise ValueError("post_scale and post_shift come together")
+        if addend is None and act_slope is None and not relu and post_scale is None:
             return None, None
         ep = self._Epilogue(None, float(act_slope) if act_slope is not None else 0.0, self.EP_RELU if relu else 0)
+        if post_scale is not None:
+            post_scale, post_shift = _dev(post_scale, "post_scale", torch.float32), _dev(post_shift, "post_shift", torch.float32)
+            if post_scale.numel() != cout or post_shift.numel() != cout:
+                raise ValueError("post_scale / post_shift must hold %d values" % cout)
+            ep.flags |= self.EP_POST_AFFINE
+            ep.post_scale, ep.post_shift = post_scale.data_ptr(), post_shift.data_ptr()
         if addend is not None:
             addend = _dev(addend, "addend", dtype)
             if tuple(addend.shape) != (kmap.n_dst, cout):
                 raise ValueError("addend %s does not match the output (%d, %d)" % (tuple(addend.shape), kmap.n_dst, cout))
             ep.addend = addend.data_ptr()
-        return ctypes.byref(ep), (ep, addend)
+        return ctypes.byref(ep), (ep, addend, post_scale, post_shift)
 
     def _conv_launch(self, fn, src, wbuf, k, cin, cout, kmap, bias, tile_rows, bn_sums, ordered, bn_raw, addend=None,
-                     act_slope=None, relu=False, code=0, x3=False):
+                     act_slope=None, relu=False, code=0, x3=False, post_scale=None, post_shift=None):
         """What the three conv entries share once their operands are checked: tile height, segment table, destination, BatchNorm
         partial workspace, tile order, write-back extras, the C call `fn` and the reduction of the partials. code: dtype code
         of src and dst (0 fp32). x3: the bf16x3 kernel has its own partials query and its entry takes no pcs_conv_epilogue."""
@@ -759,8 +770,8 @@ class HipBackend:
             # only the fp32 entry has kernels that ignore the order (conv_wave4, conv_block): it does not build one for them
             if x3 or code or self.lib.pcs_conv_uses_tile_order(cin, cout, k, 0):
                 order = self._tile_order(kmap, t)
-        # write-back extras: addend (dgrad + skip gradient, inference residual), LeakyReLU slope, ReLU
-        ep, keep = self._epilogue(addend, kmap, cout, src.dtype, act_slope, relu)
+        # write-back extras: addend (dgrad + skip gradient, inference residual), LeakyReLU slope, ReLU, post-activation affine map
+        ep, keep = self._epilogue(addend, kmap, cout, src.dtype, act_slope, relu, post_scale, post_shift)
         _check(fn(_ptr(src), src.shape[0], cin, _ptr(wbuf), k, cout, _ptr(kmap._pairs_raw), 0, _ptr(seg), t, kmap.n_dst, _ptr(bias),
                   *(() if x3 else (ep,)), _ptr(dst), *((code,) if code else ()), _ptr(part), _ptr(order), _stream()), fn.__name__)
         if part is not None:
@@ -768,7 +779,7 @@ class HipBackend:
         return dst
 
     def conv_gather_gemm(self, src, weight, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True, bn_raw=False, addend=None,
-                         act_slope=None, relu=False):
+                         act_slope=None, relu=False, post_scale=None, post_shift=None):
         """dst[d] = sum_{(s,d) in offset k} src[s] @ weight[k] (+bias); kmap dst-sorted. bn_sums: a list; when the
         kernel can, the [sum x | sum x^2 | n] vector of dst (what bn_stats(dst) returns) is appended to it, computed in
         the convolution's write-back instead of by a pass over dst. ordered: True = heaviest-first tile order where it
@@ -779,7 +790,7 @@ class HipBackend:
         if src.shape[1] != cin:
             raise ValueError("Input feature size and kernel size mismatch")  # convolution_cuda.cu:57-59
         return self._conv_launch(self.lib.pcs_conv_gather_gemm_f32_ex, src, weight, k, cin, cout, kmap, bias, tile_rows, bn_sums, ordered,
-                                 bn_raw, addend, act_slope, relu)
+                                 bn_raw, addend, act_slope, relu, post_scale=post_scale, post_shift=post_shift)
 
     # -- half-precision convolution (bf16 / fp16 MFMA) ------------------------------------------------------
     _HALF = {torch.bfloat16: 1, torch.float16: 2}
@@ -803,7 +814,7 @@ class HipBackend:
         return wp
 
     def conv_gather_gemm_h(self, src, wp, k, cout, kmap, bias=None, tile_rows=None, bn_sums=None, ordered=True, bn_raw=False,
-                           addend=None, act_slope=None, relu=False):
+                           addend=None, act_slope=None, relu=False, post_scale=None, post_shift=None):
         """Half-precision fused conv: src (n, cin) bf16 / fp16, wp = prepare_weights_h(...) of the same dtype."""
         if src.dtype not in self._HALF:
             raise TypeError("openpcseg_amd: conv_gather_gemm_h wants bfloat16 / float16 features, got %s" % src.dtype)
@@ -813,7 +824,7 @@ class HipBackend:
         if meta is not None and meta != ("half", src.dtype, k, cin, cout):
             raise ValueError("openpcseg_amd: prepared weights %s do not match this call (%s)" % (meta, ("half", src.dtype, k, cin, cout)))
         return self._conv_launch(self.lib.pcs_conv_gather_gemm_h_ex, src, wp, k, cin, cout, kmap, bias, tile_rows, bn_sums, ordered, bn_raw,
-                                 addend, act_slope, relu, code=self._HALF[src.dtype])
+                                 addend, act_slope, relu, code=self._HALF[src.dtype], post_scale=post_scale, post_shift=post_shift)
 
     # -- fp32 convolution on the 16-bit MFMAs (three bf16 planes per operand, opt-in) ------------------------------
     def conv_x3_applies(self, cin, cout, k):

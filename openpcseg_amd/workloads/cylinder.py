@@ -13,6 +13,9 @@ the kernel emits them -- the fusions block_fusion.py applies to the reference's 
 
 is one kernel per direction behind the three convolutions (fused.recon_gate, csrc/recongate.hip); PCS_RECON_GATE=0 and widths
 the kernel does not serve take the literal sequence. cy480 = init_size 32 (R:tools/cfgs/voxel/semantic_kitti/cylinder_cy480_cr10.yaml).
+Inference: after `openpcseg_amd.freeze(model)` every block triple is ONE launch -- the BatchNorm's running statistics ride as a
+per-column affine map behind the LeakyReLU, the residual behind that (inference.PostAffineConv) -- `up_subm` takes `+ skip` as
+its addend and the point MLPs run with their BatchNorms folded into the Linear layers (inference.FoldedDense).
 """
 import os
 
@@ -21,7 +24,7 @@ import torch
 from torch import nn
 
 from .. import functional as F
-from .. import fused, native
+from .. import fused, inference, native
 from .. import modules as spnn
 from ..block_fusion import _PointLinear
 from ..fused import FusedBatchNorm
@@ -46,8 +49,12 @@ def _dense_bn(bn, h, relu=False):
     return fused.bn_rows(bn, h, relu=relu)
 
 
-def _cab(conv, bn, x, residual=None, want_skip=False):
-    """conv -> LeakyReLU -> BatchNorm (+ residual) on a SparseTensor; -> (result, x routed through conv when want_skip)."""
+def _cab(conv, bn, x, residual=None, want_skip=False, frozen=None):
+    """conv -> LeakyReLU -> BatchNorm (+ residual) on a SparseTensor; -> (result, x routed through conv when want_skip).
+    frozen: the triple's inference.PostAffineConv while the owner's folded path applies -- one launch, no BatchNorm."""
+    if frozen is not None:
+        y = frozen(x, residual=residual)
+        return (y, x) if want_skip else y
     if CYL_FUSED and conv.bias is None and conv.kernel.dim() == 3 and F.conv_act_fusable(x.feats, conv.kernel):
         skip = want_skip and SKIP_FUSED and torch.is_grad_enabled() and x.feats.requires_grad
         out = F.conv3d(x, conv.kernel, kernel_size=conv.kernel_size, stride=conv.stride, dilation=conv.dilation,
@@ -67,6 +74,7 @@ def _conv(cin, cout, ks, stride=1, transposed=False, bias=False):
 
 class ResContextBlock(nn.Module):       # cylinder_ts.py:88-155
     first, second = (1, 3, 3), (3, 1, 3)
+    TRIPLES = (("conv1", "act1", "bn0"), ("conv1_2", "act1_2", "bn0_2"), ("conv2", "act2", "bn1"), ("conv3", "act3", "bn2"))
 
     def __init__(self, cin, cout, dist):
         super().__init__()
@@ -76,10 +84,11 @@ class ResContextBlock(nn.Module):       # cylinder_ts.py:88-155
         self.conv3, self.act3, self.bn2 = _conv(cout, cout, self.first), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
 
     def forward(self, x):
-        shortcut, xs = _cab(self.conv1, self.bn0, x, want_skip=True)
-        shortcut = _cab(self.conv1_2, self.bn0_2, shortcut)
-        res_a = _cab(self.conv2, self.bn1, xs)
-        return _cab(self.conv3, self.bn2, res_a, residual=shortcut)
+        fz = (inference.active(self) or {}).get
+        shortcut, xs = _cab(self.conv1, self.bn0, x, want_skip=True, frozen=fz("conv1"))
+        shortcut = _cab(self.conv1_2, self.bn0_2, shortcut, frozen=fz("conv1_2"))
+        res_a = _cab(self.conv2, self.bn1, xs, frozen=fz("conv2"))
+        return _cab(self.conv3, self.bn2, res_a, residual=shortcut, frozen=fz("conv3"))
 
 
 class ResBlock(ResContextBlock):        # cylinder_ts.py:158-250: the other order of the asymmetric pair, then `pool`
@@ -95,6 +104,8 @@ class ResBlock(ResContextBlock):        # cylinder_ts.py:158-250: the other orde
 
 
 class UpBlock(nn.Module):               # cylinder_ts.py:253-334
+    TRIPLES = (("trans_dilao", "trans_act", "trans_bn"), ("conv1", "act1", "bn1"), ("conv2", "act2", "bn2"), ("conv3", "act3", "bn3"))
+
     def __init__(self, cin, cout, dist, height_pooling):
         super().__init__()
         self.trans_dilao, self.trans_act, self.trans_bn = _conv(cin, cout, 3), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
@@ -104,11 +115,16 @@ class UpBlock(nn.Module):               # cylinder_ts.py:253-334
         self.up_subm = _conv(cout, cout, 3, stride=2 if height_pooling else (2, 2, 1), transposed=True)
 
     def forward(self, x, skip):
-        up_a = self.up_subm(_cab(self.trans_dilao, self.trans_bn, x))
-        up_a.F = up_a.F + skip.F
-        up_e = _cab(self.conv1, self.bn1, up_a)
-        up_e = _cab(self.conv2, self.bn2, up_e)
-        return _cab(self.conv3, self.bn3, up_e)
+        fz = (inference.active(self) or {}).get
+        up_a = _cab(self.trans_dilao, self.trans_bn, x, frozen=fz("trans_dilao"))
+        if fz("up_subm") is not None:
+            up_a = fz("up_subm")(up_a, residual=skip.F)   # + skip in the convolution's write-back
+        else:
+            up_a = self.up_subm(up_a)
+            up_a.F = up_a.F + skip.F
+        up_e = _cab(self.conv1, self.bn1, up_a, frozen=fz("conv1"))
+        up_e = _cab(self.conv2, self.bn2, up_e, frozen=fz("conv2"))
+        return _cab(self.conv3, self.bn3, up_e, frozen=fz("conv3"))
 
 
 class ReconBlock(nn.Module):            # cylinder_ts.py:337-384
@@ -176,6 +192,12 @@ class CylinderTS(nn.Module):
 
     def _point_mlp(self, x):
         pp = self.PPmodel
+        rec = inference.active(self)
+        if rec is not None and "pp" in rec:   # the four BatchNorms folded into the three Linear layers they surround
+            h = x
+            for lin in rec["pp"]:
+                h = torch.relu(lin(h))
+            return _linear(pp[10], h)
         h = _dense_bn(pp[0], x)
         for i in (1, 4, 7):
             h = _dense_bn(pp[i + 1], _linear(pp[i], h), relu=True)
@@ -214,8 +236,11 @@ class CylinderTS(nn.Module):
         if self.point_refinement:
             voxel_hash = F.sphash(batch["voxel_coord"].int())
             from_voxel = up0e.F[self._refine_rows(batch, up0e, voxel_hash)]
-            cd = self.change_dim
-            from_voxel = torch.nn.functional.leaky_relu(_dense_bn(cd[1], _linear(cd[0], from_voxel)), cd[2].negative_slope)
+            cd, rec = self.change_dim, inference.active(self)
+            if rec is not None and "cd" in rec:
+                from_voxel = torch.nn.functional.leaky_relu(rec["cd"](from_voxel), cd[2].negative_slope)
+            else:
+                from_voxel = torch.nn.functional.leaky_relu(_dense_bn(cd[1], _linear(cd[0], from_voxel)), cd[2].negative_slope)
             out["point_logits"] = _linear(self.point_logits, point_feature + from_voxel.to(point_feature.dtype))
         if self.training:
             if voxel_hash is None:

@@ -3,7 +3,9 @@
 synthetic scans: the ReconBlock gate alone -- the kernels of csrc/recongate.hip against the literal sequence they replace
 (three BatchNorm applies, three sigmoids, two adds, a multiply, and their autograd backward), forward and backward, fp32 and
 bf16 -- and one training step (forward, loss, backward, SGD update) in fp32 and under bf16 autocast with the gate kernel on and
-off (PCS_RECON_GATE).
+off (PCS_RECON_GATE). --eval: the evaluation forward (eval mode, no grad) of the same batch, unfrozen against
+`openpcseg_amd.freeze` (every conv -> LeakyReLU -> BatchNorm triple one launch, PCS_EP_POST_AFFINE), in fp32 and under bf16
+autocast; that section alone is measured and merged into the record --out already holds.
 
 Device events around blocks of calls / steps, the variants alternating block by block, the median of the blocks of a variant
 (three rounds by default), after a warm-up of every variant. The gate's bytes are ALGORITHMIC, counted from shapes: forward 4
@@ -119,6 +121,32 @@ def step_bench(args, batch):
                 "frames_per_s": round(frames / v * 1e3, 2)} for k, v in med.items()}
 
 
+def eval_bench(args, batch):
+    """Eval-mode forward, two models with the same weights: one as it is, one frozen. The traffic the frozen forward no longer
+    moves is counted from shapes: a triple's (N, C) output is neither read again nor written a second time, 2 N C e bytes."""
+    import openpcseg_amd
+    plain = CylinderTS(num_class=20, init_size=32).cuda().eval()
+    frozen = CylinderTS(num_class=20, init_size=32).cuda().eval()
+    frozen.load_state_dict(plain.state_dict())
+    report = openpcseg_amd.freeze(frozen)
+
+    def forward(model, amp):
+        def run():
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                model(batch)
+        return run
+
+    variants = {"fp32/unfrozen": forward(plain, False), "fp32/frozen": forward(frozen, False),
+                "bf16/unfrozen": forward(plain, True), "bf16/frozen": forward(frozen, True)}
+    med, spread = alternate(variants, args.steps, args.rounds, args.step_warmup)
+    frames = int(batch["point_coord"][:, -1].max()) + 1
+    out = {k: {"ms_per_forward": round(v, 2), "ms_min_max": [round(spread[k][0], 2), round(spread[k][1], 2)],
+               "frames_per_s": round(frames / v * 1e3, 2)} for k, v in med.items()}
+    out["freeze_report"] = report
+    out["frozen_speedup"] = {d: round(med[d + "/unfrozen"] / med[d + "/frozen"], 3) for d in ("fp32", "bf16")}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scans", type=int, default=2)
@@ -129,6 +157,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--step-warmup", type=int, default=2)
     ap.add_argument("--no-steps", action="store_true", help="the gate measurement only")
+    ap.add_argument("--eval", action="store_true", help="the eval forward, unfrozen against frozen, only; merged into --out")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                   "cylinder_workload_bench.json"))
     args = ap.parse_args()
@@ -145,8 +174,16 @@ def main():
     rec = {"device": torch.cuda.get_device_name(0), "scans": args.scans, "points": int(batch["point_coord"].shape[0]), "voxels": n,
            "rounds": args.rounds, "gate_reps": args.reps, "steps_per_block": args.steps,
            "method": "device events, alternating blocks, median block per variant"}
-    rec["gate"] = gate_bench(args, n, 64)
-    if not args.no_steps:
+    if args.eval:
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                rec = json.load(f)
+        rec["eval_forward"] = dict(eval_bench(args, batch), scans=args.scans, points=int(batch["point_coord"].shape[0]), voxels=n,
+                                   forwards_per_block=args.steps, rounds=args.rounds, device=torch.cuda.get_device_name(0))
+        print(json.dumps(rec["eval_forward"]), flush=True)
+    else:
+        rec["gate"] = gate_bench(args, n, 64)
+    if not args.no_steps and not args.eval:
         rec["training_step"] = step_bench(args, batch)
         print(json.dumps(rec["training_step"]), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
