@@ -208,7 +208,7 @@ class _PointLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .functional import _identity_map
+        from .functional import _identity_map, _weight_grad
         x, weight = ctx.saved_tensors
         dy = dy.contiguous()
         hd = ctx.hd
@@ -219,15 +219,8 @@ class _PointLinear(torch.autograd.Function):
             if len(_POINT_MAPS) > 4:
                 _POINT_MAPS.clear()
             km = _identity_map(x.shape[0], x.device, _POINT_MAPS)
-            be = native.backend()
-            xa, cin = x.contiguous(), x.shape[1]
-            if cin % 4:   # e.g. Cylinder_TS's first point layer, Linear(9, 64): zero columns bring the rows to 16-byte granularity
-                xa = torch.nn.functional.pad(xa, (0, (-cin) % 4))
-            if hd is not None:
-                gw = be.conv_wgrad_h(xa.to(hd), dy.to(hd), km, 0)[0]
-            else:
-                gw = be.conv_wgrad(xa.float(), dy.float(), km, 0)[0]
-            gw = gw[:cin].t().to(weight.dtype)
+            # pad_a: e.g. Cylinder_TS's first point layer, Linear(9, 64): zero columns bring the rows to 16-byte granularity
+            gw = _weight_grad(native.backend(), x.contiguous(), dy, km, 0, hd, pad_a=True)[0].t().to(weight.dtype)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = dy.float().sum(0).to(weight.dtype)
         return gx, gw, gb

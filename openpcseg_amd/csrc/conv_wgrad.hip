@@ -115,7 +115,6 @@ __device__ __forceinline__ void find_split_wave(const int32_t *koff, int K, int 
   *gsid = __shfl(incl - ns, src, 64) + sidx;
 }
 
-template <bool VEC>
 __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs w) {
   __shared__ __attribute__((aligned(16))) float abuf[WG_PB * WG_TS];
   __shared__ __attribute__((aligned(16))) float bbuf[WG_PB * WG_TS];
@@ -147,28 +146,13 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs w) {
       ib[tid] = w.a_col ? p.x : p.y;
     }
     __syncthreads();
-    if (VEC) {
-      for (int e = tid; e < WG_PB * (capad / 4); e += 256) {
-        const int r = e / (capad / 4), c4 = (e % (capad / 4)) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r < np && c4 < cat) v = *reinterpret_cast<const float4 *>(w.fa + (int64_t)ia[r] * w.ca + a0 + c4);
-        *reinterpret_cast<float4 *>(abuf + r * WG_TS + c4) = v;
-      }
-      for (int e = tid; e < WG_PB * (cbpad / 4); e += 256) {
-        const int r = e / (cbpad / 4), c4 = (e % (cbpad / 4)) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r < np && c4 < cbt) v = *reinterpret_cast<const float4 *>(w.fb + (int64_t)ib[r] * w.cb + b0 + c4);
-        *reinterpret_cast<float4 *>(bbuf + r * WG_TS + c4) = v;
-      }
-    } else {
-      for (int e = tid; e < WG_PB * capad; e += 256) {
-        const int r = e / capad, c = e % capad;
-        abuf[r * WG_TS + c] = (r < np && c < cat) ? w.fa[(int64_t)ia[r] * w.ca + a0 + c] : 0.f;
-      }
-      for (int e = tid; e < WG_PB * cbpad; e += 256) {
-        const int r = e / cbpad, c = e % cbpad;
-        bbuf[r * WG_TS + c] = (r < np && c < cbt) ? w.fb[(int64_t)ib[r] * w.cb + b0 + c] : 0.f;
-      }
+    for (int e = tid; e < WG_PB * capad; e += 256) {
+      const int r = e / capad, c = e % capad;
+      abuf[r * WG_TS + c] = (r < np && c < cat) ? w.fa[(int64_t)ia[r] * w.ca + a0 + c] : 0.f;
+    }
+    for (int e = tid; e < WG_PB * cbpad; e += 256) {
+      const int r = e / cbpad, c = e % cbpad;
+      bbuf[r * WG_TS + c] = (r < np && c < cbt) ? w.fb[(int64_t)ib[r] * w.cb + b0 + c] : 0.f;
     }
     __syncthreads();
     const int g = lane >> 4, l15 = lane & 15;
@@ -752,160 +736,176 @@ __global__ void __launch_bounds__(NT, NT == 256 ? (W3Mode<ET>::PLANES == 1 ? 3 :
     }
 }
 
-template <typename ET>
-int launch_wgrad3(const Wgrad3Args &w, int ns, hipStream_t st) {
-  const int nsa = (w.nag + 1) / 2;
-  const int nsy = nsa * w.nsb;
-  const dim3 grid = w.interleave == 2 ? dim3((unsigned)(8 * ((ns + 7) / 8) * nsy), 1u) : dim3((unsigned)ns, (unsigned)nsy);
-  const int na = w.aw / 16, nb = w.bw / 16;
-#define PCS_W3_CASE(A, B) if (na == A && nb == B) { hipLaunchKernelGGL((wgrad3_kernel<ET, A, B>), grid, dim3(256), 0, st, w); return check_launch("pcs_conv_wgrad(wgrad3)"); }
-  PCS_W3_CASE(4, 4) PCS_W3_CASE(4, 3) PCS_W3_CASE(4, 2) PCS_W3_CASE(4, 1)
-  PCS_W3_CASE(3, 4) PCS_W3_CASE(3, 3) PCS_W3_CASE(3, 2) PCS_W3_CASE(3, 1)
-  PCS_W3_CASE(2, 4) PCS_W3_CASE(2, 3) PCS_W3_CASE(2, 2) PCS_W3_CASE(2, 1)
-  PCS_W3_CASE(1, 4) PCS_W3_CASE(1, 3) PCS_W3_CASE(1, 2) PCS_W3_CASE(1, 1)
-#undef PCS_W3_CASE
-  set_error("pcs_conv_wgrad(wgrad3): unreachable");
-  return PCS_EINVAL;
+// Host side: one route decides kernel family, split plan, launch order and grid for every entry; the workspace query is derived
+// from the same function (DESIGN.md section 6 has the table).
+struct WgradEnv { int wgrad3, thin, target, interleave; };
+const WgradEnv &wgrad_env() {   // each value is read once
+  auto num = [](const char *v, int dflt) { return v ? atoi(v) : dflt; };
+  static const WgradEnv env = {num(getenv("PCS_WGRAD3"), 1),              // 0: wgrad2 always (A/B), 2: wgrad3 for every shape
+                               num(getenv("PCS_WGRAD3_THIN"), 1),         // 0: wgrad2 as before (A/B)
+                               num(getenv("PCS_WGRAD_TARGET"), 0),        // debug: workgroups per launch
+                               num(getenv("PCS_WGRAD_INTERLEAVE"), -1)};  // launch order of the splits, -1: by operand type
+  return env;
 }
 
-// thin half-operand shapes: the whole gradient block is one <= 64 x 64 tile -> one-wave workgroups (wgrad3_kernel<.., 64, 64>)
-inline bool wgrad3_thin(int ca, int cb, int dtype) {
-  static const int on = getenv("PCS_WGRAD3_THIN") ? atoi(getenv("PCS_WGRAD3_THIN")) : 1;  // 0: wgrad2 as before (A/B)
-  return on && dtype != 0 && ca % 16 == 0 && cb % 16 == 0 && ca <= 64 && cb <= 64 && ca >= 32 && cb >= 32;
-}
+int g_wgrad_interleave = -1;   // debug / A-B override of PCS_WGRAD_INTERLEAVE (pcs_debug_wgrad_interleave)
+enum class WgradFamily { generic, wgrad2, wgrad3, wgrad3_thin };
+// pch pairs per split, ns splits in the launch (= partial blocks in the workspace), interleave = launch order of the splits
+struct WgradPlan { WgradFamily family; int pch, ns, interleave; dim3 grid; };
 
-template <typename ET>
-int launch_wgrad3_thin(const Wgrad3Args &w, int ns, hipStream_t st) {
-  const dim3 grid((unsigned)(w.interleave == 2 ? 8 * ((ns + 7) / 8) : ns), 1);
-  const int na = w.aw / 16, nb = w.bw / 16;
-#define PCS_W3T_CASE(A, B) if (na == A && nb == B) { hipLaunchKernelGGL((wgrad3_kernel<ET, A, B, 64, 64>), grid, dim3(64), 0, st, w); return check_launch("pcs_conv_wgrad(wgrad3 thin)"); }
-  PCS_W3T_CASE(4, 4) PCS_W3T_CASE(4, 3) PCS_W3T_CASE(4, 2) PCS_W3T_CASE(3, 4) PCS_W3T_CASE(3, 3) PCS_W3T_CASE(3, 2)
-  PCS_W3T_CASE(2, 4) PCS_W3T_CASE(2, 3) PCS_W3T_CASE(2, 2)
-#undef PCS_W3T_CASE
-  set_error("pcs_conv_wgrad(wgrad3 thin): unreachable");
-  return PCS_EINVAL;
-}
-
-int wgrad_plan(const int32_t *koff_host, int K, int ca, int cb, int *pch_out, bool thin = false, bool half = false) {
-  // workgroup = 4 output blocks of one split; >= 64 pairs per split
-  const int nbq = (wg_ngroups(ca) * wg_ngroups(cb) + 3) / 4;
-  int64_t P = koff_host[K] - koff_host[0];
-  // measured per shape (tools/conv_microbench.py): ~3072 workgroups when an offset's weight block needs >= 4 of them
-  // (256-channel layers), ~1536 otherwise (64..128 channels: +2..16 %; fewer, longer splits = less partial traffic)
-  static const int tgt_env = getenv("PCS_WGRAD_TARGET") ? atoi(getenv("PCS_WGRAD_TARGET")) : 0;  // debug: workgroups per launch
-  // [r6] 16-bit operands on the 256-channel layers: ~2048 (profiles/round6_wgrad_target_sweep.txt: 256 x 256 0.289 -> 0.248 ms at
-  // stride 8, 0.144 -> 0.121 ms at stride 16 -- the kernel is 3x shorter than the fp32 one, the partial sums weigh more)
-  int64_t target = (tgt_env > 0 ? tgt_env : (nbq >= 4 ? (half ? 2048 : 3072) : 1536)) / nbq;
-  if (thin) target *= 4;   // one-wave workgroups: as many waves in flight as the four-wave form
-  if (target < K) target = K;
-  int pch = (int)ceil_div(P > 0 ? P : 1, target);
-  pch = (int)(ceil_div(pch, 32) * 32);
-  if (pch < 64) pch = 64;
+int wgrad_splits(const int32_t *koff_host, int K, int pch) {   // every offset's pairs cut into pieces of pch
   int64_t ns = 0;
   for (int k = 0; k < K; ++k) ns += ceil_div((int64_t)koff_host[k + 1] - koff_host[k], pch);
-  *pch_out = pch;
   return (int)ns;
 }
 
-}  // namespace
-
-extern "C" size_t pcs_conv_wgrad_ws_bytes(const int32_t *koff_host, int32_t K, int32_t ca,
-                                          int32_t cb) {
-  if (!koff_host || K <= 0 || ca <= 0 || cb <= 0) return 0;
-  int pch;
-  int ns = wgrad_plan(koff_host, K, ca, cb, &pch);
-  if (wgrad3_thin(ca, cb, 1)) {   // the query does not know the operand type: room for the thin plan's (more, shorter) splits too
-    const int ns_thin = wgrad_plan(koff_host, K, ca, cb, &pch, true);
-    ns = ns_thin > ns ? ns_thin : ns;
-  }
-  const int ns_half = wgrad_plan(koff_host, K, ca, cb, &pch, false, true);
-  ns = ns_half > ns ? ns_half : ns;
-  return (size_t)(ns > 0 ? ns : 1) * ca * cb * sizeof(float);
-}
-
-static int g_wgrad_interleave = -1;   // debug / A-B override of PCS_WGRAD_INTERLEAVE (pcs_debug_wgrad_interleave)
-extern "C" void pcs_debug_wgrad_interleave(int32_t mode) { g_wgrad_interleave = mode; }
-
-// dtype 0: fp32 operands; 1 / 2: bf16 / fp16 operands (the weight gradient is accumulated and returned in fp32)
-static int conv_wgrad_any(const void *fa_v, int32_t ca, const void *fb_v, int32_t cb,
-                          const int32_t *pairs, int32_t a_col, const int32_t *koff_dev,
-                          const int32_t *koff_host, int32_t K, float *gW, void *ws,
-                          size_t ws_bytes, int dtype, void *stream, bool force_split = false) {
-  const float *fa = reinterpret_cast<const float *>(fa_v), *fb = reinterpret_cast<const float *>(fb_v);
-  if (ca <= 0 || cb <= 0 || K <= 0 || !koff_dev || !koff_host || !gW || (a_col != 0 && a_col != 1) || dtype < 0 || dtype > 2) {
-    set_error("pcs_conv_wgrad_f32: bad args");
-    return PCS_EINVAL;
-  }
-  hipStream_t st = as_stream(stream);
-  int pch;
-  static const int use3_thin = getenv("PCS_WGRAD3") ? atoi(getenv("PCS_WGRAD3")) : 1;
-  const bool thin = use3_thin >= 1 && wgrad3_thin(ca, cb, dtype) && (((uintptr_t)fa_v | (uintptr_t)fb_v) & 15) == 0;
-  const int ns = wgrad_plan(koff_host, K, ca, cb, &pch, thin, dtype != 0);
-  const int64_t cc = (int64_t)ca * cb;
-  if (ns == 0) {
-    if (hipMemsetAsync(gW, 0, (size_t)K * cc * 4, st) != hipSuccess) { set_error("pcs_conv_wgrad_f32: memset failed"); return PCS_ELAUNCH; }
-    return PCS_OK;
-  }
-  if (!fa || !fb || !pairs || !ws) { set_error("pcs_conv_wgrad_f32: null pointer"); return PCS_EINVAL; }
-  if (ws_bytes < (size_t)ns * cc * 4) { set_error("pcs_conv_wgrad_f32: workspace too small"); return PCS_EWORKSPACE; }
-  WgradArgs w;
-  w.fa = fa; w.fb = fb; w.pairs = pairs; w.koff = koff_dev; w.partial = reinterpret_cast<float *>(ws);
-  w.ca = ca; w.cb = cb; w.K = K; w.a_col = a_col; w.pch = pch;
-  const bool vec = (ca % 4 == 0) && (cb % 4 == 0) && (((uintptr_t)fa | (uintptr_t)fb) & 15) == 0;
-  if (dtype != 0 && !vec) { set_error("pcs_conv_wgrad_h: half operands need channel counts that are multiples of 4 and 16-byte aligned tensors"); return PCS_EUNSUPPORTED; }
+// dtype 0: fp32 operands; 1 / 2: bf16 / fp16. operands_aligned: both operand tensors start on 16 bytes. use3: PCS_WGRAD3.
+// count = false leaves ns and the grid out (the workspace query wants pch alone: K divisions less per plan).
+WgradPlan wgrad_route(const int32_t *koff_host, int K, int ca, int cb, int dtype, bool force_split, bool operands_aligned,
+                      int use3 = wgrad_env().wgrad3, bool count = true) {
+  const WgradEnv &env = wgrad_env();
+  const bool half = dtype != 0;
+  const int nag = wg_ngroups(ca), nbg = wg_ngroups(cb);
+  WgradPlan p;
+  // thin half-operand shapes: the whole gradient block is one <= 64 x 64 tile -> one-wave workgroups (wgrad3_kernel<.., 64, 64>)
+  const bool thin = use3 >= 1 && env.thin && half && ca % 16 == 0 && cb % 16 == 0 && ca <= 64 && cb <= 64 && ca >= 32 && cb >= 32 &&
+                    operands_aligned;
+  const bool vec = (ca % 4 == 0) && (cb % 4 == 0) && operands_aligned;
   // 16-bit MFMA path (wgrad3): 16-byte row pieces in both operands. PCS_WGRAD3=0 keeps the fp32-MFMA kernel (A/B, debug).
   // Policy (tools/wgrad_microbench.py, profiles/round2_wgrad3_microbench.md): half operands with >= 4 output blocks
   // (all four waves of a super-block busy) take wgrad3 -- 2.7-3.4x the fp32-MFMA kernel. fp32 operands keep the exact
   // fp32-MFMA kernel (wgrad2) by default: the three-plane split is 1.3-1.4x faster on the >= 96-channel layers and
   // fp32-grade, but the fp32 path of this library stays on fp32 arithmetic unless the caller opts in
   // (pcs_conv_wgrad_f32_bf16x3, or PCS_WGRAD3=2 for every shape). PCS_WGRAD3=0: wgrad2 always (A/B).
-  static const int use3 = getenv("PCS_WGRAD3") ? atoi(getenv("PCS_WGRAD3")) : 1;
+  const int cgran = half ? 8 : 4;
+  const bool want3 = !half ? (use3 == 2 || force_split) : (use3 >= 1 && (use3 == 2 || nag * nbg >= 4));
+  p.family = thin ? WgradFamily::wgrad3_thin
+                  : (vec && want3 && ca % cgran == 0 && cb % cgran == 0) ? WgradFamily::wgrad3
+                                                                         : (vec ? WgradFamily::wgrad2 : WgradFamily::generic);
+  // workgroup = 4 output blocks of one split; >= 64 pairs per split
+  const int nbq = (nag * nbg + 3) / 4;
+  const int64_t P = koff_host[K] - koff_host[0];
+  // measured per shape (tools/conv_microbench.py): ~3072 workgroups when an offset's weight block needs >= 4 of them
+  // (256-channel layers), ~1536 otherwise (64..128 channels: +2..16 %; fewer, longer splits = less partial traffic)
+  // [r6] 16-bit operands on the 256-channel layers: ~2048 (profiles/round6_wgrad_target_sweep.txt: 256 x 256 0.289 -> 0.248 ms at
+  // stride 8, 0.144 -> 0.121 ms at stride 16 -- the kernel is 3x shorter than the fp32 one, the partial sums weigh more)
+  int64_t target = (env.target > 0 ? env.target : (nbq >= 4 ? (half ? 2048 : 3072) : 1536)) / nbq;
+  if (thin) target *= 4;   // one-wave workgroups: as many waves in flight as the four-wave form
+  if (target < K) target = K;
+  p.pch = (int)ceil_div(P > 0 ? P : 1, target);
+  p.pch = (int)(ceil_div(p.pch, 32) * 32);
+  if (p.pch < 64) p.pch = 64;
+  p.ns = count ? wgrad_splits(koff_host, K, p.pch) : 0;
   // launch order of the splits (find_split_wave): 0 offset-major, 1 position-major, 2 position-major with every XCD on its own
   // contiguous eighth of the sequence. Measured [r6, profiles/round6_wgrad_interleave_ab{,2}.txt], bit-identical results: 1 is
   // neutral (0.94-1.05x); 2 is 1.04-1.31x on the 16-bit kernel (3.05 -> 2.56 ms over the shapes of a step: all offsets of a stretch
   // of rows meet in ONE L2 instead of the Infinity Cache) and neutral / 0.90x on the MFMA-bound fp32 kernel -> 2 for half operands
-  static const int interleave_env = getenv("PCS_WGRAD_INTERLEAVE") ? atoi(getenv("PCS_WGRAD_INTERLEAVE")) : -1;
-  const int interleave = g_wgrad_interleave >= 0 ? g_wgrad_interleave : (interleave_env >= 0 ? interleave_env : (dtype != 0 ? 2 : 0));
-  const int cgran = dtype == 0 ? 4 : 8;
-  const bool want3 = dtype == 0 ? (use3 == 2 || force_split) : (use3 >= 1 && (use3 == 2 || wg_ngroups(ca) * wg_ngroups(cb) >= 4));
-  if (thin) {
-    Wgrad3Args w3;
-    w3.fa = fa_v; w3.fb = fb_v; w3.pairs = pairs; w3.koff = koff_dev; w3.partial = reinterpret_cast<float *>(ws);
-    w3.ca = ca; w3.cb = cb; w3.K = K; w3.a_col = a_col; w3.pch = pch;
-    w3.aw = wg_gwidth(ca); w3.bw = wg_gwidth(cb); w3.nag = 1; w3.nbg = 1; w3.nsb = 1; w3.interleave = interleave;
-    int rc3 = dtype == 1 ? launch_wgrad3_thin<Bf16>(w3, ns, st) : launch_wgrad3_thin<Fp16>(w3, ns, st);
-    if (rc3) return rc3;
-  } else if (vec && want3 && ca % cgran == 0 && cb % cgran == 0) {
-    Wgrad3Args w3;
-    w3.fa = fa_v; w3.fb = fb_v; w3.pairs = pairs; w3.koff = koff_dev; w3.partial = reinterpret_cast<float *>(ws);
-    w3.ca = ca; w3.cb = cb; w3.K = K; w3.a_col = a_col; w3.pch = pch;
-    w3.aw = wg_gwidth(ca); w3.bw = wg_gwidth(cb); w3.nag = wg_ngroups(ca); w3.nbg = wg_ngroups(cb); w3.nsb = (w3.nbg + 1) / 2;
-    w3.interleave = interleave;
-    w3.nsy = ((w3.nag + 1) / 2) * w3.nsb;
-    int rc3 = dtype == 0 ? launch_wgrad3<Fp32>(w3, ns, st) : (dtype == 1 ? launch_wgrad3<Bf16>(w3, ns, st) : launch_wgrad3<Fp16>(w3, ns, st));
-    if (rc3) return rc3;
-  } else if (vec) {
-    Wgrad2Args w2;
-    w2.fa = fa; w2.fb = fb; w2.pairs = pairs; w2.koff = koff_dev; w2.partial = reinterpret_cast<float *>(ws);
-    w2.ca = ca; w2.cb = cb; w2.K = K; w2.a_col = a_col; w2.pch = pch; w2.nbg = wg_ngroups(cb); w2.interleave = interleave;
-    const dim3 grid2((unsigned)(interleave == 2 ? 8 * ((ns + 7) / 8) : ns), (unsigned)(((wg_ngroups(ca) + 1) / 2) * ((wg_ngroups(cb) + 1) / 2)));
-    if (dtype == 0) hipLaunchKernelGGL(wgrad2_kernel<Fp32>, grid2, dim3(256), 0, st, w2);
-    else if (dtype == 1) hipLaunchKernelGGL(wgrad2_kernel<Bf16>, grid2, dim3(256), 0, st, w2);
-    else hipLaunchKernelGGL(wgrad2_kernel<Fp16>, grid2, dim3(256), 0, st, w2);
-  } else {
-    dim3 grid((unsigned)ns, (unsigned)ceil_div(ca, 128), (unsigned)ceil_div(cb, 128));
-    hipLaunchKernelGGL(wgrad_kernel<false>, grid, dim3(256), 0, st, w);
+  p.interleave = g_wgrad_interleave >= 0 ? g_wgrad_interleave : (env.interleave >= 0 ? env.interleave : (half ? 2 : 0));
+  // order 2 pads the splits to whole rounds of the 8 XCDs; there wgrad3 also folds its super-blocks (2 x 2 channel groups each)
+  // into the one launch dimension. The generic kernel knows no launch order.
+  const unsigned nx = (unsigned)(p.interleave == 2 ? 8 * ((p.ns + 7) / 8) : p.ns), nsy = (unsigned)(((nag + 1) / 2) * ((nbg + 1) / 2));
+  if (p.family == WgradFamily::generic) p.grid = dim3((unsigned)p.ns, (unsigned)ceil_div(ca, 128), (unsigned)ceil_div(cb, 128));
+  else if (p.family == WgradFamily::wgrad2) p.grid = dim3(nx, nsy);
+  else p.grid = p.interleave == 2 ? dim3(nx * nsy, 1u) : dim3((unsigned)p.ns, nsy);   // thin: nsy = 1
+  return p;
+}
+
+// the fields that WgradArgs, Wgrad2Args and Wgrad3Args share
+template <typename Args>
+Args wgrad_args(const void *fa, const void *fb, const int32_t *pairs, const int32_t *koff_dev, void *ws, int ca, int cb, int K,
+                int a_col, int pch) {
+  Args w;
+  w.fa = static_cast<decltype(w.fa)>(fa); w.fb = static_cast<decltype(w.fb)>(fb); w.pairs = pairs; w.koff = koff_dev;
+  w.partial = reinterpret_cast<float *>(ws);
+  w.ca = ca; w.cb = cb; w.K = K; w.a_col = a_col; w.pch = pch;
+  return w;
+}
+
+// one (na, nb) table for both instances of wgrad3: the four-wave one (NT = 256, ROW = W3_ROW) exists for all 16 pairs, the thin
+// one (NT = ROW = 64) for the 9 with na, nb >= 2
+template <typename ET, int NT, int ROW>
+int launch_wgrad3(const Wgrad3Args &w, dim3 grid, hipStream_t st, const char *what) {
+  const int na = w.aw / 16, nb = w.bw / 16;
+#define PCS_W3_CASE(A, B) if constexpr (NT == 256 || (A >= 2 && B >= 2)) if (na == A && nb == B) { hipLaunchKernelGGL((wgrad3_kernel<ET, A, B, NT, ROW>), grid, dim3(NT), 0, st, w); return check_launch(what); }
+  PCS_W3_CASE(4, 4) PCS_W3_CASE(4, 3) PCS_W3_CASE(4, 2) PCS_W3_CASE(4, 1)
+  PCS_W3_CASE(3, 4) PCS_W3_CASE(3, 3) PCS_W3_CASE(3, 2) PCS_W3_CASE(3, 1)
+  PCS_W3_CASE(2, 4) PCS_W3_CASE(2, 3) PCS_W3_CASE(2, 2) PCS_W3_CASE(2, 1)
+  PCS_W3_CASE(1, 4) PCS_W3_CASE(1, 3) PCS_W3_CASE(1, 2) PCS_W3_CASE(1, 1)
+#undef PCS_W3_CASE
+  set_error("%s: unreachable", what);
+  return PCS_EINVAL;
+}
+
+}  // namespace
+
+// Room for the most splits of any plan the route can return for this map and these widths: the query knows neither the operand
+// type, their alignment nor the entry, so it walks the route's inputs (PCS_WGRAD3 too: both sides of that A/B allocate alike).
+// The most splits are those of the fewest pairs per split.
+extern "C" size_t pcs_conv_wgrad_ws_bytes(const int32_t *koff_host, int32_t K, int32_t ca, int32_t cb) {
+  if (!koff_host || K <= 0 || ca <= 0 || cb <= 0) return 0;
+  int pch = INT_MAX;
+  for (int dtype = 0; dtype <= 2; ++dtype)
+    for (int in = 0; in < 4; ++in)   // force_split x operands_aligned
+      for (int use3 = 0; use3 <= 2; ++use3) pch = std::min(pch, wgrad_route(koff_host, K, ca, cb, dtype, in & 1, in & 2, use3, false).pch);
+  return (size_t)std::max(wgrad_splits(koff_host, K, pch), 1) * ca * cb * sizeof(float);
+}
+
+extern "C" void pcs_debug_wgrad_interleave(int32_t mode) { g_wgrad_interleave = mode; }
+
+// dtype 0: fp32 operands; 1 / 2: bf16 / fp16 operands (the weight gradient is accumulated and returned in fp32)
+static int conv_wgrad_any(const void *fa, int32_t ca, const void *fb, int32_t cb, const int32_t *pairs, int32_t a_col,
+                          const int32_t *koff_dev, const int32_t *koff_host, int32_t K, float *gW, void *ws, size_t ws_bytes,
+                          int dtype, void *stream, bool force_split = false) {
+  if (ca <= 0 || cb <= 0 || K <= 0 || !koff_dev || !koff_host || !gW || (a_col != 0 && a_col != 1) || dtype < 0 || dtype > 2) {
+    set_error("pcs_conv_wgrad_f32: bad args");
+    return PCS_EINVAL;
+  }
+  hipStream_t st = as_stream(stream);
+  const WgradPlan p = wgrad_route(koff_host, K, ca, cb, dtype, force_split, (((uintptr_t)fa | (uintptr_t)fb) & 15) == 0);
+  const int64_t cc = (int64_t)ca * cb;
+  if (p.ns == 0) {
+    if (hipMemsetAsync(gW, 0, (size_t)K * cc * 4, st) != hipSuccess) { set_error("pcs_conv_wgrad_f32: memset failed"); return PCS_ELAUNCH; }
+    return PCS_OK;
+  }
+  if (!fa || !fb || !pairs || !ws) { set_error("pcs_conv_wgrad_f32: null pointer"); return PCS_EINVAL; }
+  if (ws_bytes < (size_t)p.ns * cc * 4) { set_error("pcs_conv_wgrad_f32: workspace too small"); return PCS_EWORKSPACE; }
+  const bool vec = p.family != WgradFamily::generic;   // 16-byte granular rows on aligned tensors
+  if (dtype != 0 && !vec) { set_error("pcs_conv_wgrad_h: half operands need channel counts that are multiples of 4 and 16-byte aligned tensors"); return PCS_EUNSUPPORTED; }
+  switch (p.family) {
+    case WgradFamily::generic:
+      hipLaunchKernelGGL(wgrad_kernel, p.grid, dim3(256), 0, st, wgrad_args<WgradArgs>(fa, fb, pairs, koff_dev, ws, ca, cb, K, a_col, p.pch));
+      break;
+    case WgradFamily::wgrad2: {
+      Wgrad2Args w = wgrad_args<Wgrad2Args>(fa, fb, pairs, koff_dev, ws, ca, cb, K, a_col, p.pch);
+      w.nbg = wg_ngroups(cb); w.interleave = p.interleave;
+      if (dtype == 0) hipLaunchKernelGGL(wgrad2_kernel<Fp32>, p.grid, dim3(256), 0, st, w);
+      else if (dtype == 1) hipLaunchKernelGGL(wgrad2_kernel<Bf16>, p.grid, dim3(256), 0, st, w);
+      else hipLaunchKernelGGL(wgrad2_kernel<Fp16>, p.grid, dim3(256), 0, st, w);
+      break;
+    }
+    default: {   // wgrad3, four-wave or thin (one channel group per operand there: nag = nbg = nsb = nsy = 1)
+      Wgrad3Args w = wgrad_args<Wgrad3Args>(fa, fb, pairs, koff_dev, ws, ca, cb, K, a_col, p.pch);
+      w.aw = wg_gwidth(ca); w.bw = wg_gwidth(cb); w.nag = wg_ngroups(ca); w.nbg = wg_ngroups(cb); w.nsb = (w.nbg + 1) / 2;
+      w.interleave = p.interleave;
+      w.nsy = ((w.nag + 1) / 2) * w.nsb;
+      const bool thin = p.family == WgradFamily::wgrad3_thin;
+      const char *what = thin ? "pcs_conv_wgrad(wgrad3 thin)" : "pcs_conv_wgrad(wgrad3)";
+      const int rc3 = thin ? (dtype == 1 ? launch_wgrad3<Bf16, 64, 64>(w, p.grid, st, what) : launch_wgrad3<Fp16, 64, 64>(w, p.grid, st, what))
+                      : dtype == 0 ? launch_wgrad3<Fp32, 256, W3_ROW>(w, p.grid, st, what)
+                      : dtype == 1 ? launch_wgrad3<Bf16, 256, W3_ROW>(w, p.grid, st, what) : launch_wgrad3<Fp16, 256, W3_ROW>(w, p.grid, st, what);
+      if (rc3) return rc3;
+    }
   }
   int rc = check_launch("pcs_conv_wgrad_f32");
   if (rc) return rc;
   if (vec && (((uintptr_t)ws | (uintptr_t)gW) & 15) == 0) {
     hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)ceil_div(cc, 64), K), dim3(256), 0, st,
-                       reinterpret_cast<const float *>(ws), koff_dev, (int)K, pch, cc, gW);
+                       reinterpret_cast<const float *>(ws), koff_dev, (int)K, p.pch, cc, gW);
   } else {
     int gx = (int)ceil_div(cc, 256);
     if (gx > 64) gx = 64;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(gx, K), dim3(256), 0, st,
-                       reinterpret_cast<const float *>(ws), koff_dev, (int)K, pch, cc, gW);
+                       reinterpret_cast<const float *>(ws), koff_dev, (int)K, p.pch, cc, gW);
   }
   return check_launch("pcs_conv_wgrad_f32(reduce)");
 }

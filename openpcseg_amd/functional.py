@@ -531,16 +531,26 @@ class _SparseConv(Function):
         elif grad_skip is not None:
             grad_input = grad_skip
         if need_dw:
-            # fwd pairs are (in_row, out_row) of the NON-transposed conv; a transposed conv's
-            # input lives on the out rows (column 1)
+            # fwd pairs are (in_row, out_row) of the NON-transposed conv; a transposed conv's input lives on the out rows (column 1)
             a_col = 1 if transposed else 0
-            if x.dtype in _HALF and cin % 4 == 0 and cout % 4 == 0:
-                grad_weight = be.conv_wgrad_h(x, grad_output.contiguous().to(x.dtype), entry.fwd, a_col)
-            else:
-                grad_weight = be.conv_wgrad(x.float(), grad_output.contiguous().float(), entry.fwd, a_col,
-                                            split=_wgrad_split(cin, cout))
+            grad_weight = _weight_grad(be, x, grad_output.contiguous(), entry.fwd, a_col, x.dtype, split=_wgrad_split(cin, cout))
             grad_weight = grad_weight.view_as(weight).to(weight.dtype)
         return grad_input, grad_weight, None, None, None, None, None
+
+
+def _weight_grad(be, fa, fb, kmap, a_col, hd, *, split=False, pad_a=False, pad_b=False):
+    """The weight gradient of every layer kind: sum over the map's pairs of fa[row a]^T (x) fb[row b] -> (K, ca, cb) in fp32. The entry
+    rule, stated once: the half entry (be.conv_wgrad_h) if and only if hd is a half dtype, the backend has that entry and both widths are
+    multiples of 4; else both operands go to fp32 and take be.conv_wgrad, with `split` (the bf16x3 policy) passed only there. pad_a /
+    pad_b: first zero columns bring that operand's width to a multiple of 4; their rows / columns of the result are cut off again."""
+    ca, cb = fa.shape[1], fb.shape[1]
+    fa = torch.nn.functional.pad(fa, (0, (-ca) % 4)) if pad_a and ca % 4 else fa
+    fb = torch.nn.functional.pad(fb, (0, (-cb) % 4)) if pad_b and cb % 4 else fb
+    if hd in _HALF and hasattr(be, "conv_wgrad_h") and fa.shape[1] % 4 == 0 and fb.shape[1] % 4 == 0:
+        gw = be.conv_wgrad_h(fa.to(hd), fb.to(hd), kmap, a_col)
+    else:
+        gw = be.conv_wgrad(fa.float(), fb.float(), kmap, a_col, split=split)
+    return gw if gw.shape[1:] == (ca, cb) else gw[:, :ca, :cb]
 
 
 def conv_act_fusable(feats, weight):
@@ -593,20 +603,10 @@ class _PointwiseConv(Function):
                 gin = grad_output.to(hd).matmul(weight.to(hd).t())
         if ctx.needs_input_grad[1]:
             km = _identity_map(feats.shape[0], feats.device, ctx.cache)
-            ca, cb = feats.shape[1], grad_output.shape[1]
-            fa, gb = feats.contiguous(), grad_output
-            pa, pb = (-ca) % 4, (-cb) % 4
-            if (pa or pb) and feats.is_cuda and ca + pa >= 32:
-                # widths that are not 16-byte granular (cr 1.6: 153, 409, 613 ...): zero columns bring the operands onto the MFMA
-                # weight-gradient kernels (the generic kernel ran these 1x1x1 layers at 16-19 TFLOP/s); the padding's rows /
-                # columns of the result are cut off again
-                fa = torch.nn.functional.pad(fa, (0, pa)) if pa else fa
-                gb = torch.nn.functional.pad(gb, (0, pb)) if pb else gb
-            if hd is not None and fa.shape[1] % 4 == 0 and gb.shape[1] % 4 == 0:
-                gw = _be().conv_wgrad_h(fa.to(hd), gb.to(hd), km, 0)[0]
-            else:
-                gw = _be().conv_wgrad(fa.float(), gb.float(), km, 0)[0]
-            gw = gw[:ca, :cb].to(weight.dtype)
+            # widths that are not 16-byte granular (cr 1.6: 153, 409, 613 ...): zero columns bring the operands onto the MFMA
+            # weight-gradient kernels (the generic kernel ran these 1x1x1 layers at 16-19 TFLOP/s)
+            pad = feats.is_cuda and feats.shape[1] + (-feats.shape[1]) % 4 >= 32
+            gw = _weight_grad(_be(), feats.contiguous(), grad_output, km, 0, hd, pad_a=pad, pad_b=pad)[0].to(weight.dtype)
         return gin, gw, None
 
 

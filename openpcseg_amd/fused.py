@@ -274,6 +274,7 @@ class _SkinnyLinear(Function):
 
     @staticmethod
     def backward(ctx, dy):
+        from .functional import _weight_grad
         be = native.backend()
         x, weight = ctx.saved_tensors
         dy = dy.contiguous()
@@ -281,11 +282,7 @@ class _SkinnyLinear(Function):
         if ctx.needs_input_grad[0]:
             dx = be.conv_gather_gemm(dy.float(), weight.detach().float().contiguous().unsqueeze(0), ctx.km)
         if ctx.needs_input_grad[1]:
-            if x.dtype != torch.float32 and x.shape[1] % 4 == 0 and dy.shape[1] % 4 == 0:
-                dw = be.conv_wgrad_h(x, dy.to(x.dtype), ctx.km, 0)[0].t()
-            else:
-                dw = be.conv_wgrad(x.float(), dy.float(), ctx.km, 0)[0].t()
-            dw = dw.to(weight.dtype)
+            dw = _weight_grad(be, x, dy, ctx.km, 0, x.dtype)[0].t().to(weight.dtype)
         if ctx.needs_input_grad[2]:
             db = dy.float().sum(0)
         return dx, dw, db, None, None
@@ -322,6 +319,7 @@ class _SkinnyLinearParts(Function):
 
     @staticmethod
     def backward(ctx, dy):
+        from .functional import _weight_grad
         be = native.backend()
         weight, parts = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         dy32 = dy.contiguous().float()
@@ -334,10 +332,7 @@ class _SkinnyLinearParts(Function):
                 dx = be.conv_gather_gemm(dy32, w[:, col:col + cin].contiguous().unsqueeze(0), ctx.km)
             grads.append(dx)
             if ctx.needs_input_grad[0]:
-                if x.dtype != torch.float32 and cin % 4 == 0 and dy.shape[1] % 4 == 0:
-                    dws.append(be.conv_wgrad_h(x, dy32.to(x.dtype), ctx.km, 0)[0].t())
-                else:
-                    dws.append(be.conv_wgrad(x.float(), dy32, ctx.km, 0)[0].t())
+                dws.append(_weight_grad(be, x, dy32, ctx.km, 0, x.dtype)[0].t())
             col += cin
         dw = torch.cat(dws, dim=1).to(weight.dtype) if ctx.needs_input_grad[0] else None
         db = dy32.sum(0) if (ctx.has_bias and ctx.needs_input_grad[1]) else None

@@ -859,15 +859,8 @@ class HipBackend:
         """Weight gradient from half operands, accumulated and returned in fp32 (K, ca, cb)."""
         if fa.dtype not in self._HALF or fb.dtype != fa.dtype:
             raise TypeError("openpcseg_amd: conv_wgrad_h wants two tensors of the same half dtype")
-        fa, fb = _dev(fa, "input"), _dev(fb, "grad_output")
-        ca, cb = fa.shape[1], fb.shape[1]
-        gw = torch.empty((kmap.K, ca, cb), dtype=torch.float32, device=fa.device)
-        ws_bytes = self.lib.pcs_conv_wgrad_ws_bytes(kmap._koff_c, kmap.K, ca, cb)
-        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=fa.device)
-        _check(self.lib.pcs_conv_wgrad_h(_ptr(fa), ca, _ptr(fb), cb, _ptr(kmap.pairs), a_col, _ptr(kmap.koff),
-                                         kmap._koff_c, kmap.K, _ptr(gw), _ptr(ws), ws_bytes, self._HALF[fa.dtype],
-                                         _stream()), "pcs_conv_wgrad_h")
-        return gw
+        return self._wgrad_launch(self.lib.pcs_conv_wgrad_h, _dev(fa, "input"), _dev(fb, "grad_output"), kmap, a_col,
+                                  self._HALF[fa.dtype])
 
     def transpose_weights(self, w):
         """(K, A, B) -> (K, B, A) contiguous: the weights dgrad contracts with."""
@@ -922,17 +915,19 @@ class HipBackend:
     def conv_wgrad(self, fa, fb, kmap, a_col, split=False):
         """gW[k] = sum_{pairs of k} fa[pair[a_col]]^T (x) fb[pair[1-a_col]] -> (K, ca, cb). split=True: the operands go
         through the bf16 MFMAs as three bf16 planes each (fp32-grade result, pcs_conv_wgrad_f32_bf16x3)."""
-        fa = _dev(fa, "input", torch.float32)
-        fb = _dev(fb, "grad_output", torch.float32)
+        fn = self.lib.pcs_conv_wgrad_f32_bf16x3 if split else self.lib.pcs_conv_wgrad_f32
+        return self._wgrad_launch(fn, _dev(fa, "input", torch.float32), _dev(fb, "grad_output", torch.float32), kmap, a_col)
+
+    def _wgrad_launch(self, fn, fa, fb, kmap, a_col, *tail):
+        """The body both weight-gradient entries share: fp32 (K, ca, cb) output, a workspace of the size the library asks for, the
+        call. tail: what the entry takes between the workspace size and the stream (the half entry's dtype code)."""
         ca, cb = fa.shape[1], fb.shape[1]
         gw = torch.empty((kmap.K, ca, cb), dtype=torch.float32, device=fa.device)
         ws_bytes = self.lib.pcs_conv_wgrad_ws_bytes(kmap._koff_c, kmap.K, ca, cb)
         ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=fa.device)
-        fn = self.lib.pcs_conv_wgrad_f32_bf16x3 if split else self.lib.pcs_conv_wgrad_f32
         _check(fn(_ptr(fa), ca, _ptr(fb), cb, _ptr(kmap.pairs), a_col, _ptr(kmap.koff), kmap._koff_c, kmap.K, _ptr(gw),
-                  _ptr(ws), ws_bytes, _stream()), "pcs_conv_wgrad_f32")
+                  _ptr(ws), ws_bytes, *tail, _stream()), "pcs_conv_wgrad_h" if tail else "pcs_conv_wgrad_f32")
         return gw
-
 
     # -- cylinder / range scatter ---------------------------------------------------------------
     def _csr(self, index, m):

@@ -22,7 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from stage_reference import reference_root  # noqa: E402
 from test_reference_models import _Env, _load, _np  # noqa: E402
 
-REFERENCE_FREE = {"test_dense_linear_and_batchnorm_match_torch_on_hip"}   # stock torch modules only
+REFERENCE_FREE = {"test_dense_linear_and_batchnorm_match_torch_on_hip",   # stock torch modules only
+                  "test_point_linear_weight_gradient_off_the_half_entry_under_autocast"}
 
 
 @pytest.fixture(autouse=True)
@@ -498,6 +499,32 @@ def test_dense_linear_and_batchnorm_match_torch_on_hip(hip, cin, cout):
     small = torch.randn(100, cin, device="cuda")
     assert torch.allclose(plain.eval()(small), fused.eval()(small), atol=1e-5)
     assert torch.allclose(plain(x), fused(x), atol=2e-5 * float(y0.abs().max()))
+
+
+@pytest.mark.gpu
+def test_point_linear_weight_gradient_off_the_half_entry_under_autocast(hip):
+    """_PointLinear under bf16 autocast with Linear(8, 6) on 257 rows: the output width is no multiple of 4, so the weight gradient
+    takes the fp32 entry on the bf16-rounded operands (the half entry refuses such a width). Against x^T dy in float64 of the same
+    rounded operands, at the fp32 weight-gradient bound of the suite (2e-5 of the maximum: fp32 summation order over 257 products
+    of exact bf16 x bf16 terms); bit-identical on a second call."""
+    from openpcseg_amd import block_fusion as fz
+    g = torch.Generator().manual_seed(11)
+    x = (torch.randn(257, 8, generator=g) * 2 + 0.5).cuda()
+    coef = torch.randn(257, 6, generator=g).cuda()
+    lin = torch.nn.Linear(8, 6).cuda()
+    grads = []
+    for _ in range(2):
+        lin.zero_grad()
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            y = fz._PointLinear.apply(x, lin.weight, lin.bias)
+        assert y.dtype == torch.bfloat16
+        (y.float() * coef).sum().backward()   # the layer is handed dy = coef rounded to bf16
+        grads.append(lin.weight.grad.clone())
+    want = (x.bfloat16().double().t() @ coef.bfloat16().double()).t()
+    err = float((grads[0].double() - want).abs().max()) / float(want.abs().max())
+    print("point linear 8 -> 6 weight gradient: %.3g" % err)
+    assert grads[0].dtype == torch.float32 and grads[0].shape == (6, 8) and err <= 2e-5, err
+    assert torch.equal(grads[0], grads[1])
 
 
 def test_checkpoint_round_trip_in_the_reference_format(golden_e2e, env_oracle, tmp_path):

@@ -1132,7 +1132,7 @@ def test_half_paths_empty_and_ragged(hip, dtype):
         gw = hip.conv_wgrad_h(xd, xd, entry.fwd, 0)  # 128 x 128: wgrad3
         close(gw[13], x.float().numpy().T @ x.float().numpy(), 2e-5)
         assert float(gw[0].abs().max()) == 0.0 and float(gw[26].abs().max()) == 0.0
-        gw2 = hip.conv_wgrad_h(xd[:, :32].contiguous(), xd[:, :32].contiguous(), entry.fwd, 0)  # 32 x 32: wgrad2<half>
+        gw2 = hip.conv_wgrad_h(xd[:, :32].contiguous(), xd[:, :32].contiguous(), entry.fwd, 0)  # 32 x 32: the thin wgrad3 instance
         close(gw2[13], x.float().numpy()[:, :32].T @ x.float().numpy()[:, :32], 2e-5)
         xf = xd.float()
         close(hip.conv_wgrad(xf, xf, entry.fwd, 0, split=True)[13], x.float().numpy().T @ x.float().numpy(), 2e-5)

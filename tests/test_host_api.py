@@ -817,3 +817,113 @@ def test_fused_batchnorm_has_the_dtype_rules_of_bn_forward(training):
                 assert got.dtype == torch.float32 and got.shape == want.shape == (_BN_N, 2 * c if "cat_with" in kw else c)
                 assert float((got.detach() - want).abs().max()) <= 1e-5, sorted(kw)
                 assert torch.allclose(bn.running_mean, ref.running_mean, atol=1e-6) and torch.allclose(bn.running_var, ref.running_var, atol=1e-6)
+
+
+# ---- one weight-gradient entry for every layer kind (functional._weight_grad) ---------------------------------------------------
+class _WgradStub:
+    """A backend of which only the two weight-gradient entries exist; they record (entry, operand dtypes, operand shapes, a_col,
+    split) and return zeros."""
+
+    def __init__(self, half_entry=True):
+        self.calls = []
+        if half_entry:
+            self.conv_wgrad_h = lambda fa, fb, kmap, a_col: self._record("conv_wgrad_h", fa, fb, kmap, a_col, None)
+
+    def conv_wgrad(self, fa, fb, kmap, a_col, split=False):
+        return self._record("conv_wgrad", fa, fb, kmap, a_col, split)
+
+    def _record(self, name, fa, fb, kmap, a_col, split):
+        self.calls.append((name, (fa.dtype, fb.dtype), (tuple(fa.shape), tuple(fb.shape)), a_col, split))
+        return torch.zeros((kmap.K, fa.shape[1], fb.shape[1]))
+
+
+_WG_N = 5
+
+
+def _wgrad_sites():
+    """name -> run(ca, cb, dtype, hd): the backward of each of the five Functions, asked for the weight gradient alone, on
+    (_WG_N, ca) rows and a (_WG_N, cb) gradient of `dtype`; hd is the half dtype the forward would have noted. -> weight gradient."""
+    from types import SimpleNamespace as NS
+    from openpcseg_amd import block_fusion, fused
+    rows = lambda c, dtype: torch.ones(_WG_N, c, dtype=dtype)
+    ident = lambda: {("_pcs_identity", _WG_N, "cpu"): NS(K=1)}
+
+    def sparse(ca, cb, dtype, hd, transposed=False):
+        ctx = NS(for_backwards=(rows(ca, dtype), torch.zeros(2, ca, cb), NS(fwd=NS(K=2)), transposed, hd), with_skip=False,
+                 needs_input_grad=(False, True))
+        return F._SparseConv.backward(ctx, rows(cb, dtype))[1]
+
+    def pointwise(ca, cb, dtype, hd):
+        ctx = NS(saved_tensors=(rows(ca, dtype), torch.zeros(ca, cb)), hd=hd, cache=ident(), needs_input_grad=(False, True, False))
+        return F._PointwiseConv.backward(ctx, rows(cb, dtype))[1]
+
+    def skinny(ca, cb, dtype, hd):
+        ctx = NS(saved_tensors=(rows(ca, dtype), torch.zeros(cb, ca)), km=NS(K=1), hd=hd, needs_input_grad=(False, True, False))
+        return fused._SkinnyLinear.backward(ctx, rows(cb, dtype))[1]
+
+    def parts(ca, cb, dtype, hd):
+        ctx = NS(saved_tensors=(torch.zeros(cb, ca), rows(ca, dtype)), km=NS(K=1), hd=hd, has_bias=False,
+                 needs_input_grad=(True, False, False, False, False))
+        return fused._SkinnyLinearParts.backward(ctx, rows(cb, dtype))[0]
+
+    def point(ca, cb, dtype, hd):
+        ctx = NS(saved_tensors=(rows(ca, dtype), torch.zeros(cb, ca)), hd=hd, has_bias=False, in_dtype=dtype,
+                 needs_input_grad=(False, True, False))
+        block_fusion._POINT_MAPS.update(ident())
+        try:
+            return block_fusion._PointLinear.backward(ctx, rows(cb, dtype))[1]
+        finally:
+            block_fusion._POINT_MAPS.clear()
+
+    return {"_SparseConv": sparse, "_PointwiseConv": pointwise, "_SkinnyLinear": skinny, "_SkinnyLinearParts": parts, "_PointLinear": point}
+
+
+def test_weight_gradient_entry_table(monkeypatch):
+    """Which backend entry each of the five weight-gradient callers takes, with which operands: the half entry if and only if the
+    layer runs in a half dtype, the backend has it and both widths (after the caller's zero padding) are multiples of 4; otherwise
+    both operands in fp32 to the fp32 entry. _PointwiseConv pads both widths on a device tensor of >= 32 padded input channels,
+    _PointLinear always pads its input width; the result comes back at the unpadded widths. `split` reaches the backend from
+    _SparseConv alone, under the bf16x3 policy from 96 x 96 channels."""
+    f32, bf = torch.float32, torch.bfloat16
+    sites = _wgrad_sites()
+    shapes = lambda ca, cb: ((_WG_N, ca), (_WG_N, cb))
+
+    def one(site, ca, cb, dtype, hd, be=None, **kw):
+        be = be or _WgradStub()
+        with monkeypatch.context() as mp:
+            mp.setattr(native, "_BACKEND", be)
+            gw = sites[site](ca, cb, dtype, hd, **kw)
+        (call,) = be.calls   # one entry call per weight gradient
+        assert gw.dtype == f32 and tuple(gw.shape) in ((ca, cb), (cb, ca), (2, ca, cb)), (site, gw.shape)
+        return call
+
+    for site in sites:
+        assert one(site, 32, 32, f32, None) == ("conv_wgrad", (f32, f32), shapes(32, 32), 0, False), site
+        assert one(site, 32, 32, bf, bf) == ("conv_wgrad_h", (bf, bf), shapes(32, 32), 0, None), site
+        # a backend without the half entry: fp32 operands to the fp32 entry
+        assert one(site, 32, 32, bf, bf, be=_WgradStub(half_entry=False)) == ("conv_wgrad", (f32, f32), shapes(32, 32), 0, False), site
+    for site in ("_SparseConv", "_SkinnyLinear", "_SkinnyLinearParts"):   # a width off the half entry: fp32 entry, operands unpadded
+        for ca, cb in ((6, 32), (32, 6)):
+            assert one(site, ca, cb, bf, bf) == ("conv_wgrad", (f32, f32), shapes(ca, cb), 0, False), (site, ca, cb)
+    assert one("_SparseConv", 32, 32, f32, None, transposed=True)[3] == 1   # a transposed conv's input rows are the map's column 1
+    # _PointLinear: the input width is padded (Linear(9, 64): 9 -> 12), the output width is not -- off the half entry it is fp32
+    assert one("_PointLinear", 9, 64, f32, None) == ("conv_wgrad", (f32, f32), shapes(12, 64), 0, False)
+    assert one("_PointLinear", 9, 64, bf, bf) == ("conv_wgrad_h", (bf, bf), shapes(12, 64), 0, None)
+    assert one("_PointLinear", 8, 6, bf, bf) == ("conv_wgrad", (f32, f32), shapes(8, 6), 0, False)
+    # _PointwiseConv pads on the device only, and only layers of >= 32 (padded) input channels
+    assert one("_PointwiseConv", 153, 32, f32, None) == ("conv_wgrad", (f32, f32), shapes(153, 32), 0, False)   # host rows
+    with monkeypatch.context() as mp:
+        mp.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
+        assert one("_PointwiseConv", 153, 32, f32, None) == ("conv_wgrad", (f32, f32), shapes(156, 32), 0, False)
+        assert one("_PointwiseConv", 153, 32, f32, bf) == ("conv_wgrad_h", (bf, bf), shapes(156, 32), 0, None)
+        assert one("_PointwiseConv", 32, 153, f32, bf) == ("conv_wgrad_h", (bf, bf), shapes(32, 156), 0, None)
+        assert one("_PointwiseConv", 9, 32, f32, bf) == ("conv_wgrad", (f32, f32), shapes(9, 32), 0, False)
+    F.set_wgrad_policy("bf16x3")
+    try:
+        assert one("_SparseConv", 96, 96, f32, None)[4] is True and one("_SparseConv", 64, 96, f32, None)[4] is False
+        assert one("_SparseConv", 96, 96, bf, bf)[0] == "conv_wgrad_h"
+        for site in sites:
+            if site != "_SparseConv":
+                assert one(site, 96, 96, f32, None)[4] is False, site
+    finally:
+        F.set_wgrad_policy("fp32")

@@ -43,6 +43,8 @@ def main():
     rows.append(("be.hash", cost(lambda: be.hash(coords))))
     rows.append(("be.conv_gather_gemm", cost(lambda: be.conv_gather_gemm(x, w, entry.fwd))))
     rows.append(("be.conv_wgrad", cost(lambda: be.conv_wgrad(x, gy, entry.fwd, 0))))
+    xh, gh = x.bfloat16(), gy.bfloat16()
+    rows.append(("be.conv_wgrad_h", cost(lambda: be.conv_wgrad_h(xh, gh, entry.fwd, 0))))
     rows.append(("w.transpose(1,2).contiguous()", cost(lambda: w.transpose(1, 2).contiguous())))
     sums = be.bn_stats(x)
     stat = be.bn_finalize(sums, float(n), 1e-5, 0.1, None, None)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Workgroups per weight-gradient launch (wgrad_plan's target; fewer, longer splits = less partial-sum traffic and a shorter
+# Workgroups per weight-gradient launch (wgrad_route's split target; fewer, longer splits = less partial-sum traffic and a shorter
 # wgrad_reduce4, more = better fill of the last round): PCS_WGRAD_TARGET sweep over tools/wgrad_microbench.py (kernel + reduce).
 cd "$(dirname "$0")/.."
 for t in 0 768 1024 1536 2048 3072 4096 6144; do
