@@ -721,8 +721,17 @@ int pcs_lovasz_softmax_f32(const float *probas, const int64_t *labels, int64_t n
  *   weight-stationary kernel where the policy picks it, >= 2 = wherever an instance exists; `ru` unused; rs = 1: two-row-block
  *   sub-groups on the two shapes that have both instances.
  * pcs_debug_wgrad_interleave: launch order of the weight-gradient splits, -1 = default (2 for 16-bit operands, 0 for fp32),
- *   0 offset-major, 1 position-major, 2 position-major with every XCD on a contiguous eighth. */
+ *   0 offset-major, 1 position-major, 2 position-major with every XCD on a contiguous eighth.
+ * pcs_debug_conv_plan: host only; the plan the library routes a forward / input-gradient convolution call on -- the one value the
+ *   entries launch from and the shape queries answer from. kind 0 = pcs_conv_gather_gemm_f32(_ex), 1 = pcs_conv_gather_gemm_h(_ex),
+ *   2 = pcs_conv_gather_gemm_f32_bf16x3; dtype as there; flags: 1 bn_partial given, 2 tile_order given, 4 write-back extras,
+ *   8 PCS_EP_POST_AFFINE among them, 16 a tensor off 16 bytes. out = {family (0 not served, 1 conv_block, 2 conv_wave4,
+ *   3 conv_wave5, 4 conv_wave5h, 5 conv_wave6h, 6 conv_wave5x), 16-column tiles per column tile, column tiles, threads per
+ *   workgroup, TAIL instance, row blocks per group, wave6h row blocks per sub-group, wave6h contraction chunks, nt16, ns of the
+ *   prepared weights, LDS bytes, answers (1 emits BatchNorm partials at this height, 2 reads tile_order, 4 takes extras)}. */
 void pcs_debug_convh_ws(int32_t mode, int32_t ru, int32_t rs);
+void pcs_debug_conv_plan(int32_t kind, int32_t dtype, int32_t cin, int32_t cout, int32_t K, int32_t tile_rows, int32_t flags,
+                         int32_t out[12]);
 void pcs_debug_wgrad_interleave(int32_t mode);
 
 #ifdef __cplusplus

@@ -12,7 +12,7 @@
 //   4. runs 16x16x4 fp32 MFMAs on the compact m x 32 tile (only ceil(m/16) row blocks issue),
 //   5. adds the compact result rows into the accumulator tile through the dst-row map.
 // Every destination row is written exactly once at the end: no atomics, no zero fill of dst.
-#include "conv_common.h"
+#include "conv_plan.h"
 
 using namespace pcs;
 
@@ -29,8 +29,7 @@ struct ConvCfg {
   static constexpr int ACS = CT + 4;   // accumulator row stride
   static constexpr int WS = CT + 16;   // wbuf row stride: == 16 (mod 32)
   static constexpr int NRB = T / 16 / RG;
-  static constexpr size_t lds_bytes =
-      (size_t)(T * ACS + T * AS + CK * WS) * 4 + (size_t)2 * T * 4;
+  // LDS: (T ACS + CK WS + T AS) floats + 2 T ints, the layout at the head of the kernel; conv_route (conv.hip) sizes it
 };
 
 template <int CG, int RG, int T, bool VEC>
@@ -174,35 +173,30 @@ __global__ void __launch_bounds__(64 * CG * RG) conv_os_kernel(ConvArgs a) {
 }
 
 template <int CG, int RG, int T>
-int launch_conv(const ConvArgs &a, bool vec, hipStream_t st) {
-  using C = ConvCfg<CG, RG, T>;
+int launch_conv(const ConvArgs &a, const ConvPlan &p, hipStream_t st) {
   const int64_t nblocks = a.ntiles * a.ncoltiles;
   if (nblocks <= 0) return PCS_OK;
   if (nblocks > 0x7FFFFFFF) { set_error("pcs_conv: grid too large"); return PCS_EUNSUPPORTED; }
-  auto kern = vec ? conv_os_kernel<CG, RG, T, true> : conv_os_kernel<CG, RG, T, false>;
+  auto kern = p.vec ? conv_os_kernel<CG, RG, T, true> : conv_os_kernel<CG, RG, T, false>;
   static bool attr_set_v = false, attr_set_s = false;
-  bool &flag = vec ? attr_set_v : attr_set_s;
+  bool &flag = p.vec ? attr_set_v : attr_set_s;
   if (!flag) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::lds_bytes);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
     flag = true;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(C::NT), C::lds_bytes, st, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(p.nt), p.lds, st, a);
   return check_launch("pcs_conv_gather_gemm_f32");
 }
 
 }  // namespace
 
-int pcs::launch_conv_block(ConvArgs a, bool vec, hipStream_t st) {
-  // column tile: 32*CG with CG in 1..4; wider outputs are covered by several column tiles
-  int cg = (a.cout + 31) / 32;
-  if (cg > 4) cg = 4;
-  a.ncoltiles = (int)ceil_div(a.cout, 32 * cg);
+int pcs::launch_conv_block(const ConvArgs &a, const ConvPlan &p, hipStream_t st) {
 #define PCS_CONV_CASE(CGv, RGv)                                                       \
   case CGv:                                                                           \
-    return a.tile_rows == 128 ? launch_conv<CGv, RGv, 128>(a, vec, st)                \
-                              : launch_conv<CGv, RGv, 64>(a, vec, st);
-  switch (cg) {
+    return a.tile_rows == 128 ? launch_conv<CGv, RGv, 128>(a, p, st)                  \
+                              : launch_conv<CGv, RGv, 64>(a, p, st);
+  switch (p.nctt / 2) {   // 32-column groups per column tile
     PCS_CONV_CASE(1, 4)
     PCS_CONV_CASE(2, 2)
     PCS_CONV_CASE(3, 2)

@@ -1,6 +1,6 @@
-// Shared by the fused-convolution translation units (conv.hip = picker + C entry point, conv_block.hip = generic
+// Shared by the fused-convolution translation units (conv.hip = route + picker + C entry point, conv_block.hip = generic
 // block-synchronous kernel, conv_wave*.hip = wave-autonomous kernels, conv_wgrad.hip = weight gradient). The skeleton the wave
-// kernels share (tile mapping, offset lists, commit, launch) is conv_wave_common.h.
+// kernels share (tile mapping, offset lists, commit, launch) is conv_wave_common.h; the host-side plan is conv_plan.h.
 #pragma once
 #include <stdlib.h>
 
@@ -146,10 +146,5 @@ __device__ __forceinline__ void conv_tile_epilogue(float *acc_l, int ACS, int ro
 }
 // rows of tile scratch the statistics need: 2 per row group + the pivot row
 inline bool conv_stats_fit(int tile_rows, int ct, int nt) { return tile_rows + 1 >= 2 * (nt / (ct / 4)) + 1; }
-
-// launchers (each picks its template instance from the shape; `a.ncoltiles` is set inside)
-int launch_conv_block(ConvArgs a, bool vec, hipStream_t st);   // any shape; tile_rows 64 / 128
-int launch_conv_wave4(ConvArgs a, hipStream_t st);              // cin % 4 == 0, cout % 4 == 0, K <= 32; tile_rows 64 / 128
-int launch_conv_wave5(ConvArgs a, hipStream_t st);              // conv5_applies(); any tile_rows % 16 == 0
 
 }  // namespace pcs

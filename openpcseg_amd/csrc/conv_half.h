@@ -1,7 +1,7 @@
 // Shared by the 16-bit-MFMA fused-convolution code: conv_wave5h.hip (wave-autonomous row-block groups, ticket commit),
 // conv_wave6h.hip (weight-stationary ranges) and weights_multi.hip. They read the same prepared weights (MFMA fragment order, pcs_conv_prepare_weights_h) and share the tile epilogue of conv_common.h.
 #pragma once
-#include "conv_wave_common.h"
+#include "conv_plan.h"
 
 namespace pcs {
 
@@ -31,5 +31,7 @@ struct ConvArgsH {
   float act_slope = 1.f;             // LeakyReLU in the write-back, as ConvArgs::act_slope
   const float *post_scale = nullptr, *post_shift = nullptr;  // PCS_EP_POST_AFFINE, as ConvArgs::post_scale (fp32; ONE rounding, on the store)
 };
+
+int launch_conv_wave6h(const ConvArgsH &a, const ConvPlan &p, hipStream_t st);   // conv_wave6h.hip
 
 }  // namespace pcs

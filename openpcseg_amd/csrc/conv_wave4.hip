@@ -1,6 +1,6 @@
 // Wave-autonomous fused convolution, one row block per wave step ("wave4"): serves the 16-byte-granular shapes the
 // wave5 kernel does not take (cin < 64 or cin % 32 != 0, odd column-tile counts).
-#include "conv_wave_common.h"
+#include "conv_plan.h"
 
 using namespace pcs;
 
@@ -31,7 +31,6 @@ struct Conv4Cfg {
   static constexpr int N4 = NCTT / 4;            // 64-column groups  (float4 W loads)
   static constexpr int N2 = (NCTT % 4) / 2;      // one 32-column group (float2 W loads)
   static constexpr int N1 = NCTT % 2;            // one 16-column group (float  W loads)
-  static constexpr size_t lds_bytes = (size_t)((T + 1) * ACS) * 4 + 4 * 32 * 4 + 32;
 };
 
 template <int NCTT, int T, bool E32, int NW, int MINW>
@@ -274,24 +273,19 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os4_kernel(ConvArgs a) {
 }
 
 template <int NCTT, int T, int NW, int MINW>
-int launch_conv4_cfg(const ConvArgs &a, hipStream_t st) {
-  using C = Conv4Cfg<NCTT, T, NW>;
+int launch_conv4_cfg(const ConvArgs &a, const ConvPlan &p, hipStream_t st) {
   constexpr const char *who = "pcs_conv", *label = "pcs_conv_gather_gemm_f32(wave4)";
-  if (a.cin % 32 == 0) return conv_wave_launch<conv_os4_kernel<NCTT, T, true, NW, MINW>>(a, false, C::NT, C::lds_bytes, st, who, label);
-  return conv_wave_launch<conv_os4_kernel<NCTT, T, false, NW, MINW>>(a, false, C::NT, C::lds_bytes, st, who, label);
+  if (!p.tail) return conv_wave_launch<conv_os4_kernel<NCTT, T, true, NW, MINW>>(a, p, st, who, label);
+  return conv_wave_launch<conv_os4_kernel<NCTT, T, false, NW, MINW>>(a, p, st, who, label);
 }
-
 
 }  // namespace
 
-int pcs::launch_conv_wave4(ConvArgs a, hipStream_t st) {
-  const int nctt = conv_nctt(a.cout);
-  a.ncoltiles = (int)ceil_div(a.cout, 16 * nctt);
-  // 4 waves with <= 168 VGPRs: 3 workgroups per CU
+int pcs::launch_conv_wave4(const ConvArgs &a, const ConvPlan &p, hipStream_t st) {
 #define PCS_CONV4_CASE(N)                                                                              \
   case N:                                                                                              \
-    return a.tile_rows == 128 ? launch_conv4_cfg<N, 128, 4, 3>(a, st) : launch_conv4_cfg<N, 64, 4, 3>(a, st);
-  switch (nctt) {
+    return a.tile_rows == 128 ? launch_conv4_cfg<N, 128, 4, 3>(a, p, st) : launch_conv4_cfg<N, 64, 4, 3>(a, p, st);
+  switch (p.nctt) {
     PCS_CONV4_CASE(1)
     PCS_CONV4_CASE(2)
     PCS_CONV4_CASE(3)

@@ -1,5 +1,5 @@
 // Wave-autonomous fused convolution with row-block groups ("wave5"): the kernel behind every >= 64-channel layer.
-#include "conv_wave_common.h"
+#include "conv_plan.h"
 
 using namespace pcs;
 
@@ -362,11 +362,9 @@ void trace_prepare(hipStream_t st) {
 #endif
 
 template <int NCTT, int NW, int MINW, int R, bool TAIL>
-int launch_conv5(const ConvArgs &a, hipStream_t st) {
-  using C = ConvWaveCfg<NCTT, NW, R>;
+int launch_conv5(const ConvArgs &a, const ConvPlan &p, hipStream_t st) {
   constexpr auto kern = conv_os5_kernel<NCTT, NW, MINW, R, TAIL>;
-  const size_t lds = C::lds_bytes(a.tile_rows);
-  return conv_wave_launch<kern>(a, a.order != nullptr, C::NT, lds, st, "pcs_conv", "pcs_conv_gather_gemm_f32(wave5)", [&](int64_t nblocks) {
+  return conv_wave_launch<kern>(a, p, st, "pcs_conv", "pcs_conv_gather_gemm_f32(wave5)", [&](int64_t nblocks) {
     PCS_T(trace_prepare(st);)
     static const int dbg = getenv("PCS_CONV_DEBUG") ? atoi(getenv("PCS_CONV_DEBUG")) : 0;  // debug: launch shape + residency
     static long long dbg_last = -1;
@@ -374,9 +372,9 @@ int launch_conv5(const ConvArgs &a, hipStream_t st) {
     if (dbg && dbg_key != dbg_last) {
       dbg_last = dbg_key;
       int nb = 0;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern), C::NT, lds);
+      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern), p.nt, p.lds);
       fprintf(stderr, "[pcs_conv] wave5<%d,%d,%d,%d%s> T=%d cin=%d cout=%d grid=%lld lds=%zu resident WG/CU=%d (waves/SIMD=%d)\n", NCTT, NW,
-              MINW, R, TAIL ? ",tail" : "", a.tile_rows, a.cin, a.cout, (long long)nblocks, lds, nb, nb * NW / 4);
+              MINW, R, TAIL ? ",tail" : "", a.tile_rows, a.cin, a.cout, (long long)nblocks, p.lds, nb, nb * NW / 4);
     }
   });
 }
@@ -392,21 +390,12 @@ extern "C" int pcs_debug_conv_trace(long long *host_out) {
 }
 #endif
 
-int pcs::launch_conv_wave5(ConvArgs a, hipStream_t st) {
-  int nctt = conv5_nctt(a.cout, a.tile_rows);  // wide outputs on tall tiles: 64-column tiles
-  static const int force_nctt = getenv("PCS_CONV_NCTT") ? atoi(getenv("PCS_CONV_NCTT")) : 0;  // debug
-  static const int force_nw = getenv("PCS_CONV_NW") ? atoi(getenv("PCS_CONV_NW")) : 0;        // debug: 4 / 8
-  if (force_nctt && nctt > force_nctt) nctt = force_nctt;
-  a.ncoltiles = (int)ceil_div(a.cout, 16 * nctt);
-  const bool nw8 = force_nw ? force_nw == 8 : conv_nw8(a.tile_rows, nctt);
-  // groups of 2 row blocks (groups of 3 / 4 were instantiated and measured through round 2: within +-1 % where they fit
-  // the registers -- the W stream they save is not what bounds the kernel -- and spilling at 6 / 8 column tiles)
-  const bool tail = (a.cin % 32) != 0;
+int pcs::launch_conv_wave5(const ConvArgs &a, const ConvPlan &p, hipStream_t st) {
 #define PCS_CONV5_CASE(N)                                                                           \
   case N:                                                                                           \
-    if (nw8) return tail ? launch_conv5<N, 8, 2, 2, true>(a, st) : launch_conv5<N, 8, 2, 2, false>(a, st);  \
-    return tail ? launch_conv5<N, 4, 2, 2, true>(a, st) : launch_conv5<N, 4, 2, 2, false>(a, st);
-  switch (nctt) {
+    if (p.nt == 512) return p.tail ? launch_conv5<N, 8, 2, 2, true>(a, p, st) : launch_conv5<N, 8, 2, 2, false>(a, p, st);  \
+    return p.tail ? launch_conv5<N, 4, 2, 2, true>(a, p, st) : launch_conv5<N, 4, 2, 2, false>(a, p, st);
+  switch (p.nctt) {
     PCS_CONV5_CASE(2)
     PCS_CONV5_CASE(4)
     PCS_CONV5_CASE(6)

@@ -23,13 +23,6 @@
 
 using namespace pcs;
 
-namespace pcs {
-int launch_conv_wave6h(const ConvArgsH &a, int dtype, hipStream_t st);  // conv_wave6h.hip
-bool conv6h_applies(int cin, int cout, int K);
-bool conv6h_is_chunked(int cin, int cout);
-int conv6h_mode();
-}
-
 namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // native vector: loads from LDS address-space pointers
@@ -410,40 +403,23 @@ void traceh_prepare(hipStream_t st) {
 #endif
 
 template <typename HT, int NCTT, int NW, int MINW, int R, bool TAIL, bool POST = false>
-int launch_conv5h(const ConvArgsH &a, hipStream_t st) {
-  using C = ConvWaveCfg<NCTT, NW, R>;
-  return conv_wave_launch<conv_os5h_kernel<HT, NCTT, NW, MINW, R, TAIL, POST>>(a, a.order != nullptr, C::NT, C::lds_bytes(a.tile_rows), st, "pcs_conv_h",
-                                                                          "pcs_conv_gather_gemm_h(wave5h)", [&](int64_t) { PCS_T(traceh_prepare(st);) });
-}
-
-// row blocks per group of the half kernel per column-tile width (picked from profiles/round3_convh_group_rows.txt)
-inline int convh_group_rows(int nctt) {
-  (void)nctt;
-  return 2;
+int launch_conv5h(const ConvArgsH &a, const ConvPlan &p, hipStream_t st) {
+  return conv_wave_launch<conv_os5h_kernel<HT, NCTT, NW, MINW, R, TAIL, POST>>(a, p, st, "pcs_conv_h", "pcs_conv_gather_gemm_h(wave5h)",
+                                                                          [&](int64_t) { PCS_T(traceh_prepare(st);) });
 }
 
 template <typename HT>
-int launch_h(ConvArgsH a, hipStream_t st) {
-  int nctt = conv_nctt(a.cout);
-  static const int force_nctt = getenv("PCS_CONVH_NCTT") ? atoi(getenv("PCS_CONVH_NCTT")) : 0;  // debug: narrower column tiles
-  if (force_nctt && nctt > force_nctt && a.cout % (16 * force_nctt) == 0 && !a.stats) nctt = force_nctt;
-  a.ncoltiles = (int)ceil_div(a.cout, 16 * nctt);
-  const bool nw8 = conv_nw8(a.tile_rows, nctt);
-  const bool tail = (a.cin % 32) != 0;
-  // row blocks per group: the kernel is bound by the vector-memory address unit (TA ~65-80 % busy, MFMA pipe 10-20 %,
-  // profiles/round3_convh_pmc.md): one 16-byte operand load per lane feeds R N / (R + N) MFMAs, so more row blocks per B
-  // fragment = fewer loads per MFMA (R = 2, N = 8: 1.6; R = 4, N = 8: 2.67) as far as the registers allow
-  static const int force_r = getenv("PCS_CONVH_R") ? atoi(getenv("PCS_CONVH_R")) : 0;  // A/B
-  const int rsel = tail ? 2 : (force_r >= 2 && force_r <= 4 ? force_r : convh_group_rows(nctt));
+int launch_h(const ConvArgsH &a, const ConvPlan &p, hipStream_t st) {
+  const bool nw8 = p.nt == 512, tail = p.tail;
 #define PCS_CONV5H_CASE(N)                                                                          \
   case N:                                                                                           \
-    if (a.post_scale && tail) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, true, true>(a, st) : launch_conv5h<HT, N, 4, 2, 2, true, true>(a, st);  \
-    if (a.post_scale) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, false, true>(a, st) : launch_conv5h<HT, N, 4, 2, 2, false, true>(a, st);  \
-    if (tail) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, true>(a, st) : launch_conv5h<HT, N, 4, 2, 2, true>(a, st);  \
-    if (rsel == 4) return nw8 ? launch_conv5h<HT, N, 8, 2, 4, false>(a, st) : launch_conv5h<HT, N, 4, 2, 4, false>(a, st);  \
-    if (rsel == 3) return nw8 ? launch_conv5h<HT, N, 8, 2, 3, false>(a, st) : launch_conv5h<HT, N, 4, 2, 3, false>(a, st);  \
-    return nw8 ? launch_conv5h<HT, N, 8, 2, 2, false>(a, st) : launch_conv5h<HT, N, 4, 2, 2, false>(a, st);
-  switch (nctt) {
+    if (a.post_scale && tail) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, true, true>(a, p, st) : launch_conv5h<HT, N, 4, 2, 2, true, true>(a, p, st);  \
+    if (a.post_scale) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, false, true>(a, p, st) : launch_conv5h<HT, N, 4, 2, 2, false, true>(a, p, st);  \
+    if (tail) return nw8 ? launch_conv5h<HT, N, 8, 2, 2, true>(a, p, st) : launch_conv5h<HT, N, 4, 2, 2, true>(a, p, st);  \
+    if (p.R == 4) return nw8 ? launch_conv5h<HT, N, 8, 2, 4, false>(a, p, st) : launch_conv5h<HT, N, 4, 2, 4, false>(a, p, st);  \
+    if (p.R == 3) return nw8 ? launch_conv5h<HT, N, 8, 2, 3, false>(a, p, st) : launch_conv5h<HT, N, 4, 2, 3, false>(a, p, st);  \
+    return nw8 ? launch_conv5h<HT, N, 8, 2, 2, false>(a, p, st) : launch_conv5h<HT, N, 4, 2, 2, false>(a, p, st);
+  switch (p.nctt) {
     PCS_CONV5H_CASE(2)
     PCS_CONV5H_CASE(4)
     PCS_CONV5H_CASE(6)
@@ -467,7 +443,7 @@ extern "C" int pcs_debug_convh_trace(long long *host_out) {
 
 extern "C" size_t pcs_conv_prepared_weights_bytes(int32_t K, int32_t ccon, int32_t ccols) {
   if (K <= 0 || ccon <= 0 || ccols <= 0 || ccon % 8) return 0;
-  return (size_t)K * (size_t)ceil_div(ccols, 16 * conv_nctt(ccols)) * conv_nctt(ccols) * (size_t)ceil_div(ccon, 32) * 1024;
+  return K * conv_prepared_geom(ccon, ccols, false).bytes;
 }
 
 extern "C" int pcs_conv_h_applies(int32_t cin, int32_t cout, int32_t K) { return convh_applies(cin, cout, K) ? 1 : 0; }
@@ -479,15 +455,14 @@ extern "C" int pcs_conv_prepare_weights_h(const float *W, int32_t K, int32_t A, 
     set_error("pcs_conv_prepare_weights_h: bad args / shape not served by the half kernels");
     return PCS_EINVAL;
   }
-  const int nctt = conv_nctt(ccols), nt16 = (int)ceil_div(ccols, 16 * nctt) * nctt, ns = (int)ceil_div(ccon, 32);
-  const int64_t total = (int64_t)K * nt16 * ns * 64;
-  const int grid = stream_grid(total, 256);
+  const ConvPreparedGeom g = conv_prepared_geom(ccon, ccols, false);
+  const int grid = stream_grid((int64_t)K * g.nt16 * g.ns * 64, 256);
   if (dtype == 1)
-    hipLaunchKernelGGL(prepare_weights_kernel<Bf16>, dim3(grid), dim3(256), 0, as_stream(stream), W, K, A, B, transpose, nctt,
-                       nt16, ns, reinterpret_cast<uint4 *>(Wp));
+    hipLaunchKernelGGL(prepare_weights_kernel<Bf16>, dim3(grid), dim3(256), 0, as_stream(stream), W, K, A, B, transpose, g.nctt,
+                       g.nt16, g.ns, reinterpret_cast<uint4 *>(Wp));
   else
-    hipLaunchKernelGGL(prepare_weights_kernel<Fp16>, dim3(grid), dim3(256), 0, as_stream(stream), W, K, A, B, transpose, nctt,
-                       nt16, ns, reinterpret_cast<uint4 *>(Wp));
+    hipLaunchKernelGGL(prepare_weights_kernel<Fp16>, dim3(grid), dim3(256), 0, as_stream(stream), W, K, A, B, transpose, g.nctt,
+                       g.nt16, g.ns, reinterpret_cast<uint4 *>(Wp));
   return check_launch("pcs_conv_prepare_weights_h");
 }
 
@@ -503,33 +478,22 @@ extern "C" int pcs_conv_gather_gemm_h_ex(const void *src, int64_t n_src, int32_t
                                          const int32_t *pairs, int32_t src_col, const int32_t *seg, int32_t tile_rows,
                                          int64_t n_dst, const float *bias, const pcs_conv_epilogue *ep, void *dst, int32_t dtype,
                                          double *bn_partial, const int32_t *tile_order, void *stream) {
-  if (cin <= 0 || cout <= 0 || K <= 0 || n_dst < 0 || n_src < 0 || (src_col != 0 && src_col != 1) || (dtype != 1 && dtype != 2)) {
-    set_error("pcs_conv_gather_gemm_h: bad sizes");
-    return PCS_EINVAL;
-  }
-  if (!convh_applies(cin, cout, K)) { set_error("pcs_conv_gather_gemm_h: shape not served by the half kernels (needs cin %% 8 == 0, cin >= 32, cout %% 4 == 0, an even number of 16-column tiles)"); return PCS_EUNSUPPORTED; }
-  if (n_dst == 0) return PCS_OK;
-  if (!Wp || !seg || !dst || (n_src > 0 && !src)) { set_error("pcs_conv_gather_gemm_h: null pointer"); return PCS_EINVAL; }
-  if ((((uintptr_t)src | (uintptr_t)Wp | (uintptr_t)bias) & 15) || ((uintptr_t)dst & 7)) { set_error("pcs_conv_gather_gemm_h: misaligned pointer"); return PCS_EINVAL; }
-  if (tile_rows < 16 || tile_rows > 512 || tile_rows % 16) { set_error("pcs_conv_gather_gemm_h: tile_rows must be a multiple of 16 in [16, 512]"); return PCS_EINVAL; }
-  ConvArgsH a;
-  a.src = reinterpret_cast<const char *>(src); a.Wp = reinterpret_cast<const char *>(Wp); a.bias = bias;
-  a.dst = reinterpret_cast<uint16_t *>(dst); a.pairs = pairs; a.seg = seg;
-  a.n_dst = n_dst; a.ntiles = ceil_div(n_dst, tile_rows); a.tile_rows = tile_rows;
-  a.cin = cin; a.cout = cout; a.K = K; a.src_col = src_col; a.ncoltiles = 1; a.stats = bn_partial; a.order = tile_order;
+  const char *who = "pcs_conv_gather_gemm_h";
+  const bool post = ep && (ep->flags & PCS_EP_POST_AFFINE);   // decoded below; the route wants to know in front
+  const ConvPlan p = conv_route(ConvKind::half, dtype, cin, cout, K, tile_rows, (bn_partial ? kConvStats : 0) | (tile_order ? kConvOrder : 0) |
+                                (ep ? kConvExtras : 0) | (post ? kConvPostAffine : 0));
+  const int rc = conv_check_call(who, p.family == ConvFamily::none ? "shape not served by the half kernels (needs cin % 8 == 0, cin >= 32, cout % 4 == 0, an even number of 16-column tiles)" : nullptr,
+                                 cin, cout, K, n_src, n_dst, src_col, dtype == 1 || dtype == 2, src, Wp, seg, dst,
+                                 (((uintptr_t)src | (uintptr_t)Wp | (uintptr_t)bias) & 15) || ((uintptr_t)dst & 7), tile_rows);
+  if (rc != PCS_OK || n_dst == 0) return rc;
+  ConvArgsH a = conv_args<ConvArgsH>(src, bias, dst, pairs, seg, n_dst, tile_rows, cin, cout, K, src_col, bn_partial, tile_order, p);
+  a.Wp = reinterpret_cast<const char *>(Wp); a.nt16 = p.nt16; a.ns = p.ns;
   const void *addend = nullptr;
   if (conv_decode_epilogue(ep, "pcs_conv_gather_gemm_h_ex", 8, bn_partial != nullptr, addend, a.act_slope, a.post_scale, a.post_shift) != PCS_OK)
     return PCS_EINVAL;
   a.addend = reinterpret_cast<const uint16_t *>(addend);
-  if (bn_partial && !pcs_conv_emits_bn_partials(cin, cout, K, tile_rows, dtype)) {
-    set_error("pcs_conv_gather_gemm_h: this shape / tile height does not produce BatchNorm partials");
-    return PCS_EUNSUPPORTED;
-  }
-  const int nctt = conv_nctt(cout);
-  a.nt16 = (int)ceil_div(cout, 16 * nctt) * nctt;
-  a.ns = (int)ceil_div(cin, 32);
-  // the weight-stationary kernel (conv_wave6h.hip); its chunked-contraction instances only on 4-wave workgroups (<= 160-row tiles)
-  if (conv6h_mode() && conv6h_applies(cin, cout, K) && (!conv6h_is_chunked(cin, cout) || tile_rows <= 160))
-    return launch_conv_wave6h(a, dtype, as_stream(stream));
-  return dtype == 1 ? launch_h<Bf16>(a, as_stream(stream)) : launch_h<Fp16>(a, as_stream(stream));
+  if (bn_partial && !p.emits_stats) return conv_no_stats(who);
+  hipStream_t st = as_stream(stream);
+  if (p.family == ConvFamily::wave6h) return launch_conv_wave6h(a, p, st);
+  return dtype == 1 ? launch_h<Bf16>(a, p, st) : launch_h<Fp16>(a, p, st);
 }

@@ -21,7 +21,7 @@
 //   * groups hold R = 4 row blocks at 64 columns, 3 at 96, 2 at 32: the kernel is bound by the vector-memory address path
 //     (TA 78-87 % busy, MFMA pipe 29-37 %; without the MFMAs the launch takes the same time), a column tile costs 2 A loads
 //     + 3 N / R weight-fragment loads per row block and step, and R is what 256 registers allow (profiles/round3_convx.md).
-#include "conv_wave_common.h"
+#include "conv_plan.h"
 
 #ifndef PCS_ABLATEX
 #define PCS_ABLATEX 0  /* debug builds: 1 no operand split (planes = raw bits), 2 no B reloads inside a group, 3 no A reloads, 4 no MFMA */
@@ -53,15 +53,6 @@ __device__ __forceinline__ void split3(float x, float y, uint32_t &hi, uint32_t 
   const x_f32x2 r2 = r1 - __builtin_convertvector(m, x_f32x2);
   const x_bf16x2 l = __builtin_convertvector(r2, x_bf16x2);
   hi = __builtin_bit_cast(uint32_t, h); mid = __builtin_bit_cast(uint32_t, m); lo = __builtin_bit_cast(uint32_t, l);
-}
-
-// 16-column MFMA tiles per column tile: 2, 4 or 6 (>= 112 output columns as 64-column tiles)
-__host__ __device__ inline int convx_nctt(int cout) {
-  const int n = (cout + 15) / 16;
-  if (n <= 2) return 2;
-  if (n <= 4) return 4;
-  if (n <= 6) return 6;
-  return 4;
 }
 
 // prepared weights: fragment order and values of conv_wfrag_values (conv_wave_common.h), split into three bf16 planes
@@ -294,32 +285,19 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os5x_kernel(ConvArgsX a) {
 }
 
 template <int NCTT, int NW, int MINW, int R, bool TAIL>
-int launch_conv5x(const ConvArgsX &a, hipStream_t st) {
-  using C = ConvWaveCfg<NCTT, NW, R>;
-  return conv_wave_launch<conv_os5x_kernel<NCTT, NW, MINW, R, TAIL>>(a, a.order != nullptr, C::NT, C::lds_bytes(a.tile_rows), st, "pcs_conv_x3",
-                                                                      "pcs_conv_gather_gemm_f32_bf16x3(wave5x)");
-}
-
-inline bool convx_applies(int cin, int cout, int K) {
-  return cin % 8 == 0 && cin >= 32 && cout % 4 == 0 && cout >= 32 && K <= 32 && convx_nctt(cout) * 16 >= 32;
+int launch_conv5x(const ConvArgsX &a, const ConvPlan &p, hipStream_t st) {
+  return conv_wave_launch<conv_os5x_kernel<NCTT, NW, MINW, R, TAIL>>(a, p, st, "pcs_conv_x3", "pcs_conv_gather_gemm_f32_bf16x3(wave5x)");
 }
 
 }  // namespace
 
 extern "C" int pcs_conv_x3_applies(int32_t cin, int32_t cout, int32_t K) { return convx_applies(cin, cout, K) ? 1 : 0; }
 
-extern "C" int32_t pcs_conv_x3_column_tiles(int32_t cout) { return cout > 0 ? convx_nctt(cout) : 0; }
-
-extern "C" int32_t pcs_conv_x3_emits_bn_partials(int32_t cin, int32_t cout, int32_t K, int32_t tile_rows) {
-  if (!convx_applies(cin, cout, K) || tile_rows < 16) return 0;
-  const int nctt = convx_nctt(cout);
-  return conv_stats_fit(tile_rows, 16 * nctt, conv_nw8(tile_rows, nctt) ? 512 : 256) ? 1 : 0;
-}
+extern "C" int32_t pcs_conv_x3_column_tiles(int32_t cout) { return cout > 0 ? conv_prepared_geom(32, cout, true).nctt : 0; }
 
 extern "C" size_t pcs_conv_prepared_weights_x3_bytes(int32_t K, int32_t ccon, int32_t ccols) {
   if (K <= 0 || ccon <= 0 || ccols <= 0 || ccon % 8) return 0;
-  const int nctt = convx_nctt(ccols);
-  return 3 * (size_t)K * (size_t)ceil_div(ccols, 16 * nctt) * nctt * (size_t)ceil_div(ccon, 32) * 1024;
+  return K * conv_prepared_geom(ccon, ccols, true).bytes;
 }
 
 extern "C" int pcs_conv_prepare_weights_x3(const float *W, int32_t K, int32_t A, int32_t B, int32_t transpose, void *Wp,
@@ -329,10 +307,9 @@ extern "C" int pcs_conv_prepare_weights_x3(const float *W, int32_t K, int32_t A,
     set_error("pcs_conv_prepare_weights_x3: bad args / shape not served by the bf16x3 kernel");
     return PCS_EINVAL;
   }
-  const int nctt = convx_nctt(ccols), nt16 = (int)ceil_div(ccols, 16 * nctt) * nctt, ns = (int)ceil_div(ccon, 32);
-  const int64_t total = (int64_t)K * nt16 * ns * 64;
-  hipLaunchKernelGGL(prepare_weights_x3_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, as_stream(stream), W, K, A, B,
-                     transpose, nctt, nt16, ns, reinterpret_cast<uint4 *>(Wp));
+  const ConvPreparedGeom g = conv_prepared_geom(ccon, ccols, true);
+  hipLaunchKernelGGL(prepare_weights_x3_kernel, dim3(stream_grid((int64_t)K * g.nt16 * g.ns * 64, 256)), dim3(256), 0, as_stream(stream),
+                     W, K, A, B, transpose, g.nctt, g.nt16, g.ns, reinterpret_cast<uint4 *>(Wp));
   return check_launch("pcs_conv_prepare_weights_x3");
 }
 
@@ -340,57 +317,26 @@ extern "C" int pcs_conv_gather_gemm_f32_bf16x3(const float *src, int64_t n_src, 
                                                int32_t cout, const int32_t *pairs, int32_t src_col, const int32_t *seg,
                                                int32_t tile_rows, int64_t n_dst, const float *bias, float *dst,
                                                double *bn_partial, const int32_t *tile_order, void *stream) {
-  if (cin <= 0 || cout <= 0 || K <= 0 || n_dst < 0 || n_src < 0 || (src_col != 0 && src_col != 1)) {
-    set_error("pcs_conv_gather_gemm_f32_bf16x3: bad sizes");
-    return PCS_EINVAL;
-  }
-  if (!convx_applies(cin, cout, K)) {
-    set_error("pcs_conv_gather_gemm_f32_bf16x3: shape not served (needs cin %% 8 == 0, cin >= 32, cout %% 4 == 0, cout >= 32, K <= 32)");
-    return PCS_EUNSUPPORTED;
-  }
-  if (n_dst == 0) return PCS_OK;
-  if (!Wp || !seg || !dst || (n_src > 0 && !src)) { set_error("pcs_conv_gather_gemm_f32_bf16x3: null pointer"); return PCS_EINVAL; }
-  if (((uintptr_t)src | (uintptr_t)Wp | (uintptr_t)bias | (uintptr_t)dst) & 15) { set_error("pcs_conv_gather_gemm_f32_bf16x3: misaligned pointer"); return PCS_EINVAL; }
-  if (tile_rows < 16 || tile_rows > 512 || tile_rows % 16) { set_error("pcs_conv_gather_gemm_f32_bf16x3: tile_rows must be a multiple of 16 in [16, 512]"); return PCS_EINVAL; }
-  ConvArgsX a;
-  a.src = reinterpret_cast<const char *>(src); a.Wp = reinterpret_cast<const char *>(Wp); a.bias = bias; a.dst = dst;
-  a.pairs = pairs; a.seg = seg; a.n_dst = n_dst; a.ntiles = ceil_div(n_dst, tile_rows); a.tile_rows = tile_rows;
-  a.cin = cin; a.cout = cout; a.K = K; a.src_col = src_col; a.stats = bn_partial; a.order = tile_order;
-  const int nctt = convx_nctt(cout);
-  a.ncoltiles = (int)ceil_div(cout, 16 * nctt);
-  a.nt16 = a.ncoltiles * nctt;
-  a.ns = (int)ceil_div(cin, 32);
-  a.plane_bytes = (int64_t)K * a.nt16 * a.ns * 1024;
-  const bool nw8 = conv_nw8(tile_rows, nctt);
-  if (conv5_lds_est(tile_rows, nctt) > kMaxDynLds) { set_error("pcs_conv_gather_gemm_f32_bf16x3: tile_rows too large for this column tile"); return PCS_EUNSUPPORTED; }
-  if (bn_partial && !conv_stats_fit(tile_rows, 16 * nctt, nw8 ? 512 : 256)) {
-    set_error("pcs_conv_gather_gemm_f32_bf16x3: this tile height does not produce BatchNorm partials");
-    return PCS_EUNSUPPORTED;
-  }
-  const bool tail = (cin % 32) != 0;
+  const char *who = "pcs_conv_gather_gemm_f32_bf16x3";
+  const ConvPlan p = conv_route(ConvKind::x3, 0, cin, cout, K, tile_rows, (bn_partial ? kConvStats : 0) | (tile_order ? kConvOrder : 0));
+  const int rc = conv_check_call(who, p.family == ConvFamily::none ? "shape not served (needs cin % 8 == 0, cin >= 32, cout % 4 == 0, cout >= 32, K <= 32)" : nullptr,
+                                 cin, cout, K, n_src, n_dst, src_col, true, src, Wp, seg, dst,
+                                 ((uintptr_t)src | (uintptr_t)Wp | (uintptr_t)bias | (uintptr_t)dst) & 15, tile_rows);
+  if (rc != PCS_OK || n_dst == 0) return rc;
+  if (bn_partial && !p.emits_stats) return conv_no_stats(who);
+  ConvArgsX a = conv_args<ConvArgsX>(src, bias, dst, pairs, seg, n_dst, tile_rows, cin, cout, K, src_col, bn_partial, tile_order, p);
+  a.Wp = reinterpret_cast<const char *>(Wp); a.nt16 = p.nt16; a.ns = p.ns;
+  a.plane_bytes = (int64_t)K * conv_prepared_geom(cin, cout, true).plane_bytes;
+  const bool nw8 = p.nt == 512;
   hipStream_t st = as_stream(stream);
-  // Row blocks per group. The kernel is bound by the vector-memory address path (TA 78-87 % busy, MFMA pipe 29-37 %,
-  // profiles/round3_convx.md): per row block and step a column tile costs 2 A loads + 3 N / R weight-fragment loads, so R is
-  // the lever -- four row blocks per group at <= 64 columns, three at 96 (what the 256 registers of two waves per SIMD hold).
-  static const int force_r = getenv("PCS_CONVX_R") ? atoi(getenv("PCS_CONVX_R")) : 0;  // A/B
-  // measured (profiles/round3_convx.md): R = 4 at 64 columns 1.11x R = 2 (256->256 985 -> 868 us), R = 3 at 96 columns 1.08-1.10x,
-  // 32 columns lose with R > 2
-  const int rsel = force_r >= 2 && force_r <= 4 ? (nctt == 6 && force_r > 3 ? 3 : force_r) : (nctt == 6 ? 3 : (nctt == 4 ? 4 : 2));
-#define PCS_CONV5X_R(N, RR)                                                                         \
-  if (tail) return nw8 ? launch_conv5x<N, 8, 2, RR, true>(a, st) : launch_conv5x<N, 4, 2, RR, true>(a, st);  \
-  return nw8 ? launch_conv5x<N, 8, 2, RR, false>(a, st) : launch_conv5x<N, 4, 2, RR, false>(a, st);
-#define PCS_CONV5X_CASE(N)                                                                          \
-  case N:                                                                                           \
-    if (rsel == 4 && N < 6) { PCS_CONV5X_R(N, (N < 6 ? 4 : 3)) }                                      \
-    if (rsel >= 3) { PCS_CONV5X_R(N, 3) }                                                           \
-    { PCS_CONV5X_R(N, 2) }
-  switch (nctt) {
-    PCS_CONV5X_CASE(2)
-    PCS_CONV5X_CASE(4)
-    PCS_CONV5X_CASE(6)
+  // (16-column tiles per column tile, row blocks per group) the kernel is instantiated for
+#define PCS_CONV5X(N, RR)                                                                                              \
+  if (p.nctt == N && p.R == RR) {                                                                                      \
+    if (p.tail) return nw8 ? launch_conv5x<N, 8, 2, RR, true>(a, p, st) : launch_conv5x<N, 4, 2, RR, true>(a, p, st);  \
+    return nw8 ? launch_conv5x<N, 8, 2, RR, false>(a, p, st) : launch_conv5x<N, 4, 2, RR, false>(a, p, st);            \
   }
-#undef PCS_CONV5X_CASE
-#undef PCS_CONV5X_R
+  PCS_CONV5X(2, 4) PCS_CONV5X(2, 3) PCS_CONV5X(2, 2) PCS_CONV5X(4, 4) PCS_CONV5X(4, 3) PCS_CONV5X(4, 2) PCS_CONV5X(6, 3) PCS_CONV5X(6, 2)
+#undef PCS_CONV5X
   set_error("pcs_conv_gather_gemm_f32_bf16x3: unreachable");
   return PCS_EINVAL;
 }

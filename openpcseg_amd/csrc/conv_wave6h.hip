@@ -31,13 +31,6 @@
 
 using namespace pcs;
 
-namespace pcs {
-int launch_conv_wave6h(const ConvArgsH &a, int dtype, hipStream_t st);
-bool conv6h_applies(int cin, int cout, int K);
-bool conv6h_is_chunked(int cin, int cout);
-int conv6h_mode();
-}
-
 namespace {
 
 #if PCS_TRACE
@@ -54,7 +47,6 @@ template <int NCTT, int NW_>
 struct Conv6hCfg : ConvWaveCfg<NCTT, NW_> {   // no offset tables in LDS: the slice table lives in registers
   static constexpr int Q8 = 16 * NCTT / 8;          // epilogue: threads per row (8 columns each)
   static constexpr int NRG8 = 64 * NW_ / Q8;        // row groups
-  static constexpr size_t lds_bytes(int T) { return conv_tile_bytes(T, NCTT) + 64; }
 };
 
 // Tile epilogue with 16-byte stores: a thread owns 8 consecutive columns and every NRG-th row; `stats` as conv_tile_epilogue
@@ -468,92 +460,34 @@ __global__ void __launch_bounds__(64 * NW, MINW) conv_os6h_kernel(ConvArgsH a) {
 }
 
 template <typename HT, int NCTT, int NS, int RS, int NW, int KC = 1>
-int launch6h(const ConvArgsH &a, hipStream_t st) {
-  using C = Conv6hCfg<NCTT, NW>;
-  return conv_wave_launch<conv_os6h_kernel<HT, NCTT, NS, RS, NW, 2, KC>>(a, a.order != nullptr, C::NT, C::lds_bytes(a.tile_rows), st, "pcs_conv_h",
-                                                                          "pcs_conv_gather_gemm_h(wave6h)");
+int launch6h(const ConvArgsH &a, const ConvPlan &p, hipStream_t st) {
+  return conv_wave_launch<conv_os6h_kernel<HT, NCTT, NS, RS, NW, 2, KC>>(a, p, st, "pcs_conv_h", "pcs_conv_gather_gemm_h(wave6h)");
 }
 
-// (16-column tiles per column tile, 32-channel steps) the stationary-weight kernel is instantiated for, and the row blocks per
-// sub-group of each: NS x NCTT weight fragments of 4 registers stay resident next to RS x NCTT accumulators and two sets of
-// NS x RS gathered pieces
-struct Ws6Shape { int nctt, ns, rs; };
-constexpr Ws6Shape kWs6Shapes[] = {{6, 3, 2}, {6, 4, 1}, {8, 3, 1}, {8, 4, 1}, {4, 2, 2}, {8, 2, 2}, {4, 4, 2}, {6, 2, 2}, {2, 2, 2},
-                                   {2, 1, 2}, {4, 1, 2}, {6, 1, 2}, {8, 1, 2}};
-inline int conv6h_rs(int nctt, int ns) {
-  for (const auto &e : kWs6Shapes)
-    if (e.nctt == nctt && e.ns == ns) return e.rs;
-  if (nctt == 8 && (ns == 8 || ns == 12 || ns == 6)) return 1;   // chunked contractions (KC = 2 / 3 / 2)
-  if (nctt == 6 && ns == 6) return 2;
-  if (nctt == 6 && ns == 8) return 1;
-  return 0;
-}
-inline bool conv6h_chunked(int nctt, int ns) { return ns > 4; }
-int g_ws_mode = -1, g_ws_rs = 0;  // debug / A-B overrides (pcs_debug_convh_ws); -1 / 0 = environment / default
-
+// the instance of PCS_CONV6H_INSTANCES (conv_plan.h) the route picked
 template <typename HT, int NW>
-int dispatch6h(const ConvArgsH &a, int nctt, int rs, hipStream_t st) {
-#define PCS_C6H(N, S, R) \
-  if (nctt == N && a.ns == S && rs == R) return launch6h<HT, N, S, R, NW>(a, st);
-  PCS_C6H(6, 3, 2) PCS_C6H(6, 4, 2) PCS_C6H(8, 3, 2) PCS_C6H(8, 4, 1) PCS_C6H(4, 2, 2) PCS_C6H(8, 2, 2) PCS_C6H(4, 4, 2)
-  PCS_C6H(6, 2, 2) PCS_C6H(2, 2, 2) PCS_C6H(2, 1, 2) PCS_C6H(4, 1, 2) PCS_C6H(6, 1, 2) PCS_C6H(8, 1, 2)
-  PCS_C6H(6, 4, 1) PCS_C6H(8, 3, 1)
+int dispatch6h(const ConvArgsH &a, const ConvPlan &p, hipStream_t st) {
+#define PCS_C6H(N, S, R, KC, AB) \
+  if (p.nctt == N && p.ns == S && p.rs == R) return launch6h<HT, N, S / KC, R, NW, KC>(a, p, st);
+  PCS_CONV6H_INSTANCES(PCS_C6H)
 #undef PCS_C6H
-  // chunked contractions: 256 / 384 / 192 input channels on 128-column tiles, 192 / 256 on 96-column tiles
-  if (nctt == 8 && a.ns == 8) return launch6h<HT, 8, 4, 1, NW, 2>(a, st);
-  if (nctt == 8 && a.ns == 12) return launch6h<HT, 8, 4, 1, NW, 3>(a, st);
-  if (nctt == 8 && a.ns == 6) return launch6h<HT, 8, 3, 1, NW, 2>(a, st);
-  if (nctt == 6 && a.ns == 6) return launch6h<HT, 6, 3, 2, NW, 2>(a, st);
-  if (nctt == 6 && a.ns == 8) return launch6h<HT, 6, 4, 1, NW, 2>(a, st);
   set_error("pcs_conv_gather_gemm_h(wave6h): no instance for this shape");
   return PCS_EUNSUPPORTED;
 }
 
 }  // namespace
 
-namespace pcs {
-
-bool conv6h_applies(int cin, int cout, int K) {
-  if (!convh_applies(cin, cout, K) || cin % 32) return false;
-  const int nctt = conv_nctt(cout), ns = cin / 32;
-  if (conv6h_rs(nctt, ns) == 0) return false;
-  if (conv6h_mode() >= 2 || conv6h_chunked(nctt, ns)) return true;
-  // measured on the 12-frame bench maps (profiles/round6_convh_ws.md): 1.2-1.3x on the 64 ... 128-channel layers; the thin
-  // shapes (<= 2 weight fragments per step and tile, or one step) stay on conv_wave5h.hip
-  // chunked contractions (192 ... 384 input channels): 1.06-1.26x on 4-wave workgroups (tiles <= 160 rows, two per CU), 0.6-0.8x on
-  // the 8-wave ones -- the entry point (conv_wave5h.hip) sends only tiles of <= 160 rows here, the picker (conv.hip) asks for 144
-  // rows where that pays (everything but 256 -> 256 on the big stride-8 level: 0.97x)
-  if (K <= 8) return ns * nctt >= 16 && ns >= 3;   // k = 2 strided / transposed maps: one pair per row and offset
-  return ns * nctt >= 8 && ns >= 2 && !(nctt == 8 && ns == 2);
+int pcs::launch_conv_wave6h(const ConvArgsH &a, const ConvPlan &p, hipStream_t st) {
+  if (p.dtype == 1) return p.nt == 512 ? dispatch6h<Bf16, 8>(a, p, st) : dispatch6h<Bf16, 4>(a, p, st);
+  return p.nt == 512 ? dispatch6h<Fp16, 8>(a, p, st) : dispatch6h<Fp16, 4>(a, p, st);
 }
 
-int launch_conv_wave6h(const ConvArgsH &a0, int dtype, hipStream_t st) {
-  ConvArgsH a = a0;
-  const int nctt = conv_nctt(a.cout);
-  a.ncoltiles = (int)ceil_div(a.cout, 16 * nctt);
-  int rs = conv6h_rs(nctt, a.ns);
-  if (g_ws_rs == 1 && ((nctt == 6 && a.ns == 4) || (nctt == 8 && a.ns == 3))) rs = 2;   // A/B: two row blocks (spills a few registers)
-  const bool nw8 = conv_nw8(a.tile_rows, nctt);
-  if (dtype == 1) return nw8 ? dispatch6h<Bf16, 8>(a, nctt, rs, st) : dispatch6h<Bf16, 4>(a, nctt, rs, st);
-  return nw8 ? dispatch6h<Fp16, 8>(a, nctt, rs, st) : dispatch6h<Fp16, 4>(a, nctt, rs, st);
-}
-
-// 0: conv_wave5h.hip for everything; 1 (default): the shapes of conv6h_applies() that measured faster (policy below);
-// 2: every shape conv6h_applies() serves (A/B)
-bool conv6h_is_chunked(int cin, int cout) { return cin % 32 == 0 && conv6h_chunked(conv_nctt(cout), cin / 32); }
-
-int conv6h_mode() {
-  static const int ws = getenv("PCS_CONVH_WS") ? atoi(getenv("PCS_CONVH_WS")) : 1;
-  return g_ws_mode >= 0 ? g_ws_mode : ws;
-}
-
-}  // namespace pcs
-
-// debug / A-B (tools/convh_ws_ab.py): mode -1 environment, 0 off, 1 on; rs = 1: two-row-block sub-groups for the two shapes that
-// have both instances (128 -> 96, 96 -> 128)
+// debug / A-B (tools/convh_ws_ab.py): mode -1 environment (PCS_CONVH_WS), 0: conv_wave5h.hip for everything, 1 (default): the
+// shapes of conv6h_applies() that measured faster, >= 2: every shape it has an instance for; rs = 1: two-row-block sub-groups for
+// the two shapes that have both instances (128 -> 96, 96 -> 128)
 extern "C" void pcs_debug_convh_ws(int32_t mode, int32_t ru, int32_t rs) {
   (void)ru;
-  g_ws_mode = mode; g_ws_rs = rs & 1;
+  conv_env().ws_debug = mode; conv_env().ws_ab = rs & 1;
 }
 
 #if PCS_TRACE

@@ -1,7 +1,7 @@
 // The skeleton of the wave-autonomous fused-convolution kernels, each piece defined once:
 //   conv_os5_kernel (conv_wave5.hip, fp32), conv_os5h_kernel (conv_wave5h.hip, bf16 / fp16), conv_os5x_kernel (conv_wave5x.hip,
 //   fp32 as three bf16 planes), conv_os6h_kernel (conv_wave6h.hip, weight-stationary half), conv_os4_kernel (conv_wave4.hip).
-// Launch shape (config, LDS size, 4- or 8-wave workgroups, the launch itself), workgroup id -> tile, the LDS layout of a tile
+// Launch shape (config, tile size, 4- or 8-wave workgroups; the plan and the launch itself: conv_plan.h), workgroup id -> tile, the LDS layout of a tile
 // with its offset-list prologue, group -> offset entry (`conv_locate`), the ticket-ordered commit, the two write-back functors,
 // the fragment order of the prepared weights and the decoding of pcs_conv_epilogue. The .hip files keep what is theirs: operand
 // loads, the MFMA schedule, pipelining and their debug / trace / ablation switches. Everything here is inlined into its caller
@@ -39,7 +39,6 @@ struct ConvWaveCfg {
   static constexpr int N1 = NCTT % 2;        // one single tile
   static constexpr int NWL = N4 + N2 + N1;   // fp32 W loads per contraction step
   static constexpr int SINK = kConvSinkRows;
-  static constexpr size_t lds_bytes(int T) { return conv_tile_bytes(T, NCTT) + kConvTableBytes; }
 };
 
 // local column (inside a column tile of nctt 16-column tiles) that lane n of tile tl feeds -- the interleave the commit and the
@@ -72,29 +71,6 @@ __device__ __forceinline__ void conv_wfrag_values(const float *__restrict__ W, i
     if (col < ccols && c < ccon)
       v[j] = transpose ? W[((int64_t)k * A + col) * B + c] : W[((int64_t)k * A + c) * B + col];
   }
-}
-
-// One launch: grid (padded to 8 * ncoltiles for the round-robin deal of an ordered launch), the checks, the once-only attribute
-// of this kernel instance (the function is a template on the kernel pointer), `pre(nblocks)` right before the launch (trace
-// preparation, debug prints). `who` heads the error texts, `label` names the launch to check_launch.
-template <auto Kern, typename Args, typename Pre>
-int conv_wave_launch(const Args &a, bool pad8, int nt, size_t lds, hipStream_t st, const char *who, const char *label, Pre pre) {
-  const int64_t nblocks = pad8 ? ceil_div(a.ntiles, 8) * 8 * a.ncoltiles : a.ntiles * a.ncoltiles;
-  if (nblocks <= 0) return PCS_OK;
-  if (nblocks > 0x7FFFFFFF) { set_error("%s: grid too large", who); return PCS_EUNSUPPORTED; }
-  if (lds > kMaxDynLds) { set_error("%s: tile_rows too large for this column tile", who); return PCS_EUNSUPPORTED; }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
-    attr_set = true;
-  }
-  pre(nblocks);
-  hipLaunchKernelGGL(Kern, dim3((unsigned)nblocks), dim3(nt), lds, st, a);
-  return check_launch(label);
-}
-template <auto Kern, typename Args>
-int conv_wave_launch(const Args &a, bool pad8, int nt, size_t lds, hipStream_t st, const char *who, const char *label) {
-  return conv_wave_launch<Kern>(a, pad8, nt, lds, st, who, label, [](int64_t) {});
 }
 
 // pcs_conv_epilogue of the _ex entry points -> addend / act_slope of the kernels (ReLU = their LeakyReLU branch with slope 0;

@@ -86,10 +86,8 @@ __global__ void __launch_bounds__(256) weights_multi_kernel(const Job *__restric
 
 int64_t job_blocks(pcs_weight_job &j) {
   if (j.kind == 0) return (int64_t)j.K * ceil_div(j.A, 32) * ceil_div(j.B, 32);
-  const int ccon = j.transpose ? j.B : j.A, ccols = j.transpose ? j.A : j.B;
-  j.nctt = conv_nctt(ccols);
-  j.nt16 = (int)ceil_div(ccols, 16 * j.nctt) * j.nctt;
-  j.ns = (int)ceil_div(ccon, 32);
+  const ConvPreparedGeom g = conv_prepared_geom(j.transpose ? j.B : j.A, j.transpose ? j.A : j.B, false);
+  j.nctt = g.nctt; j.nt16 = g.nt16; j.ns = g.ns;
   return ceil_div((int64_t)j.K * j.nt16 * j.ns * 64, 256);
 }
 

@@ -136,6 +136,7 @@ SIGNATURES = {
     "pcs_lovasz_softmax_f32": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int64, _P, _P, _P, c_int64, _P]),
     "pcs_debug_convh_ws": (None, [c_int32, c_int32, c_int32]),       # measurement switches (A/B tools), not part of the contract
     "pcs_debug_wgrad_interleave": (None, [c_int32]),
+    "pcs_debug_conv_plan": (None, [c_int32] * 7 + [_P]),             # host only: the route's plan for a call (tests read it)
     "pcs_debug_pointvoxel_h_inflight": (None, [c_int32]),
 }
 

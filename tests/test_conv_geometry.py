@@ -7,9 +7,9 @@ Two scene families: the golden scene (expected values = outputs of the reference
 dense scene `random_scene(rng, 40000, 60, 3)` of test_hip_parity.py (38 811 voxels, 8 pairs per row at K = 125, and the same
 scene shifted to negative coordinates; expected values = the oracle, which tests/test_oracle_pinning.py pins to the same fixture).
 
-Which kernel a call reaches is asserted, not assumed: through the library's own shape queries (pcs_conv_uses_tile_order = conv_wave5,
-pcs_conv_supports_epilogue without it = conv_wave4, neither = conv_block; pcs_conv_h_applies, pcs_conv_x3_applies,
-pcs_conv_emits_bn_partials) and through call counters on the backend entries. Bounds are the suite's: 2e-5 of the tensor maximum for
+Which kernel a call reaches is asserted, not assumed: through the plan the library launches from (pcs_debug_conv_plan: family, waves,
+column tiles), its shape queries (pcs_conv_h_applies, pcs_conv_x3_applies, pcs_conv_emits_bn_partials -- fields of the same plan)
+and through call counters on the backend entries. Bounds are the suite's: 2e-5 of the tensor maximum for
 fp32 against the oracle, close_half for 16-bit outputs, 40 half-ulps of the maximum under autocast (test_conv3d_under_autocast)."""
 import contextlib
 import ctypes
@@ -22,6 +22,7 @@ import geometry_cases as gc
 from oracle import oracle as orc
 from test_dense_parity import _HALF_TOL, _round_half, _ws_mode, close_half
 from test_hip_parity import random_scene
+from test_host_api import PLAN_EXTRAS, PLAN_ORDER, PLAN_STATS, conv_plan
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -55,6 +56,8 @@ def scene(which, tensor_stride=1):
             c = gc.input_coords(OPS, tensor_stride)
         elif which == "golden_neg":
             c = GEO["neg_coords"]
+        elif which == "small":   # one batch, about 1500 of the 1728 cells of a 12^3 box: 6 row tiles at 288 rows, ~20 pairs per row at k3
+            c = random_scene(np.random.default_rng(12), 3500, 12, 1)
         else:
             c = random_scene(np.random.default_rng(4), 40000, 60, 3)
             c[:, :3] *= tensor_stride   # a level at tensor stride s holds multiples of s
@@ -157,10 +160,9 @@ DGRAD_FAMILY = {(32, 32): "wave5", (64, 96): "wave5", (96, 128): "wave5", (16, 3
 
 
 def fp32_family(lib, cin, cout, k):
-    """Which of the three fused fp32 kernels pcs_conv_gather_gemm_f32 launches for a shape, from the library's own queries."""
-    if lib.pcs_conv_uses_tile_order(cin, cout, k, 0):
-        return "wave5"
-    return "wave4" if lib.pcs_conv_supports_epilogue(cin, cout, k, 0) else "block"
+    """Which of the three fused fp32 kernels pcs_conv_gather_gemm_f32 launches for a shape on aligned tensors: the plan's family (it
+    does not depend on the tile height)."""
+    return conv_plan(lib, "fp32", cin, cout, k, 128)["family"]
 
 
 def operands(rng, c, cin, cout, transposed=False):
@@ -449,6 +451,103 @@ def test_rows_without_pairs(hip, name, direction):
         if got:
             stats_match(hip, got, y3b, cout)
     assert fams == ({"block"} if k > 32 else {"wave5", "wave4", "block"})
+
+
+# ---- the boundaries the plan owns --------------------------------------------------------------------------------------------------------
+# (entry, cin, cout, case of NEG_CASES on the small scene, [(tile_rows, family, waves, 16-column tiles per column tile, kc)])
+PLAN_BOUNDARIES = [
+    # 4-wave workgroups while two tiles fit a CU's LDS (conv_nw8): 128 columns 144 | 160, 96 columns 192 | 208, 64 columns 288 | 304;
+    # fp32 128 -> 128 narrows to 64-column tiles from 176 rows on (conv5_nctt), which fit twice again
+    ("fp32", 128, 128, "k3s1", [(144, "wave5", 4, 8, 0), (160, "wave5", 8, 8, 0), (176, "wave5", 4, 4, 0)]),
+    ("bf16", 128, 128, "k3s1", [(144, "wave6h", 4, 8, 1), (160, "wave6h", 8, 8, 1)]),
+    ("fp16", 128, 128, "k3s1", [(144, "wave6h", 4, 8, 1), (160, "wave6h", 8, 8, 1)]),
+    ("fp32", 96, 96, "k3s1", [(192, "wave5", 4, 6, 0), (208, "wave5", 8, 6, 0)]),
+    ("bf16", 96, 96, "k3s1", [(192, "wave6h", 4, 6, 1), (208, "wave6h", 8, 6, 1)]),
+    ("x3", 96, 96, "k3s1", [(192, "wave5x", 4, 6, 0), (208, "wave5x", 8, 6, 0)]),
+    ("fp32", 64, 64, "k3s1", [(288, "wave5", 4, 4, 0), (304, "wave5", 8, 4, 0)]),
+    ("bf16", 64, 64, "k3s1", [(288, "wave6h", 4, 4, 1), (304, "wave6h", 8, 4, 1)]),
+    ("x3", 64, 64, "k3s1", [(288, "wave5x", 4, 4, 0), (304, "wave5x", 8, 4, 0)]),
+    # the chunked weight-stationary instances stop above 160 rows
+    ("bf16", 256, 256, "k3s1", [(160, "wave6h", 8, 8, 2), (176, "wave5h", 8, 8, 0)]),
+    # K <= 8 (one pair per row and offset): the weight-stationary kernel from 16 fragments per step on
+    ("bf16", 96, 96, "k2s2", [(128, "wave6h", 4, 6, 1)]),
+    ("bf16", 64, 64, "k2s2", [(128, "wave5h", 4, 4, 0)]),
+    # 32 columns on 256 threads: 32 row groups, the statistics need 64 rows of scratch (48: the query says no, no partials come back)
+    ("fp32", 32, 32, "k3s1", [(48, "wave5", 4, 2, 0), (64, "wave5", 4, 2, 0)]),
+    ("bf16", 32, 32, "k3s1", [(48, "wave5h", 4, 2, 0), (64, "wave5h", 4, 2, 0)]),
+    ("x3", 32, 32, "k3s1", [(48, "wave5x", 4, 2, 0), (64, "wave5x", 4, 2, 0)]),
+]
+_PLAN_REFS = {}
+
+
+def plan_reference(c, name, cin, cout, half):
+    """Operands (rounded to `half` where given) and the oracle's output for them, computed once per (map, shape, storage).
+    The features are scaled by 0.2: operands() sizes the weights for ~8 pairs per row and this k3 map has ~20, and the last check of
+    stats_match is absolute (1e-7 on the mean) while the write-back sums in fp32 about the tile's first row -- at worst an error of
+    2^-24 n |x - pivot| in a column sum, 3.6e-4 sigma over these 1510 rows with a pivot 4 sigma out. At sigma = 0.32 that is 7.6e-8 on
+    the mean: inside the bound for any pivot, not by the luck of the draw (at sigma = 1.6 a 176-row tile measured 1.3e-7)."""
+    key = (name, cin, cout, half)
+    if key not in _PLAN_REFS:
+        rng = np.random.default_rng(c.K * 1000 + cin + cout)
+        x, w, _ = operands(rng, c, cin, cout)
+        x *= np.float32(0.2)
+        add = rng.normal(size=(c.n_out, cout)).astype(np.float32)
+        if half is not None:
+            x, w, add = (_round_half(v, half) for v in (x, w, add))
+        _PLAN_REFS[key] = (x, w, add, orc.conv_fwd(x, w, c.nbmaps, c.nbsizes, (c.n_in, c.n_out)))
+    return _PLAN_REFS[key]
+
+
+@pytest.mark.parametrize("entry,cin,cout,name,heights", PLAN_BOUNDARIES,
+                         ids=["%s-%dx%d-%s" % b[:4] for b in PLAN_BOUNDARIES])
+def test_plan_boundaries(hip, entry, cin, cout, name, heights):
+    """The three entries with tile_rows forced to both sides of every boundary conv_route owns, on a small dense cloud (about 1500
+    voxels in a 12^3 box: the k3 map has ~20 pairs per row, so the heaviest-first order is launched; 6 row tiles at 288 rows) and its
+    k2 stride-2 map. The family, wave count, column-tile width and contraction chunks are read from the plan of that very call
+    (statistics + order + extras flags as the call carries them); the output, the BatchNorm sums of the write-back and the output
+    with an addend are held to the file's bounds on every side."""
+    c = build_case("small", name, gc.NEG_CASES)
+    assert 1400 <= c.n_in <= 1600 and c.K == (27 if name == "k3s1" else 8)
+    kmap, lib = c.entry.fwd, hip.lib
+    ordered = hip._wants_order(kmap)
+    if name == "k3s1":
+        assert ordered and c.nbmaps.shape[0] > 6 * c.n_out and (c.n_out + 287) // 288 >= 5
+    half = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(entry)
+    x, w, add, ref = plan_reference(c, name, cin, cout, half)
+    dx, dw, dadd = t(x), t(w), t(add)
+    if half is not None:
+        dx, dadd, wp = dx.to(half), dadd.to(half), hip.prepare_weights_h(dw, half, transpose=False)
+        run = lambda **kw: hip.conv_gather_gemm_h(dx, wp, c.K, cout, kmap, **kw)
+    elif entry == "x3":
+        wp = hip.prepare_weights_x3(dw, transpose=False)
+        run = lambda **kw: hip.conv_gather_gemm_x3(dx, wp, c.K, cout, kmap, **kw)
+    else:
+        run = lambda **kw: hip.conv_gather_gemm(dx, dw, kmap, **kw)
+    close = (lambda y, r, what: close_half(y, r, half)) if half is not None else close32
+    for tile, family, waves, nctt, kc in heights:
+        what = "%s %dx%d %s tile %d" % (entry, cin, cout, name, tile)
+        flags = PLAN_ORDER if ordered else 0
+        p = conv_plan(lib, entry, cin, cout, c.K, tile, flags | PLAN_STATS)
+        assert (p["family"], p["waves"], p["nctt"], p["kc"]) == (family, waves, nctt, kc), (what, p)
+        assert p["ncoltiles"] == -(-cout // (16 * nctt)) and p["reads_order"]
+        assert p["emits_stats"] == (tile >= 64 or cout > 32), (what, p)
+        got = []
+        y = run(tile_rows=tile, bn_sums=got)
+        assert len(got) == (1 if p["emits_stats"] else 0), what
+        close(y, ref, what)
+        if got:
+            stats_match(hip, got, y, cout)
+        assert torch.equal(y, run(tile_rows=tile)), what   # the statistics change nothing in the output; bit-reproducible
+        if entry == "x3":
+            assert not p["takes_extras"]
+            continue
+        pa = conv_plan(lib, entry, cin, cout, c.K, tile, flags | PLAN_EXTRAS)
+        assert pa["takes_extras"] and (pa["family"], pa["waves"], pa["nctt"]) == (family, waves, nctt), (what, pa)
+        ya = run(tile_rows=tile, addend=dadd)
+        if half is None:
+            assert torch.equal(ya, y + dadd), what
+        else:
+            close_half(ya, ref + add, half)
 
 
 # ---- functional.conv3d: which backend entry ran, and what it returned ----------------------------------------------------------------------

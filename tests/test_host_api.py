@@ -927,3 +927,114 @@ def test_weight_gradient_entry_table(monkeypatch):
                 assert one(site, 96, 96, f32, None)[4] is False, site
     finally:
         F.set_wgrad_policy("fp32")
+
+
+# ---- the convolution plan (csrc/conv_plan.h): what the entries launch from and the shape queries answer from ----------------------------
+PLAN_FAMILY = ("none", "block", "wave4", "wave5", "wave5h", "wave6h", "wave5x")   # ConvFamily
+PLAN_KIND = {"fp32": (0, 0), "bf16": (1, 1), "fp16": (1, 2), "x3": (2, 0)}           # entry -> (ConvKind, dtype code)
+PLAN_STATS, PLAN_ORDER, PLAN_EXTRAS, PLAN_POST_AFFINE, PLAN_UNALIGNED = 1, 2, 4, 8, 16   # what the call carries
+
+
+def conv_plan(lib, entry, cin, cout, k, tile_rows, flags=0):
+    """pcs_debug_conv_plan as a dict: the fields of the ConvPlan a call of `entry` with these sizes and flags is launched from."""
+    import ctypes
+    out = (ctypes.c_int32 * 12)()
+    kind, dtype = PLAN_KIND[entry]
+    lib.pcs_debug_conv_plan(kind, dtype, cin, cout, k, tile_rows, flags, out)
+    keys = ("family", "nctt", "ncoltiles", "threads", "tail", "R", "rs", "kc", "nt16", "ns", "lds", "answers")
+    p = dict(zip(keys, out))
+    p["family"] = PLAN_FAMILY[p["family"]]
+    p["waves"] = p["threads"] // 64
+    p["emits_stats"], p["reads_order"], p["takes_extras"] = bool(p["answers"] & 1), bool(p["answers"] & 2), bool(p["answers"] & 4)
+    return p
+
+
+def test_conv_plan_and_queries_agree():
+    """Every shape query is the plan's own field: over dtype 0 / 1 / 2 and the x3 entry, channel widths of the configs (and some no
+    wave kernel serves), K on both sides of 8 and 32, every tile height 16 .. 512 plus 0, 8 and 520, and degenerate sizes, the plan of
+    pcs_debug_conv_plan and the query give the same answer. The prepared-weights sizes are K x nt16 x ns KB of the plan (x 3 planes for
+    bf16x3), its column tiles cover cout, and the tile-order / extras answers do not depend on the tile height."""
+    lib = native.load_library()
+    widths = (4, 5, 16, 32, 48, 56, 64, 96, 100, 128, 168, 192, 256, 384, 672)
+    tiles = (0, 8) + tuple(range(16, 513, 16)) + (520,)
+    shapes = [(ci, co, k) for ci in widths for co in widths for k in (1, 8, 9, 27, 32, 33)] + [(0, 32, 27), (32, 0, 27), (32, 32, 0), (-4, 32, 27)]
+    served = set()
+    for cin, cout, k in shapes:
+        for entry in ("fp32", "bf16", "fp16", "x3"):
+            x3, dtype = entry == "x3", PLAN_KIND[entry][1]
+            order = None if x3 else bool(lib.pcs_conv_uses_tile_order(cin, cout, k, dtype))
+            extras = None if x3 else bool(lib.pcs_conv_supports_epilogue(cin, cout, k, dtype))
+            for t in tiles:
+                p = conv_plan(lib, entry, cin, cout, k, t, PLAN_STATS)
+                emits = lib.pcs_conv_x3_emits_bn_partials(cin, cout, k, t) if x3 else lib.pcs_conv_emits_bn_partials(cin, cout, k, t, dtype)
+                assert p["emits_stats"] == bool(emits), (entry, cin, cout, k, t, p)
+                if x3:
+                    assert p["reads_order"] == (p["family"] == "wave5x") and not p["takes_extras"]
+                else:
+                    assert (p["reads_order"], p["takes_extras"]) == (order, extras), (entry, cin, cout, k, t, p)
+                if p["family"] == "none":
+                    assert p["answers"] == 0 and (min(cin, cout, k) <= 0 or entry != "fp32")
+                    continue
+                served.add(p["family"])
+                assert p["ncoltiles"] * 16 * p["nctt"] >= cout > (p["ncoltiles"] - 1) * 16 * p["nctt"] and p["threads"] in (128, 256, 384, 512)
+                if entry == "fp32":
+                    continue
+                applies = lib.pcs_conv_x3_applies(cin, cout, k) if x3 else lib.pcs_conv_h_applies(cin, cout, k)
+                nbytes = lib.pcs_conv_prepared_weights_x3_bytes(k, cin, cout) if x3 else lib.pcs_conv_prepared_weights_bytes(k, cin, cout)
+                assert applies == 1 and nbytes == k * p["nt16"] * p["ns"] * 1024 * (3 if x3 else 1), (entry, cin, cout, k, p)
+                assert p["nt16"] == p["ncoltiles"] * p["nctt"] and p["ns"] == (cin + 31) // 32
+                if x3:
+                    assert p["nctt"] == lib.pcs_conv_x3_column_tiles(cout)
+    assert served == set(PLAN_FAMILY[1:])
+    # what the call carries: statistics off 16 bytes go nowhere, and the generic kernel is what an unaligned tensor runs on
+    p = conv_plan(lib, "fp32", 64, 64, 27, 128, PLAN_STATS | PLAN_UNALIGNED)
+    assert (p["family"], p["emits_stats"], p["takes_extras"], p["reads_order"]) == ("block", False, False, False)
+
+
+# (entry, cin, cout, K, (n_dst, n_pairs) of the 12-frame bench map the shape runs on, the picker's height there,
+#  family, nctt, waves, TAIL, R, rs, kc). MinkUNet / SPVCNN / RPVNet / Cylinder3D widths; x3 serves 384 -> 256 as 64-column tiles
+# (pcs_conv_x3_applies says 1: convx_nctt(256) = 4), so it is pinned with the others.
+PLAN_TABLE = [
+    ("fp32", 32, 32, 27, (688382, 3790760), 288, "wave5", 2, 4, 0, 2, 0, 0),
+    ("bf16", 32, 32, 27, (688382, 3790760), 144, "wave5h", 2, 4, 0, 2, 0, 0),
+    ("x3", 32, 32, 27, (688382, 3790760), 288, "wave5x", 2, 4, 0, 2, 0, 0),
+    ("fp32", 64, 64, 27, (329421, 2752033), 224, "wave5", 4, 4, 0, 2, 0, 0),
+    ("bf16", 64, 64, 27, (329421, 2752033), 144, "wave6h", 4, 4, 0, 1, 2, 1),
+    ("x3", 64, 64, 27, (329421, 2752033), 224, "wave5x", 4, 4, 0, 4, 0, 0),
+    ("fp32", 96, 96, 27, (1158864, 5112372), 384, "wave5", 6, 8, 0, 2, 0, 0),
+    ("bf16", 96, 96, 27, (1158864, 5112372), 192, "wave6h", 6, 4, 0, 1, 2, 1),
+    ("x3", 96, 96, 27, (1158864, 5112372), 384, "wave5x", 6, 8, 0, 3, 0, 0),
+    ("fp32", 128, 96, 27, (1158864, 5112372), 384, "wave5", 6, 8, 0, 2, 0, 0),
+    ("bf16", 128, 96, 27, (1158864, 5112372), 192, "wave6h", 6, 4, 0, 1, 1, 1),
+    ("x3", 128, 96, 27, (1158864, 5112372), 384, "wave5x", 6, 8, 0, 3, 0, 0),
+    ("fp32", 128, 128, 27, (113008, 1001308), 224, "wave5", 4, 4, 0, 2, 0, 0),
+    ("bf16", 128, 128, 27, (113008, 1001308), 112, "wave6h", 8, 4, 0, 1, 1, 1),
+    ("x3", 128, 128, 27, (113008, 1001308), 224, "wave5x", 4, 4, 0, 4, 0, 0),
+    ("fp32", 256, 256, 27, (36068, 331722), 288, "wave5", 4, 4, 0, 2, 0, 0),
+    ("bf16", 256, 256, 27, (36068, 331722), 144, "wave6h", 8, 4, 0, 1, 1, 2),
+    ("x3", 256, 256, 27, (36068, 331722), 288, "wave5x", 4, 4, 0, 4, 0, 0),
+    ("fp32", 384, 256, 27, (113008, 1001308), 256, "wave5", 4, 4, 0, 2, 0, 0),
+    ("bf16", 384, 256, 27, (113008, 1001308), 144, "wave6h", 8, 4, 0, 1, 1, 3),
+    ("x3", 384, 256, 27, (113008, 1001308), 256, "wave5x", 4, 4, 0, 4, 0, 0),
+    ("fp32", 16, 32, 27, (688382, 3790760), 128, "wave4", 2, 4, 1, 1, 0, 0),
+    ("fp32", 5, 33, 27, (688382, 3790760), 128, "block", 4, 4, 1, 1, 0, 0),
+    ("fp32", 96, 96, 8, (329421, 688382), 192, "wave5", 6, 4, 0, 2, 0, 0),
+    ("bf16", 96, 96, 8, (329421, 688382), 192, "wave6h", 6, 4, 0, 1, 2, 1),
+    ("x3", 96, 96, 8, (329421, 688382), 192, "wave5x", 6, 4, 0, 3, 0, 0),
+    ("fp32", 64, 64, 8, (113008, 329421), 224, "wave5", 4, 4, 0, 2, 0, 0),
+    ("bf16", 64, 64, 8, (113008, 329421), 112, "wave5h", 4, 4, 0, 2, 0, 0),
+    ("x3", 64, 64, 8, (113008, 329421), 224, "wave5x", 4, 4, 0, 4, 0, 0),
+]
+
+
+def test_conv_plan_of_the_workload_shapes_is_pinned():
+    """The plan of the shapes the five workloads run, at the tile height the picker gives on the bench maps (a 256-CU device, which
+    is also what the picker assumes without one): kernel family, 16-column tiles per column tile, waves, TAIL instance, row blocks
+    per group, and the weight-stationary kernel's row blocks per sub-group and contraction chunks. Values written down from the
+    launchers of the parent of the plan (profiles/conv_plan_refactor.md has the kernel names of a traced run next to them)."""
+    lib = native.load_library()
+    for entry, cin, cout, k, (n_dst, n_pairs), tile, family, nctt, waves, tail, r, rs, kc in PLAN_TABLE:
+        assert lib.pcs_conv_pick_tile_rows_dt(n_dst, n_pairs, k, cin, cout, PLAN_KIND[entry][1]) == tile, (entry, cin, cout, k)
+        p = conv_plan(lib, entry, cin, cout, k, tile)
+        assert (p["family"], p["nctt"], p["waves"], p["tail"], p["R"], p["rs"], p["kc"]) == (family, nctt, waves, tail, r, rs, kc), \
+            (entry, cin, cout, k, tile, p)

@@ -45,6 +45,13 @@ def main():
     rows.append(("be.conv_wgrad", cost(lambda: be.conv_wgrad(x, gy, entry.fwd, 0))))
     xh, gh = x.bfloat16(), gy.bfloat16()
     rows.append(("be.conv_wgrad_h", cost(lambda: be.conv_wgrad_h(xh, gh, entry.fwd, 0))))
+    wp = be.prepare_weights_h(w, torch.bfloat16, transpose=False)
+    rows.append(("be.conv_gather_gemm_h", cost(lambda: be.conv_gather_gemm_h(xh, wp, 27, 64, entry.fwd))))
+    lib = be.lib   # the shape queries a conv launch asks (each one route through the library's plan)
+    rows.append(("lib.pcs_conv_pick_tile_rows_dt", cost(lambda: lib.pcs_conv_pick_tile_rows_dt(n, 20 * n, 27, 256, 256, 1), 5000)))
+    rows.append(("lib.pcs_conv_emits_bn_partials", cost(lambda: lib.pcs_conv_emits_bn_partials(256, 256, 27, 144, 1), 5000)))
+    rows.append(("lib.pcs_conv_uses_tile_order", cost(lambda: lib.pcs_conv_uses_tile_order(64, 64, 27, 0), 5000)))
+    rows.append(("lib.pcs_conv_supports_epilogue", cost(lambda: lib.pcs_conv_supports_epilogue(64, 64, 27, 0), 5000)))
     rows.append(("w.transpose(1,2).contiguous()", cost(lambda: w.transpose(1, 2).contiguous())))
     sums = be.bn_stats(x)
     stat = be.bn_finalize(sums, float(n), 1e-5, 0.1, None, None)
