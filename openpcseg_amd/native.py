@@ -231,21 +231,37 @@ _cache_key.uncached = 0
 CACHE_STATS = {"hit": 0, "miss": 0, "cross": 0, "epoch": 0}
 
 
-def _cached(holder, name, key, make):
-    """holder.<name> = (key, value[, epoch]) memo; rebuilt when the key differs. Tensors that refuse attributes just recompute."""
-    hit = getattr(holder, name, None)
-    if hit is not None and hit[0] == key:
+def _cached(holder, slot, extra, make):
+    """holder.<slot> = (_cache_key(holder) + extra, value, epoch) memo; rebuilt when the key differs. Tensors that refuse attributes recompute."""
+    hit = getattr(holder, slot, None)
+    if hit is not None and hit[0] == _cache_key(holder) + extra:
         CACHE_STATS["hit"] += 1
-        if len(hit) > 2 and hit[2] != CACHE_STATS["epoch"]:
+        if hit[2] != CACHE_STATS["epoch"]:
             CACHE_STATS["cross"] += 1
         return hit[1]
     CACHE_STATS["miss"] += 1
-    value = make()
+    return _cache_seed(holder, slot, extra, make())
+
+
+def _cache_seed(holder, slot, extra, value):
+    """Store a ready `value` as the memo _cached(holder, slot, extra, ...) will find -> value."""
     try:
-        setattr(holder, name, (key, value, CACHE_STATS["epoch"]))
+        setattr(holder, slot, (_cache_key(holder) + extra, value, CACHE_STATS["epoch"]))
     except AttributeError:
         pass
     return value
+
+
+def _vox_csr_memo(holder, m, n):
+    """(holder, slot, extra) of the point order of voxelize_fwd over m voxels and n points: what it looks up, what unique_inverse_csr seeds."""
+    return holder, "_pcs_vox_csr", (m, n)
+
+
+def _sorted_csr(flat, m):
+    """The torch half of HipBackend._csr (same contract); host tensors too."""
+    vals, order = torch.sort(flat, stable=True)
+    rowptr = torch.searchsorted(vals, torch.arange(m + 1, device=flat.device, dtype=vals.dtype))
+    return order.contiguous(), rowptr.contiguous()
 
 
 class HashTable:
@@ -421,7 +437,7 @@ class HipBackend:
         c = feats.shape[1]
         m = counts.shape[0]
         holder = cache_on if cache_on is not None else idx
-        csr = _cached(holder, "_pcs_vox_csr", _cache_key(holder) + (m, idx.shape[0]), lambda: self._csr(idx, m))
+        csr = _cached(*_vox_csr_memo(holder, m, idx.shape[0]), lambda: self._csr(idx, m))
         out = torch.empty((m, c), dtype=feats.dtype, device=feats.device)
         self._twin("pcs_voxelize_fwd_csr", code, [_ptr(feats), _ptr(csr[0]), _ptr(csr[1]), _ptr(counts), m, c], [_ptr(out), _stream()])
         return out
@@ -513,7 +529,7 @@ class HipBackend:
         gout fp32, bf16 or fp16, gfeat in the same dtype; w8 fp32."""
         gout, code = self._pv_feats(gout, "grad_output")
         n, c = gout.shape
-        csr = _cached(idx8, "_pcs_csr", _cache_key(idx8) + (m,), lambda: self._csr(idx8, m))
+        csr = self._index_csr(idx8, m)
         gfeat = torch.empty((m, c), dtype=gout.dtype, device=gout.device)
         if code:
             w8 = _dev(w8, "weights", torch.float32)
@@ -534,8 +550,7 @@ class HipBackend:
     def level_table(self, voxel_coords):
         """Hash table over one level's voxel coordinates, cached on the coordinate tensor (shared with its kernel maps)."""
         voxel_coords = _dev(voxel_coords, "coords", torch.int32)
-        return _cached(voxel_coords, "_pcs_table", _cache_key(voxel_coords),
-                       lambda: self.table_build(self.hash(voxel_coords)))
+        return _cached(voxel_coords, "_pcs_table", (), lambda: self.table_build(self.hash(voxel_coords)))
 
     def corner_map(self, point_coords, voxel_coords, stride):
         """(idx8 (N,8) int32, w8 (N,8) float32) of voxel_to_point in one kernel: rows of the 8 corner voxels of every
@@ -932,29 +947,33 @@ class HipBackend:
 
     # -- cylinder / range scatter ---------------------------------------------------------------
     def _csr(self, index, m):
-        """(order, rowptr) of a scatter index: entries sorted by target row (stable), row starts. int32 device indices
-        (voxelize, devoxelize) through pcs_index_csr_i32 -- a radix sort over the bits of m only; other dtypes through torch."""
+        """(order, rowptr) of a scatter index, the one place that groups entries by target row. Entries are sorted by row; equal rows
+        are in ascending position; entries with a key outside [0, m) lie outside [rowptr[0], rowptr[m]); rowptr has m + 1 entries.
+        int32 device indices (voxelize, devoxelize) through pcs_index_csr_i32 -- a radix sort over the bits of m only; other dtypes,
+        and everything under PCS_INDEX_CSR=0, through torch's stable sort (_sorted_csr)."""
         flat = index.reshape(-1)
-        if flat.is_cuda and flat.dtype == torch.int32 and os.environ.get("PCS_INDEX_CSR", "1") != "0":
-            flat = flat if flat.is_contiguous() else flat.contiguous()
-            n = flat.numel()
-            order = torch.empty(n, dtype=torch.int64, device=flat.device)
-            rowptr = torch.empty(m + 1, dtype=torch.int64, device=flat.device)
-            ws_bytes = self.lib.pcs_index_csr_ws_bytes(n, m)
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=flat.device)
-            _check(self.lib.pcs_index_csr_i32(_ptr(flat), n, m, _ptr(order), _ptr(rowptr), _ptr(ws), ws_bytes, _stream()),
-                   "pcs_index_csr_i32")
-            return order, rowptr
-        vals, order = torch.sort(flat)
-        rowptr = torch.searchsorted(vals, torch.arange(m + 1, device=index.device, dtype=vals.dtype))
-        return order.contiguous(), rowptr.contiguous()
+        if not (flat.is_cuda and flat.dtype == torch.int32 and os.environ.get("PCS_INDEX_CSR", "1") != "0"):
+            return _sorted_csr(flat, m)
+        flat = flat if flat.is_contiguous() else flat.contiguous()
+        n = flat.numel()
+        order = torch.empty(n, dtype=torch.int64, device=flat.device)
+        rowptr = torch.empty(m + 1, dtype=torch.int64, device=flat.device)
+        ws_bytes = self.lib.pcs_index_csr_ws_bytes(n, m)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=flat.device)
+        _check(self.lib.pcs_index_csr_i32(_ptr(flat), n, m, _ptr(order), _ptr(rowptr), _ptr(ws), ws_bytes, _stream()),
+               "pcs_index_csr_i32")
+        return order, rowptr
+
+    def _index_csr(self, index, m):
+        """_csr(index, m), cached on the index tensor: one map serves every call over it (each backward of one devoxelize forward in
+        every dtype; the several tensors the cylinder models scatter over one index)."""
+        return _cached(index, "_pcs_csr", (m,), lambda: self._csr(index, m))
 
     def scatter_max_fwd(self, src, index, m):
         src = _dev(src, "src", torch.float32)
         index = _dev(index, "index", torch.int64)
         c = src.shape[1]
-        # the cylinder models scatter several tensors over one index
-        order, rowptr = _cached(index, "_pcs_csr", _cache_key(index) + (m,), lambda: self._csr(index, m))
+        order, rowptr = self._index_csr(index, m)
         out = torch.empty((m, c), dtype=torch.float32, device=src.device)
         arg = torch.empty((m, c), dtype=torch.int32, device=src.device)
         _check(self.lib.pcs_scatter_max_fwd_f32(_ptr(src), _ptr(order), _ptr(rowptr), m, c, _ptr(out), _ptr(arg),
@@ -980,9 +999,8 @@ class HipBackend:
         def make():
             pb, px, py = pxpy[:, 0].long(), pxpy[:, 1].long(), pxpy[:, 2].long()
             ok = (pb >= 0) & (pb < b) & (px >= 0) & (px < w) & (py >= 0) & (py < h)
-            key = torch.where(ok, (pb * h + py) * w + px, torch.full_like(pb, -1))
-            return self._csr(key, b * h * w)
-        return _cached(pxpy, "_pcs_px_csr", _cache_key(pxpy) + (b, h, w), make)
+            return self._csr(torch.where(ok, (pb * h + py) * w + px, torch.full_like(pb, -1)), b * h * w)
+        return _cached(pxpy, "_pcs_px_csr", (b, h, w), make)
 
     def denselize_fwd(self, feat, count_map, pxpy):
         """out[b, :, py, px] = mean of the feature rows of the points of pixel (b, py, px). C % 4 == 0: segmented over
@@ -1051,10 +1069,8 @@ class HipBackend:
             keys = torch.empty(4 * n, dtype=torch.int64, device=pxpy.device)
             wts = torch.empty(4 * n, dtype=torch.float32, device=pxpy.device)
             _check(self.lib.pcs_range_sample_corners(_ptr(pxpy), n, b, h, w, _ptr(keys), _ptr(wts), _stream()), "pcs_range_sample_corners")
-            vals, order = torch.sort(keys, stable=True)   # stable: a pixel's entries stay in (point, corner) order -> fixed summation order
-            rowptr = torch.searchsorted(vals, torch.arange(b * h * w + 1, device=pxpy.device, dtype=torch.int64))
-            return order.contiguous(), rowptr.contiguous(), wts
-        return _cached(pxpy, "_pcs_corner_csr", _cache_key(pxpy) + (b, h, w), make)
+            return self._csr(keys, b * h * w) + (wts,)   # a pixel's entries in (point, corner) order: the summation order
+        return _cached(pxpy, "_pcs_corner_csr", (b, h, w), make)
 
     def range_sample_bwd(self, gout, pxpy, b, h, w):
         """d img (B, C, H, W) of range_sample_fwd: atomic-free, every element written once."""
@@ -1237,18 +1253,42 @@ class HipBackend:
                                            _ptr(coords), _ptr(bbox), _stream()), "pcs_quantize_floor")
         keys = torch.empty(n, dtype=torch.int64, device=dev)
         _check(self.lib.pcs_quantize_keys(_ptr(coords), n, _ptr(bbox), _ptr(keys), _stream()), "pcs_quantize_keys")
-        skeys, perm = torch.sort(keys, stable=True)  # rocPRIM radix sort: equal keys keep row order
-        flags = torch.empty(n, dtype=torch.int32, device=dev)
-        _check(self.lib.pcs_quantize_flags(_ptr(skeys), n, _ptr(flags), _stream()), "pcs_quantize_flags")
+        return self._voxel_emit(keys, coords, want_index, want_inverse)
+
+    def _run_heads(self, skeys):
+        """flags (n,) int32: 1 where a sorted key differs from the one before it (pcs_quantize_flags)."""
+        flags = torch.empty(skeys.numel(), dtype=torch.int32, device=skeys.device)
+        _check(self.lib.pcs_quantize_flags(_ptr(skeys), skeys.numel(), _ptr(flags), _stream()), "pcs_quantize_flags")
+        return flags
+
+    def _run_emit(self, entry, flags, rank, perm, src, *outs):
+        """pcs_quantize_emit (src = coords) / pcs_unique_emit (src = sorted keys): one pass over the sorted positions that fills the
+        three `outs` (None: not wanted). With _run_heads the only kernel calls of the sorted-run pass."""
+        _check(getattr(self.lib, entry)(_ptr(flags), _ptr(rank), _ptr(perm), _ptr(src), flags.numel(), *[_ptr(o) for o in outs],
+                                        _stream()), entry)
+
+    def _sorted_runs(self, keys):
+        """keys (n,) int64 -> (skeys, perm, flags, rank, m): the stable sort (rocPRIM radix sort: equal keys keep row order, so the
+        smallest row of a run is its head), 1 at every run head, their inclusive scan = 1-based run of every sorted position, and
+        the number of runs -- the one host read, which sizes the callers' outputs. n == 0: empties and m = 0, nothing launched."""
+        if keys.numel() == 0:
+            e = torch.empty(0, dtype=torch.int64, device=keys.device)
+            return e, e, torch.empty(0, dtype=torch.int32, device=keys.device), e, 0
+        skeys, perm = torch.sort(keys, stable=True)
+        flags = self._run_heads(skeys)
         rank = torch.cumsum(flags, dim=0, dtype=torch.int64)
-        m = int(rank[-1].item()) if n else 0  # the one host sync: the number of voxels sizes the outputs
+        return skeys, perm, flags, rank, int(rank[-1].item())
+
+    def _voxel_emit(self, keys, coords, want_index, want_inverse):
+        """One voxel per run of `keys` -> (vox (m, 3) int32 = coords of the run's first row, index (m,) int64 | None = that row,
+        inverse (n,) int64 | None = run of every row)."""
+        _, perm, flags, rank, m = self._sorted_runs(keys)
+        n, dev = keys.numel(), keys.device
         vox = torch.empty((m, 3), dtype=torch.int32, device=dev)
         index = torch.empty(m, dtype=torch.int64, device=dev) if want_index else None
         inverse = torch.empty(n, dtype=torch.int64, device=dev) if want_inverse else None
-        _check(self.lib.pcs_quantize_emit(_ptr(flags), _ptr(rank), _ptr(perm), _ptr(coords), n, _ptr(vox),
-                                          _ptr(index), _ptr(inverse), _stream()), "pcs_quantize_emit")
+        self._run_emit("pcs_quantize_emit", flags, rank, perm, coords, vox, index, inverse)
         return vox, index, inverse
-
 
     def quantize_frame_keys(self, coords, frames):
         """int64 sort keys of a collated batch: frame on top of the batch's bounding box (one launch + two reductions)."""
@@ -1267,21 +1307,7 @@ class HipBackend:
         emit -> (vox (m, 4) int32 [x, y, z, frame], index (m,), inverse (n,))."""
         keys = _dev(keys, "keys", torch.int64)
         coords = _dev(coords, "coords", torch.int32)
-        n = keys.numel()
-        dev = keys.device
-        if n == 0:
-            return (torch.empty((0, 4), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
-                    torch.empty(0, dtype=torch.int64, device=dev))
-        skeys, perm = torch.sort(keys, stable=True)
-        flags = torch.empty(n, dtype=torch.int32, device=dev)
-        _check(self.lib.pcs_quantize_flags(_ptr(skeys), n, _ptr(flags), _stream()), "pcs_quantize_flags")
-        rank = torch.cumsum(flags, dim=0, dtype=torch.int64)
-        m = int(rank[-1].item())  # the one host read of the batch
-        vox = torch.empty((m, 3), dtype=torch.int32, device=dev)
-        index = torch.empty(m, dtype=torch.int64, device=dev)
-        inverse = torch.empty(n, dtype=torch.int64, device=dev)
-        _check(self.lib.pcs_quantize_emit(_ptr(flags), _ptr(rank), _ptr(perm), _ptr(coords), n, _ptr(vox), _ptr(index),
-                                          _ptr(inverse), _stream()), "pcs_quantize_emit")
+        vox, index, inverse = self._voxel_emit(keys, coords, True, True)
         return torch.cat([vox, frames[index].int()[:, None]], dim=1), index, inverse
 
     def unique_inverse_csr(self, keys):
@@ -1289,23 +1315,15 @@ class HipBackend:
         kept as the segmented-reduction CSR of `inverse` (cached on the returned tensor, so spvoxelize over it sorts
         nothing). One radix sort + three streaming passes for torch.unique + sphashquery + spcount."""
         keys = _dev(keys, "keys", torch.int64)
-        n = keys.numel()
-        dev = keys.device
-        if n == 0:
-            z = torch.empty(0, dtype=torch.int64, device=dev)
-            return z, z.clone(), torch.empty(0, dtype=torch.int32, device=dev)
-        skeys, perm = torch.sort(keys, stable=True)
-        flags = torch.empty(n, dtype=torch.int32, device=dev)
-        _check(self.lib.pcs_quantize_flags(_ptr(skeys), n, _ptr(flags), _stream()), "pcs_quantize_flags")
-        rank = torch.cumsum(flags, dim=0, dtype=torch.int64)
-        m = int(rank[-1].item())  # the one host sync (torch.unique has the same one): sizes the outputs
+        skeys, perm, flags, rank, m = self._sorted_runs(keys)
+        n, dev = keys.numel(), keys.device
         uniq = torch.empty(m, dtype=torch.int64, device=dev)
         inverse = torch.empty(n, dtype=torch.int64, device=dev)
         rowptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
-        _check(self.lib.pcs_unique_emit(_ptr(flags), _ptr(rank), _ptr(perm), _ptr(skeys), n, _ptr(uniq), _ptr(inverse),
-                                        _ptr(rowptr), _stream()), "pcs_unique_emit")
+        self._run_emit("pcs_unique_emit", flags, rank, perm, skeys, uniq, inverse, rowptr)
         counts = (rowptr[1:] - rowptr[:-1]).int()
-        inverse._pcs_vox_csr = (_cache_key(inverse) + (m, n), (perm, rowptr))  # what voxelize_fwd would sort for
+        if n:   # no keys: no kernel ran and rowptr was never written
+            _cache_seed(*_vox_csr_memo(inverse, m, n), (perm, rowptr))   # what voxelize_fwd would sort for
         return uniq, inverse, counts
 
     # -- cylinder front-end ------------------------------------------------------------------------------

@@ -100,7 +100,7 @@ def _frames_in_order(pxpy, b):
         return True
     if _PENDING:
         verify_pending()
-    return native._cached(pxpy, "_pcs_frames_sorted", native._cache_key(pxpy) + (b,), check)
+    return native._cached(pxpy, "_pcs_frames_sorted", (b,), check)
 
 
 def range_to_point(feature_map, pxpy, grid_sample_mode="bilinear", fallback=None):
@@ -135,7 +135,7 @@ def point_to_range(pf, pxpy, b, h, w):
         px = (p32[:, 1] + 1) / 2 * float(w - 1)
         py = (p32[:, 2] + 1) / 2 * float(h - 1)
         return torch.stack([p32[:, 0], px, py], dim=1).int().contiguous()
-    int_pxpy = native._cached(pxpy, "_pcs_int_pxpy_%dx%d" % (h, w), native._cache_key(pxpy), make)
+    int_pxpy = native._cached(pxpy, "_pcs_int_pxpy_%dx%d" % (h, w), (), make)
     return denselize(pf, map_count(int_pxpy, b, h, w), int_pxpy)
 
 

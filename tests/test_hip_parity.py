@@ -292,6 +292,22 @@ def test_index_csr(hip, n, m):
     assert np.array_equal(order[:rowptr[m]], ref[:rowptr[m]])
 
 
+@pytest.mark.parametrize("n", [0, 1, 63, 5000])
+def test_index_csr_halves_honour_one_contract(hip, n):
+    """HipBackend._csr: the library half (int32 keys) and the torch half (the same values as int64) put the same entries in the same
+    order into the same rows -- ties everywhere (7 rows), five entries without a row."""
+    m = 7
+    rng = np.random.default_rng(n)
+    idx = rng.integers(0, m, size=n)
+    if n > 10:
+        idx[rng.choice(n, size=5, replace=False)] = [-1, -3, m, m + 3, 2 ** 31 - 1]
+    (o32, r32), (o64, r64) = hip._csr(t(idx, torch.int32), m), hip._csr(t(idx, torch.int64), m)
+    assert r32.shape == r64.shape == (m + 1,) and o32.shape == o64.shape == (n,)
+    assert torch.equal(r32[1:] - r32[:-1], r64[1:] - r64[:-1])
+    assert int(r32[m] - r32[0]) == int(((idx >= 0) & (idx < m)).sum())
+    assert torch.equal(o32[int(r32[0]):int(r32[m])], o64[int(r64[0]):int(r64[m])])
+
+
 def test_prebuild_coords_are_the_lazy_ones(hip):
     """functional.prebuild_coords leaves in cmaps exactly what the strided convolutions would compute themselves (both
     spdownsample branches: k2 s2 fast, k3 s2 general), so a network runs bit-identically with its levels built up front."""
@@ -1073,6 +1089,33 @@ def test_unique_inverse_csr(hip):
     close(out, orc.voxelize_fwd(feats.cpu().numpy(), inv.cpu().numpy().astype(np.int32), counts.cpu().numpy()), 1e-5)
     e = hip.unique_inverse_csr(torch.zeros(0, dtype=torch.int64, device=DEV))
     assert e[0].numel() == 0 and e[1].numel() == 0 and e[2].numel() == 0
+
+
+def test_unique_inverse_csr_seeds_the_sort_of_spvoxelize(hip):
+    """The order unique_inverse_csr leaves on `inverse` is the one spvoxelize looks up: one memo hit, no miss (nothing sorted again),
+    and the oracle's output."""
+    from openpcseg_amd import functional as F
+    rng = np.random.default_rng(14)
+    uniq, inv, counts = hip.unique_inverse_csr(t(rng.integers(0, 300, size=1000)))
+    feats = t(rng.normal(size=(1000, 7)).astype(np.float32))
+    before = dict(native.CACHE_STATS)
+    out = F.spvoxelize(feats, inv, counts)
+    assert native.CACHE_STATS["hit"] == before["hit"] + 1 and native.CACHE_STATS["miss"] == before["miss"]
+    close(out, orc.voxelize_fwd(feats.cpu().numpy(), inv.cpu().numpy().astype(np.int32), counts.cpu().numpy()), 1e-5)
+
+
+def test_sorted_run_pass_on_empty_inputs(hip):
+    """quantize, quantize_sorted_keys and unique_inverse_csr without rows: shapes and dtypes of the results."""
+    def sig(ts):
+        return [None if x is None else (tuple(x.shape), x.dtype, x.is_cuda) for x in ts]
+    i64, i32 = ((0,), torch.int64, True), ((0,), torch.int32, True)
+    for pts in (torch.zeros((0, 3), device=DEV), torch.zeros((0, 3), dtype=torch.int32, device=DEV)):
+        assert sig(hip.quantize(pts, (0.5, 0.5, 0.5), True, True)) == [((0, 3), torch.int32, True), i64, i64]
+        assert sig(hip.quantize(pts, (0.5, 0.5, 0.5), False, False)) == [((0, 3), torch.int32, True), None, None]
+    e = torch.zeros(0, dtype=torch.int64, device=DEV)
+    got = hip.quantize_sorted_keys(e, torch.zeros((0, 3), dtype=torch.int32, device=DEV), e.clone())
+    assert sig(got) == [((0, 4), torch.int32, True), i64, i64]
+    assert sig(hip.unique_inverse_csr(e)) == [i64, i64, i32]
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -504,27 +504,44 @@ def test_step_budget_tools(tmp_path):
     assert "| copies / fills (runtime) | 20 | 0.08 |" in out and "| BatchNorm" in out and "| **total** | **93** |" in out
 
 
+class _TorchRunKernels:
+    """HipBackend's own sorted-run pass (sort, scan, host read, allocations, memo) with only its two kernel calls -- run heads and
+    emit, csrc/quantize.hip -- restated in torch. No quantize_frame_keys: hostdata then builds the key in torch as well."""
+    _sorted_runs, _voxel_emit = native.HipBackend._sorted_runs, native.HipBackend._voxel_emit
+    quantize_sorted_keys, unique_inverse_csr = native.HipBackend.quantize_sorted_keys, native.HipBackend.unique_inverse_csr
+
+    def _run_heads(self, skeys):
+        flags = torch.ones(skeys.numel(), dtype=torch.int32)
+        flags[1:] = (skeys[1:] != skeys[:-1]).int()
+        return flags
+
+    def _run_emit(self, entry, flags, rank, perm, src, *outs):
+        assert entry in ("pcs_quantize_emit", "pcs_unique_emit") and len(outs) == 3
+        if flags.numel() == 0:      # the entries return before they launch
+            return
+        head = flags.bool()
+        if entry == "pcs_quantize_emit":
+            vox, index, inverse = outs
+            vox.copy_(src[perm[head]])
+            if index is not None:
+                index.copy_(perm[head])
+        else:
+            uniq, inverse, rowptr = outs
+            uniq.copy_(src[head])
+            rowptr[:-1] = head.nonzero()[:, 0]
+            rowptr[-1] = flags.numel()
+        if inverse is not None:
+            inverse[perm] = rank - 1
+
+
 def test_sparse_quantize_frames_host_logic(monkeypatch):
     """hostdata.sparse_quantize_frames / workloads.synthetic.device_collate: the key construction -- one
     lexicographic key with the frame on top orders every frame like its own ravel hash -- against the per-frame NumPy path
-    (make_batch), with the backend's sort / flag / scan / emit pass restated in torch (the HIP pass itself: -m gpu,
-    test_device_input_pipeline_matches_the_host_dataloader). Equal-length, ragged and single-frame batches."""
-    import torch
-    from openpcseg_amd import native
+    (make_batch), through the backend's own sort / flag / scan / emit pass with its two kernel calls in torch (the HIP pass itself:
+    -m gpu, test_device_input_pipeline_matches_the_host_dataloader). Equal-length, ragged and single-frame batches."""
     from openpcseg_amd.workloads import synthetic as syn
 
-    class TorchPass:
-        def quantize_sorted_keys(self, keys, coords, frames):
-            skeys, perm = torch.sort(keys, stable=True)
-            flags = torch.ones_like(skeys)
-            flags[1:] = (skeys[1:] != skeys[:-1]).long()
-            rank = torch.cumsum(flags, 0)
-            index = perm[flags.bool()]
-            inverse = torch.empty_like(keys)
-            inverse[perm] = rank - 1
-            return torch.cat([coords[index], frames[index].int()[:, None]], 1), index, inverse
-
-    monkeypatch.setattr(native, "_BACKEND", TorchPass())
+    monkeypatch.setattr(native, "_BACKEND", _TorchRunKernels())
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))   # the entry point refuses host tensors: no CPU path
     for seeds, npts in (([3, 4, 5], 6000), ([7], 3000)):
         d = syn.device_collate(syn.make_raw_batch(seeds, n_points=npts))
@@ -540,6 +557,59 @@ def test_sparse_quantize_frames_host_logic(monkeypatch):
     frames = [syn.voxelize_scan(rag["points"][a:b].numpy(), seed=0) for a, b in ((0, 4000), (4000, 6500))]
     ref = sparse_collate_fn(frames)
     assert torch.equal(d["lidar"].C, ref["lidar"].C) and torch.equal(d["lidar"].F, ref["lidar"].F)
+
+
+# ---- grouping rows by key ("Grouping rows by key") -------------------------------------------------------------------------------
+@pytest.mark.parametrize("m", [1, 7])
+@pytest.mark.parametrize("n", [0, 1, 2, 257])
+def test_csr_torch_half_contract_on_host_tensors(n, m):
+    """native._sorted_csr, the torch half of HipBackend._csr: entries sorted by row, equal rows in ascending position, keys outside
+    [0, m) outside [rowptr[0], rowptr[m]), m + 1 row pointers -- against NumPy's stable argsort and bincount; int32 keys = int64 keys."""
+    rng = np.random.default_rng(100 * n + m)
+    keys = rng.integers(-1, m + 2, size=n)     # heavy ties; -1, m and m + 1 have no row
+    valid = (keys >= 0) & (keys < m)
+    got = {}
+    for dtype in (torch.int32, torch.int64):
+        order, rowptr = native._sorted_csr(torch.from_numpy(keys).to(dtype), m)
+        assert order.dtype == torch.int64 and order.shape == (n,) and rowptr.shape == (m + 1,)
+        got[dtype] = order, rowptr = order.numpy(), rowptr.numpy()
+        ref = np.argsort(keys, kind="stable")
+        assert np.array_equal(order[rowptr[0]:rowptr[m]], ref[valid[ref]])
+        assert np.array_equal(np.diff(rowptr), np.bincount(keys[valid], minlength=m))
+        assert rowptr[0] == (keys < 0).sum()
+    assert all(np.array_equal(a, b) for a, b in zip(got[torch.int32], got[torch.int64]))
+    be = object.__new__(native.HipBackend)      # host tensors never reach the library half
+    assert all(torch.equal(a, torch.from_numpy(b)) for a, b in zip(be._csr(torch.from_numpy(keys), m), got[torch.int64]))
+
+
+@pytest.mark.parametrize("n", [0, 1, 1000])
+def test_unique_inverse_csr_run_pass_and_seeded_memo(monkeypatch, n):
+    """HipBackend.unique_inverse_csr with only its two kernel calls in torch == torch.unique(return_inverse, return_counts); the memo
+    it leaves on `inverse` carries the epoch field and is found through the one function voxelize_fwd looks its order up with."""
+    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))   # the entry refuses host tensors
+    keys = torch.from_numpy(np.random.default_rng(n).integers(-40, 40, size=n))
+    uniq, inverse, counts = _TorchRunKernels().unique_inverse_csr(keys)
+    ru, rinv, rc = torch.unique(keys, return_inverse=True, return_counts=True)
+    assert torch.equal(uniq, ru) and torch.equal(inverse, rinv) and torch.equal(counts, rc.int())
+    assert (uniq.dtype, inverse.dtype, counts.dtype) == (torch.int64, torch.int64, torch.int32)
+    if n == 0:
+        assert not hasattr(inverse, "_pcs_vox_csr")
+        return
+    m = uniq.numel()
+    holder, slot, extra = native._vox_csr_memo(inverse, m, n)
+    key, (perm, rowptr), epoch = getattr(holder, slot)
+    assert holder is inverse and slot == "_pcs_vox_csr" and key == native._cache_key(inverse) + extra and key[-2:] == (m, n)
+    assert epoch == native.CACHE_STATS["epoch"]
+    order, ptr = native._sorted_csr(inverse, m)
+    assert torch.equal(perm, order) and torch.equal(rowptr, ptr)
+    before = dict(native.CACHE_STATS)
+    native.CACHE_STATS["epoch"] += 1                       # a later step: the hit counts as one across steps
+    try:
+        hit = native._cached(*native._vox_csr_memo(inverse, m, n), lambda: pytest.fail("the seeded memo was not found"))
+        assert hit[0] is perm and hit[1] is rowptr
+        assert [native.CACHE_STATS[k] - before[k] for k in ("hit", "miss", "cross")] == [1, 0, 1]
+    finally:
+        native.CACHE_STATS["epoch"] = before["epoch"]
 
 
 # ---- convolution routing (DESIGN.md, "Convolution routing") --------------------------------------------------------------------------------

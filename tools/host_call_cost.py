@@ -52,7 +52,12 @@ def main():
     rows.append(("lib.pcs_conv_emits_bn_partials", cost(lambda: lib.pcs_conv_emits_bn_partials(256, 256, 27, 144, 1), 5000)))
     rows.append(("lib.pcs_conv_uses_tile_order", cost(lambda: lib.pcs_conv_uses_tile_order(64, 64, 27, 0), 5000)))
     rows.append(("lib.pcs_conv_supports_epilogue", cost(lambda: lib.pcs_conv_supports_epilogue(64, 64, 27, 0), 5000)))
-    rows.append(("w.transpose(1,2).contiguous()", cost(lambda: w.transpose(1, 2).contiguous())))
+    keys = torch.randint(0, 50, (600,), generator=g).to(dev)   # grouping rows by key: the sorted-run pass (one host read) and a memo hit
+    _, inv, cnt = be.unique_inverse_csr(keys)
+    inv32, f16 = inv.int(), torch.randn(600, 16, device=dev)
+    rows.append(("be.unique_inverse_csr", cost(lambda: be.unique_inverse_csr(keys))))
+    rows.append(("be.voxelize_fwd (seeded order)", cost(lambda: be.voxelize_fwd(f16, inv32, cnt, cache_on=inv))))
+    rows.append(("w.transpose(1,2).contiguous()",cost(lambda: w.transpose(1, 2).contiguous())))
     sums = be.bn_stats(x)
     stat = be.bn_finalize(sums, float(n), 1e-5, 0.1, None, None)
     rows.append(("be.bn_stats", cost(lambda: be.bn_stats(x))))
