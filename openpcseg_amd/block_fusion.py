@@ -37,7 +37,7 @@ interchangeable both ways; `unfuse(model)` restores the original forwards):
     of the Linear, without the (N, 480) concatenation;
   * [forward] a model whose class is named MinkUNet and whose `forward` source is byte-identical to
     R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:385-434 runs, in training mode, the same graph with the classifier applied
-    on the voxels before the trilinear interpolation (`fused.devoxelized_linear`: interpolation and the Linear commute; the
+    on the voxels before the trilinear interpolation (`linear.devoxelized_linear`: interpolation and the Linear commute; the
     (N, 480) point-feature tensor and its gradient are never materialised) and ONE `loss.item()` instead of two. Same
     submodules, same criterion, same returned dictionaries; eval mode keeps the reference's forward.
 
@@ -47,7 +47,7 @@ interchangeable both ways; `unfuse(model)` restores the original forwards):
     per SPVCNN step) -- on the split-reduction wgrad kernel, BatchNorm + ReLU as the fused passes.
 
   * [dense layers] in a model that contains sparse convolutions, every remaining stock `nn.BatchNorm1d` / `nn.SyncBatchNorm` and
-    `nn.Linear` keeps its class name, parameters and state_dict keys but runs (N, C) device inputs of >= 4096 rows through the same
+    `nn.Linear` keeps its class name, parameters and state_dict keys but runs tall (N, C) device inputs (`linear.tall_rows`) through the same
     fused BatchNorm passes / the split-reduction weight gradient (Cylinder_TS normalises voxel features with plain BatchNorm1d after
     every convolution, R:pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:103-124: torch's channels-last BatchNorm kernels are
     30 of its 170 ms step); any other input takes the stock forward. Every plain `nn.CrossEntropyLoss` child -> the masked mean.
@@ -68,9 +68,12 @@ import sys
 import torch
 from torch import nn
 
+from . import functional as Fn
 from . import modules as spnn
 from . import native
 from .fused import bn_forward, bn_rows
+from .linear import NOT_SERVED, devoxelized_linear, parts_linear, row_linear, tall_rows
+from .linear import _POINT_MAPS, _PointLinear  # noqa: F401  (aliases: where they lived before linear.py; nothing here uses them)
 from .sparse import SparseTensor
 
 __all__ = ["fuse", "unfuse", "restore_glue", "install_auto_fuse", "uninstall_auto_fuse", "PendingBatchNorm"]
@@ -187,55 +190,13 @@ class _Plan:
         self.pending = last is not None and last[0] == "cbr" and last[1].transposed    # decoder up-conv: cat may follow
 
 
-_POINT_MAPS = {}   # identity maps (row count, device) of the point MLPs' weight gradients: one per step, shared by all of them
-
-
-class _PointLinear(torch.autograd.Function):
-    """y = x W^T + b over ~2 M point rows: forward and input gradient stay dense GEMMs (hipBLASLt through torch), the weight gradient
-    x^T dy -- (C_in, C_out), contracted over every point -- runs on the split-reduction wgrad kernel (as functional._PointwiseConv)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        from .functional import _amp_dtype
-        hd = _amp_dtype(x)
-        ctx.hd, ctx.has_bias, ctx.in_dtype = hd, bias is not None, x.dtype
-        if hd is None:
-            ctx.save_for_backward(x, weight)
-            return torch.nn.functional.linear(x.float(), weight.float(), bias.float() if bias is not None else None)
-        xh = x.to(hd)   # kept for the weight gradient: one conversion of the (N, C_in) rows instead of one per direction
-        ctx.save_for_backward(xh, weight)
-        return torch.nn.functional.linear(xh, weight.to(hd), bias.to(hd) if bias is not None else None)
-
-    @staticmethod
-    def backward(ctx, dy):
-        from .functional import _identity_map, _weight_grad
-        x, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        hd = ctx.hd
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = (dy.float().matmul(weight.float()) if hd is None else dy.to(hd).matmul(weight.to(hd))).to(ctx.in_dtype)
-        if ctx.needs_input_grad[1]:
-            if len(_POINT_MAPS) > 4:
-                _POINT_MAPS.clear()
-            km = _identity_map(x.shape[0], x.device, _POINT_MAPS)
-            # pad_a: e.g. Cylinder_TS's first point layer, Linear(9, 64): zero columns bring the rows to 16-byte granularity
-            gw = _weight_grad(native.backend(), x.contiguous(), dy, km, 0, hd, pad_a=True)[0].t().to(weight.dtype)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            gb = dy.float().sum(0).to(weight.dtype)
-        return gx, gw, gb
-
-
 def _dense_step(lin, bn, act, x):
     """Linear -> BatchNorm -> [ReLU] on a plain (N, C) tensor through the fused passes; the modules themselves where they do not apply."""
     if not (_rows_ok(x) and _quiet(lin) and _quiet(bn) and (act is None or _quiet(act))):
         h = bn(lin(x))
         return act(h) if act is not None else h
-    if lin.out_features % 4 == 0:
-        h = _PointLinear.apply(x, lin.weight, lin.bias)
-    else:
-        h = lin(x)
-    return _dense_bn_apply(bn, h, act is not None)
+    h = row_linear(x, lin.weight, lin.bias)
+    return _dense_bn_apply(bn, lin(x) if h is NOT_SERVED else h, act is not None)
 
 
 def _dense_bn_apply(bn, h, relu):
@@ -243,8 +204,7 @@ def _dense_bn_apply(bn, h, relu):
 
 
 def _rows_ok(x):
-    return (isinstance(x, torch.Tensor) and x.dim() == 2 and x.is_cuda and x.shape[0] >= 4096 and
-            x.dtype in (torch.float32, torch.bfloat16, torch.float16) and hasattr(native.backend(), "bn_apply"))
+    return tall_rows(x) and hasattr(native.backend(), "bn_apply")
 
 
 def _dense_bn_forward(self, x):
@@ -256,9 +216,8 @@ def _dense_bn_forward(self, x):
 
 def _dense_linear_forward(self, x):
     """forward of a stock nn.Linear re-classed by fuse(): tall (N, C_in) device inputs get the split-reduction weight gradient."""
-    if not (_rows_ok(x) and _quiet(self) and self.out_features % 4 == 0):
-        return self.__dict__["_pcs_orig_class"].forward(self, x)
-    return _PointLinear.apply(x, self.weight, self.bias)
+    y = row_linear(x, self.weight, self.bias) if _quiet(self) and hasattr(native.backend(), "bn_apply") else NOT_SERVED
+    return self.__dict__["_pcs_orig_class"].forward(self, x) if y is NOT_SERVED else y
 
 
 def _skip_through(conv, x):
@@ -532,8 +491,7 @@ def _prebuild_encoder(model, x0):
             steps.append((tuple(conv.stride), tuple(conv.kernel_size)))
         model.__dict__["_pcs_enc_steps"] = steps
     if steps and os.environ.get("PCS_PREBUILD_LEVELS", "1") != "0":
-        from . import functional as F
-        F.prebuild_coords(x0, steps)
+        Fn.prebuild_coords(x0, steps)
     return x0
 
 
@@ -541,7 +499,6 @@ def _minkunet_forward(self, batch_dict, return_logit=False, return_tta=False):
     """Training-mode forward of the reference's MinkUNet (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:385-434) with the
     classifier commuted in front of the three trilinear interpolations; everything else line by line as the reference."""
     from . import sparse as ts
-    from .fused import devoxelized_linear
     from .workloads.pointvoxel import initial_voxelize, point_maps, voxel_to_point
     lin = self.classifier[0] if isinstance(self.classifier, nn.Sequential) and len(self.classifier) == 1 else None
     x = batch_dict["lidar"]
@@ -590,10 +547,9 @@ def _minkunet_forward(self, batch_dict, return_logit=False, return_tta=False):
 def _spvcnn_forward(self, batch_dict, return_logit=False, return_tta=False):
     """Training-mode forward of the reference's SPVCNN (R:pcseg/model/segmentor/fusion/spvcnn/spvcnn.py:399-456), line by line, with
     ONE change: `classifier(torch.cat([z1.F, z2.F, z3.F], 1))` is evaluated as the sum of the three column blocks of the Linear
-    (`fused._SkinnyLinearParts`): the (N, 480) concatenation of 1.9 M point rows -- 3.7 GB written and read back, and sliced again in
+    (`linear.parts_linear`): the (N, 480) concatenation of 1.9 M point rows -- 3.7 GB written and read back, and sliced again in
     backward -- is never built. Eval mode, other `multi_scale` settings and hooked classifiers take the reference's forward."""
     from . import sparse as ts
-    from .fused import _SkinnyLinearParts
     from .workloads.pointvoxel import initial_voxelize, point_to_voxel, voxel_to_point
     lin = self.classifier[0] if isinstance(self.classifier, nn.Sequential) and len(self.classifier) == 1 else None
     x = batch_dict["lidar"]
@@ -634,15 +590,8 @@ def _spvcnn_forward(self, batch_dict, return_logit=False, return_tta=False):
     z3 = voxel_to_point(y4, z2)
     z3.F = z3.F + self.point_transforms[2](z2.F)
     parts = [z1.F, z2.F, z3.F]
-    if (all(p.dim() == 2 and p.shape[1] % 4 == 0 and p.dtype in (torch.float32, torch.bfloat16, torch.float16) for p in parts) and
-            parts[0].shape[0] >= 4096 and sum(p.shape[1] for p in parts) == lin.in_features):
-        hd = next((p.dtype for p in parts if p.dtype != torch.float32), None)
-        if hd is None and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") in (torch.bfloat16, torch.float16):
-            hd = torch.get_autocast_dtype("cuda")
-        if len(_POINT_MAPS) > 4:
-            _POINT_MAPS.clear()
-        out = _SkinnyLinearParts.apply(lin.weight, lin.bias, _POINT_MAPS, hd, *parts)
-    else:
+    out = parts_linear(lin.weight, lin.bias, parts)
+    if out is NOT_SERVED:
         out = self.classifier(torch.cat(parts, dim=1))
     target = batch_dict["targets"].F.long().cuda(non_blocking=True)
     coords_xyz = batch_dict["lidar"].C[:, :3].float()
@@ -691,7 +640,6 @@ _CYL_FORWARD_SHA1 = {"ResContextBlock": "ca01095d526ca22e88e3934d5d3c584bcc79779
 
 def _cab(conv, act, bn, x, residual=None, want_skip=False):
     """conv -> LeakyReLU -> BatchNorm (+ residual) on a SparseTensor; -> (result, x routed through conv when want_skip)."""
-    from . import functional as Fn
     ok = (type(conv) is spnn.Conv3d and type(act) is nn.LeakyReLU and _bn_like(bn) and _quiet(conv) and _quiet(act) and _quiet(bn) and
           isinstance(x, SparseTensor) and _backend_fuses(x.feats) and conv.bias is None and conv.kernel.dim() == 3 and
           Fn.conv_act_fusable(x.feats, conv.kernel) and os.environ.get("PCS_CYL_FUSED", "1") != "0")

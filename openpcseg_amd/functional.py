@@ -563,8 +563,12 @@ def conv_act_fusable(feats, weight):
     return fam == "half" or (fam == "fp32" and be.conv_supports_addend(cin, cout, k, 0))
 
 
-def _identity_map(n, device, cache):
-    """K = 1 map (i, i): lets the split-reduction wgrad kernel compute x^T @ dy of a 1x1x1 convolution."""
+def _identity_map(n, device, cache, limit=None):
+    """K = 1 map (i, i): lets the split-reduction wgrad kernel compute x^T @ dy of a 1x1x1 convolution. cache: the caller's dict;
+    limit: for a dict that outlives the step -- once it holds more entries than that (a run with many distinct row counts), it is
+    started afresh. The one place that evicts."""
+    if limit is not None and len(cache) > limit:
+        cache.clear()
     key = ("_pcs_identity", n, str(device))
     km = cache.get(key)
     if km is None:
@@ -574,6 +578,18 @@ def _identity_map(n, device, cache):
                               native._h2d([n], torch.int64, device), n, n)
         cache[key] = km
     return km
+
+
+def _rows_weight_grad(x, dy, hd, cache, limit=None, pad_in=False, pad_out=False):
+    """x^T dy of a Linear over (N, cin) rows -> (cin, cout) in fp32, on the split-reduction wgrad kernel over the identity map (kept in
+    `cache`, `_identity_map`); hd: the half dtype the layer computes in, or None. Its two callers pad differently, on purpose:
+      _PointwiseConv (conv3d's 1x1x1 node)   both widths, device tensors only, and only layers of >= 32 padded input channels: the
+                                             cr 1.6 widths (153, 409, 613 ...) reach the MFMA kernels (the generic kernel ran them at
+                                             16-19 TFLOP/s), thin layers stay on the kernel that serves them; saves x as it arrives;
+      linear._PointLinear                    the input width always (Linear(9, 64): 9 -> 12), the output width never -- its callers
+                                             ask for cout % 4 == 0 first; saves x in the dtype it computes in."""
+    km = _identity_map(x.shape[0], x.device, cache, limit)
+    return _weight_grad(_be(), x.contiguous(), dy, km, 0, hd, pad_a=pad_in, pad_b=pad_out)[0]
 
 
 class _PointwiseConv(Function):
@@ -602,11 +618,8 @@ class _PointwiseConv(Function):
             else:
                 gin = grad_output.to(hd).matmul(weight.to(hd).t())
         if ctx.needs_input_grad[1]:
-            km = _identity_map(feats.shape[0], feats.device, ctx.cache)
-            # widths that are not 16-byte granular (cr 1.6: 153, 409, 613 ...): zero columns bring the operands onto the MFMA
-            # weight-gradient kernels (the generic kernel ran these 1x1x1 layers at 16-19 TFLOP/s)
             pad = feats.is_cuda and feats.shape[1] + (-feats.shape[1]) % 4 >= 32
-            gw = _weight_grad(_be(), feats.contiguous(), grad_output, km, 0, hd, pad_a=pad, pad_b=pad)[0].to(weight.dtype)
+            gw = _rows_weight_grad(feats, grad_output, hd, ctx.cache, pad_in=pad, pad_out=pad).to(weight.dtype)
         return gin, gw, None
 
 
@@ -737,7 +750,7 @@ def conv3d_inference(input, weight, bias, kernel_size, stride=1, dilation=1, tra
     weight: fp32 (K, cin, cout) or (cin, cout), typically a convolution's kernel with the BatchNorm that follows folded in; bias
     fp32 (cout) or None; addend: a tensor / SparseTensor on the output coordinates (the residual), handed over in dst's dtype.
     The kernel is picked by the rules of _SparseConv.forward: the half kernel under autocast where conv_h_applies, else fp32
-    (rounded to the autocast dtype); a 1x1x1 convolution runs on the gather-GEMM over the identity map like fused._SkinnyLinear.
+    (rounded to the autocast dtype); a 1x1x1 convolution runs on the gather-GEMM over the identity map like linear._SkinnyLinear.
     Where the kernel takes no write-back extras (generic shapes, the bf16x3 policy, zero-padded odd widths, a backend without
     `conv_epilogue_relu`), the kernel adds the bias and torch adds / clamps in place: still no BatchNorm launch.
     act_slope: LeakyReLU instead of ReLU (relu wins). post_scale / post_shift: fp32 (cout); with them the order becomes

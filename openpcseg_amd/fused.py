@@ -10,8 +10,12 @@ import torch.distributed as dist
 from torch import nn
 from torch.autograd import Function
 
+from . import functional as F_
 from . import native
 from .sparse import SparseTensor
+# Linear over tall rows lives in linear.py; these names stay importable from here, where they lived before (callers' imports, checkpoints'
+# tooling): aliases, nothing is defined here
+from .linear import FusedLinear, _SkinnyLinear, _SkinnyLinearParts, devoxelized_linear  # noqa: F401,E402
 
 
 def _world():
@@ -254,168 +258,6 @@ class FusedBatchNorm(nn.Module):
     forward = bn_forward
 
 
-class _SkinnyLinear(Function):
-    """y = x @ W^T + b for a tall-skinny problem (1.2 M rows, 480 -> 20 classes): hipBLASLt picks 32x32x256 /
-    256x256x16 macro-tiles for it (forward 1.05 ms, dgrad 1.82 ms at 12-21 TFLOP/s). The fused conv kernels treat it
-    as a K = 1 convolution over the identity map: forward + dgrad on the gather-GEMM, dW on the split-reduction wgrad."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, cache, hd=None):
-        """hd: the half dtype under autocast (the 16-bit MFMA kernel serves the forward when its shape rules allow)."""
-        from . import functional as F_
-        be = native.backend()
-        km = F_._identity_map(x.shape[0], x.device, cache)
-        w1 = weight.detach().float().t().contiguous().unsqueeze(0)  # (1, in, out)
-        fam = F_._conv_family(be, hd, x.is_cuda, w1.shape[1], w1.shape[2], 1, x3=False)
-        y, x, _ = F_._run_conv(be, fam, x, w1, km, hd, F_._per_call, bias=bias.float() if bias is not None else None)
-        ctx.save_for_backward(x, weight)
-        ctx.km, ctx.hd, ctx.in_dtype = km, hd, x.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        from .functional import _weight_grad
-        be = native.backend()
-        x, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = be.conv_gather_gemm(dy.float(), weight.detach().float().contiguous().unsqueeze(0), ctx.km)
-        if ctx.needs_input_grad[1]:
-            dw = _weight_grad(be, x, dy, ctx.km, 0, x.dtype)[0].t().to(weight.dtype)
-        if ctx.needs_input_grad[2]:
-            db = dy.float().sum(0)
-        return dx, dw, db, None, None
-
-
-class _SkinnyLinearParts(Function):
-    """y = cat(parts, 1) @ W^T + b without the concatenation: one gather-GEMM per column block of W, summed -- the
-    classifier over [z1 | z2 | z3] (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:415-417) never materialises the
-    (N, 480) tensor (2.8 GB written and read back per step at 1.4 M points) nor, in backward, the contiguous copies of
-    its sliced gradient: every d(part) is written once, by its own launch."""
-
-    @staticmethod
-    def forward(ctx, weight, bias, cache, hd, *parts):
-        from . import functional as F_
-        be = native.backend()
-        km = F_._identity_map(parts[0].shape[0], parts[0].device, cache)
-        wt = weight.detach().float().t().contiguous()  # (in, out)
-        saved, y, col = [], None, 0
-        for i, x in enumerate(parts):
-            cin = x.shape[1]
-            w1 = wt[col:col + cin].unsqueeze(0)  # (1, cin, out): a contiguous row block
-            b = bias.float() if (bias is not None and i == 0) else None
-            # a part that ARRIVES in half runs on the 16-bit kernel; an fp32 part stays fp32 even under autocast: the
-            # pass is HBM-bound, and casting first (read 4 + write 2 + read 2 bytes per element) costs twice the fp32 read
-            hx = x.dtype if x.dtype != torch.float32 else None
-            fam = F_._conv_family(be, hx, x.is_cuda, cin, w1.shape[2], 1, x3=False)
-            t, x, _ = F_._run_conv(be, fam, x, w1, km, hx, F_._per_call, bias=b, rounded=False)   # the sum stays fp32
-            y = t.float() if y is None else y.add_(t.float())
-            saved.append(x)
-            col += cin
-        ctx.save_for_backward(weight, *saved)
-        ctx.km, ctx.hd, ctx.has_bias = km, hd, bias is not None
-        return y.to(hd) if hd is not None else y
-
-    @staticmethod
-    def backward(ctx, dy):
-        from .functional import _weight_grad
-        be = native.backend()
-        weight, parts = ctx.saved_tensors[0], ctx.saved_tensors[1:]
-        dy32 = dy.contiguous().float()
-        w = weight.detach().float()  # (out, in)
-        grads, dws, col = [], [], 0
-        for i, x in enumerate(parts):
-            cin = x.shape[1]
-            dx = None
-            if ctx.needs_input_grad[4 + i]:
-                dx = be.conv_gather_gemm(dy32, w[:, col:col + cin].contiguous().unsqueeze(0), ctx.km)
-            grads.append(dx)
-            if ctx.needs_input_grad[0]:
-                dws.append(_weight_grad(be, x, dy32, ctx.km, 0, x.dtype)[0].t())
-            col += cin
-        dw = torch.cat(dws, dim=1).to(weight.dtype) if ctx.needs_input_grad[0] else None
-        db = dy32.sum(0) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
-        return (dw, db, None, None) + tuple(grads)
-
-
-def devoxelized_linear(weight, col, xf, idx, wts, cache):
-    """devoxelize(xf) @ W_i^T computed as devoxelize(xf @ W_i^T), W_i = weight[:, col : col + C_i] of an nn.Linear weight:
-    trilinear devoxelisation is linear over the voxel features (fixed per-point weights), so it commutes with the classifier --
-    the class scores are formed on the VOXELS (36 k / 329 k / 1.16 M rows of 256 / 128 / 96 channels -> num_class) and only
-    num_class channels per point are interpolated, instead of interpolating 480 channels per point and contracting them there
-    (2.7 GB of point features written, read by the classifier, and the same again as gradients in backward). Same function; the
-    fp32 rounding order differs. xf (V, C_i) voxel features, idx / wts (N, 8) the points' corner map. The bias is added on the
-    points by the caller: the weights of a point with missing corners do not sum to one. cache: dict that keeps the identity map
-    of this row count (pass the tensor's per-forward `kmaps`: built once per level and step, freed with the step)."""
-    from . import functional as F_
-    cin, cout = xf.shape[1], weight.shape[0]
-    w = weight[:, col:col + cin]
-    ok = (xf.is_cuda and xf.dim() == 2 and xf.dtype in (torch.float32, torch.bfloat16, torch.float16) and
-          xf.shape[0] >= 4096 and cin % 4 == 0 and cout % 4 == 0)
-    if ok:
-        v = _SkinnyLinear.apply(xf, w, None, cache, xf.dtype if xf.dtype != torch.float32 else None)
-    else:
-        v = torch.nn.functional.linear(xf.float(), w.float())
-    return F_.spdevoxelize(v.float(), idx, wts)
-
-
-class FusedLinear(nn.Linear):
-    """nn.Linear (same parameters / state_dict keys) whose fp32 device path runs on the fused conv kernels when the
-    row count dwarfs the feature sizes and the shapes are 16-byte granular; anything else is nn.Linear."""
-
-    def __init__(self, in_features, out_features, bias=True):
-        super().__init__(in_features, out_features, bias)
-        self._maps = {}  # identity maps by row count (a handful of distinct batch sizes per run)
-
-    def forward(self, x):
-        ok = (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16, torch.float16) and x.dim() == 2 and
-              x.shape[0] >= 4096 and self.in_features % 4 == 0 and self.out_features % 4 == 0)
-        if not ok:
-            return super().forward(x)
-        if len(self._maps) > 8:
-            self._maps.clear()
-        hd = None
-        if x.dtype != torch.float32:
-            hd = x.dtype
-        elif torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") in (torch.bfloat16, torch.float16):
-            hd = torch.get_autocast_dtype("cuda")
-        return _SkinnyLinear.apply(x, self.weight, self.bias, self._maps, hd)
-
-    def devoxelized_part(self, col, xf, idx, wts, cache=None):
-        """One term of forward(cat([devoxelize(x_i) for i], 1)) = sum_i devoxelize(x_i @ W_i^T) + b, W_i = the column
-        block [col, col + C_i) of the weight (`devoxelized_linear`). cache: a per-forward dict for the identity map of this row
-        count (the tensor's `kmaps`); default: the module's own small cache."""
-        if cache is None:
-            if len(self._maps) > 8:
-                self._maps.clear()
-            cache = self._maps
-        return devoxelized_linear(self.weight, col, xf, idx, wts, cache)
-
-    def sum_devoxelized(self, terms):
-        y = terms[0]
-        for t in terms[1:]:
-            y = y + t
-        return y + self.bias if self.bias is not None else y
-
-    def forward_parts(self, parts):
-        """forward(torch.cat(parts, 1)) without building the concatenation (column blocks of the weight)."""
-        parts = list(parts)
-        ok = (all(x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16, torch.float16) and
-                  x.shape[1] % 4 == 0 for x in parts) and parts[0].shape[0] >= 4096 and self.out_features % 4 == 0 and
-              sum(x.shape[1] for x in parts) == self.in_features)
-        if not ok:
-            return self.forward(torch.cat(parts, dim=1))
-        if len(self._maps) > 8:
-            self._maps.clear()
-        hd = None
-        if any(x.dtype != torch.float32 for x in parts):
-            hd = next(x.dtype for x in parts if x.dtype != torch.float32)
-        elif torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") in (torch.bfloat16, torch.float16):
-            hd = torch.get_autocast_dtype("cuda")
-        return _SkinnyLinearParts.apply(self.weight, self.bias, self._maps, hd, *parts)
-
-
 # ---- the point-branch merges: SPVCNN's (voxel + point) and RPVNet's (voxel + range + point) ---------------------------------
 _ROW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -538,7 +380,6 @@ def _merge_kernel_serves(be, lin_out, vox_feats, idx8, w8, feature_map=None, pxp
 
 def _merge(bn, lin_out, vox_feats, idx8, w8, feature_map=None, pxpy=None, grid_sample_mode="bilinear"):
     """`point_merge` (feature_map None) and `range_point_merge`."""
-    from . import functional as F_
     be = native.backend()
     fused = _merge_kernel_serves(be, lin_out, vox_feats, idx8, w8, feature_map, pxpy, grid_sample_mode)
     if fused and lin_out.shape[1] % 32 == 0:   # BatchNorm apply, ReLU and mask inside the kernel

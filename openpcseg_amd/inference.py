@@ -33,7 +33,8 @@ from torch import nn
 from . import functional as F
 from . import modules as spnn
 from . import native
-from .fused import FusedBatchNorm, FusedLinear
+from .fused import FusedBatchNorm
+from .linear import FusedLinear, devoxelized_linear
 from .sparse import SparseTensor
 
 __all__ = ["freeze", "unfreeze", "FoldedConv", "PostAffineConv", "FoldedDense", "SegEvaluator", "point_predict"]
@@ -200,35 +201,24 @@ class FoldedDense:
 
 
 class FoldedLinear:
-    """The classifier's column blocks (FusedLinear.devoxelized_part) as (1, cin, cout) gather-GEMM weights, kept -- with their
-    fragment-ordered half copies -- per weight version instead of being transposed and prepared on every forward. Same kernels
-    on the same values as fused._SkinnyLinear.forward: the logits are bit-identical to the unfrozen classifier's."""
+    """The classifier's column blocks (FusedLinear.devoxelized_part) with their (1, cin, cout) gather-GEMM weights and fragment-ordered
+    half copies kept per weight version instead of being transposed and prepared on every forward (`linear.devoxelized_linear`,
+    memo): the logits are bit-identical to the unfrozen classifier's."""
 
     def __init__(self, lin):
         self.lin, self._stamp, self.parts = lin, None, {}
 
     def devoxelized_part(self, col, xf, idx, wts, cache=None):
-        lin = self.lin
-        cin, cout = xf.shape[1], lin.out_features
-        ok = (cache is not None and xf.is_cuda and xf.dim() == 2 and xf.dtype in (torch.float32, torch.bfloat16, torch.float16) and
-              xf.shape[0] >= 4096 and cin % 4 == 0 and cout % 4 == 0)
-        if not ok:
-            return lin.devoxelized_part(col, xf, idx, wts, cache=cache)
-        w = lin.weight
+        w = self.lin.weight
+        if cache is None:   # no per-forward dict for the identity map: the module's own path
+            return self.lin.devoxelized_part(col, xf, idx, wts)
         try:
             stamp = (w._version, w.data_ptr(), w.device, w.dtype)
         except RuntimeError:
             stamp = None
         if stamp is None or stamp != self._stamp:
             self.parts, self._stamp = {}, stamp
-        part = self.parts.setdefault((col, cin), {})
-        w1 = F._memo(part, "w", lambda: w.detach()[:, col:col + cin].float().t().contiguous().unsqueeze(0))
-        be = native.backend()
-        km = F._identity_map(xf.shape[0], xf.device, cache)
-        hd = xf.dtype if xf.dtype != torch.float32 else None
-        fam = F._conv_family(be, hd, True, cin, cout, 1, x3=False)
-        v = F._run_conv(be, fam, xf, w1, km, hd, F._kept_in(part))[0]
-        return F.spdevoxelize(v.float(), idx, wts)
+        return devoxelized_linear(w, col, xf, idx, wts, cache, memo=self.parts.setdefault((col, xf.shape[1]), {}))
 
 
 def active(module):

@@ -26,8 +26,8 @@ from torch import nn
 from .. import functional as F
 from .. import fused, inference, native
 from .. import modules as spnn
-from ..block_fusion import _PointLinear
 from ..fused import FusedBatchNorm
+from ..linear import NOT_SERVED, row_linear
 from ..scatter import scatter_max
 from ..sparse import SparseTensor
 from .losses import SegLoss
@@ -39,9 +39,8 @@ SKIP_FUSED = os.environ.get("PCS_SKIP_FUSED", "1") != "0"  # a block input's two
 
 def _linear(lin, x):
     """nn.Linear over point / voxel rows; on the device the weight gradient runs on the split-reduction kernel."""
-    if x.is_cuda and lin.out_features % 4 == 0 and x.shape[0] >= 4096:
-        return _PointLinear.apply(x, lin.weight, lin.bias)
-    return lin(x)
+    y = row_linear(x, lin.weight, lin.bias)
+    return lin(x) if y is NOT_SERVED else y
 
 
 def _dense_bn(bn, h, relu=False):

@@ -15,7 +15,8 @@ from torch import nn
 from .. import functional as F
 from .. import inference
 from .. import modules as spnn
-from ..fused import FusedBatchNorm, FusedLinear
+from ..fused import FusedBatchNorm
+from ..linear import FusedLinear
 from ..sparse import PointTensor, cat, fapply
 from .losses import SegLoss
 from .pointvoxel import initial_voxelize, point_maps, voxel_to_point

@@ -21,8 +21,7 @@ from torch import nn
 
 from .. import functional as F
 from .. import fused, inference, rangelib
-from ..block_fusion import _PointLinear
-from ..fused import FusedLinear
+from ..linear import NOT_SERVED, FusedLinear, row_linear
 from ..sparse import PointTensor
 from .minkunet import MK34_LAYERS, PLANES, PREBUILD, MinkUNet, _norm
 from .pointvoxel import initial_voxelize, point_maps, point_to_voxel
@@ -132,9 +131,8 @@ class RPVNet(MinkUNet):
         """Hop i: the point tensor after `voxel_to_point(x, z)` and `.F = .F + range_to_point(r, pxpy) + point_transforms[i](z.F)`."""
         lin, bn = self.point_transforms[i][0], self.point_transforms[i][1]
         idx8, w8 = point_maps(x, z)
-        if z.F.is_cuda and lin.out_features % 4 == 0:
-            h = _PointLinear.apply(z.F, lin.weight, lin.bias)   # weight gradient on the split-reduction kernel
-        else:
+        h = row_linear(z.F, lin.weight, lin.bias, min_rows=0)   # weight gradient on the split-reduction kernel, at any row count
+        if h is NOT_SERVED:
             h = lin(z.F)
         feats = fused.range_point_merge(bn, h, x.F, idx8, w8, r, pxpy, self.grid_sample_mode)
         out = PointTensor(feats, z.C, idx_query=z.idx_query, weights=z.weights)

@@ -16,8 +16,7 @@ from torch import nn
 
 from .. import functional as F
 from .. import fused
-from ..block_fusion import _PointLinear
-from ..fused import FusedLinear
+from ..linear import NOT_SERVED, FusedLinear, row_linear
 from ..sparse import PointTensor
 from .minkunet import MK18_LAYERS, PLANES, PREBUILD, MinkUNet, _norm
 from .pointvoxel import initial_voxelize, point_maps, point_to_voxel, voxel_to_point
@@ -42,9 +41,8 @@ class SPVCNN(MinkUNet):
         """Hop i: the point tensor after `voxel_to_point(x, z)` and `.F += point_transforms[i](z.F)`."""
         lin, bn = self.point_transforms[i][0], self.point_transforms[i][1]
         idx8, w8 = point_maps(x, z)
-        if z.F.is_cuda and lin.out_features % 4 == 0:
-            h = _PointLinear.apply(z.F, lin.weight, lin.bias)   # weight gradient on the split-reduction kernel
-        else:
+        h = row_linear(z.F, lin.weight, lin.bias, min_rows=0)   # weight gradient on the split-reduction kernel, at any row count
+        if h is NOT_SERVED:
             h = lin(z.F)
         out = PointTensor(fused.point_merge(bn, h, x.F, idx8, w8), z.C, idx_query=z.idx_query, weights=z.weights)
         out.additional_features = z.additional_features

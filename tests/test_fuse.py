@@ -451,7 +451,7 @@ def test_dense_linear_and_batchnorm_match_torch_on_hip(hip, cin, cout):
     per-convolution BatchNorm1d, the point_transforms of SPVCNN / RPVNet) against the stock modules: outputs, input / weight / bias
     gradients, running statistics; and that the fused path is really taken."""
     import openpcseg_amd
-    from openpcseg_amd import block_fusion as fz
+    from openpcseg_amd import linear as fz
     from openpcseg_amd import modules as spnn
 
     class Net(torch.nn.Module):
@@ -507,7 +507,7 @@ def test_point_linear_weight_gradient_off_the_half_entry_under_autocast(hip):
     takes the fp32 entry on the bf16-rounded operands (the half entry refuses such a width). Against x^T dy in float64 of the same
     rounded operands, at the fp32 weight-gradient bound of the suite (2e-5 of the maximum: fp32 summation order over 257 products
     of exact bf16 x bf16 terms); bit-identical on a second call."""
-    from openpcseg_amd import block_fusion as fz
+    from openpcseg_amd import linear as fz
     g = torch.Generator().manual_seed(11)
     x = (torch.randn(257, 8, generator=g) * 2 + 0.5).cuda()
     coef = torch.randn(257, 6, generator=g).cuda()

@@ -828,7 +828,7 @@ def test_corner_map_equals_the_op_sequence(hip, stride):
 
 def test_fused_linear_matches_torch(hip):
     """The classifier (480 -> 20 over ~1e5..1e6 rows) on the fused conv kernels == nn.Linear, values and gradients."""
-    from openpcseg_amd.fused import FusedLinear
+    from openpcseg_amd.linear import FusedLinear
     torch.manual_seed(3)
     n = 50021
     lin = FusedLinear(480, 20).to(DEV)
@@ -852,7 +852,7 @@ def test_fused_linear_matches_torch(hip):
 def test_fused_linear_over_column_blocks(hip, amp):
     """forward_parts([z1, z2, z3]) == Linear(cat([z1, z2, z3], 1)): values, the three input gradients, dW, db -- the
     classifier of the workload without the (N, 480) concatenation."""
-    from openpcseg_amd.fused import FusedLinear
+    from openpcseg_amd.linear import FusedLinear
     torch.manual_seed(4)
     n = 40013
     lin = FusedLinear(480, 20).to(DEV)
@@ -876,6 +876,52 @@ def test_fused_linear_over_column_blocks(hip, amp):
     assert (lin.bias.grad - ref.bias.grad).abs().max() <= tol * ref.bias.grad.abs().max()
     few = [torch.randn(64, c, device=DEV) for c in (256, 128, 96)]  # few rows: the plain path over the concatenation
     assert torch.allclose(lin.forward_parts(few), ref(torch.cat(few, 1)), atol=1e-5)
+
+
+# (site, part widths, out width, rows, the Function that must take it or None for the stock path). 4096: the first row count of the
+# tall path, 4095: the last of the stock path; min_rows=0 is the workloads' `_merge` call, where 8 -> 6 is off the Function on account
+# of its output width (as on the parent: `lin(z.F)`) and 9 -> 64 is on it at any row count, its input width padded.
+_ROW_FLOOR = [("row_linear", (9,), 64, 4096, "_PointLinear"), ("row_linear", (9,), 64, 4095, None),
+              ("row_linear min_rows=0", (8,), 6, 257, None), ("row_linear min_rows=0", (9,), 64, 257, "_PointLinear"),
+              ("forward", (32,), 20, 4096, "_SkinnyLinear"), ("forward", (32,), 20, 4095, None),
+              ("forward_parts", (16, 8, 8), 20, 4096, "_SkinnyLinearParts"), ("forward_parts", (16, 8, 8), 20, 4095, None)]
+
+
+@pytest.mark.parametrize("site,widths,cout,n,function", _ROW_FLOOR, ids=["%s %s->%d n=%d" % (c[0], "+".join(map(str, c[1])), c[2], c[3]) for c in _ROW_FLOOR])
+def test_tall_linear_row_floor(hip, monkeypatch, site, widths, cout, n, function):
+    """The row floor of linear.tall_rows from both sides, at every kind of site: output, input gradients, weight gradient and bias
+    gradient against nn.Linear in float64 on the same inputs, at the suite's fp32 bound for these layers (2e-5 of the reference's
+    maximum), and which Function took the call."""
+    from openpcseg_amd import linear
+    g = torch.Generator().manual_seed(n + cout)
+    cin = sum(widths)
+    lin = (torch.nn.Linear if site.startswith("row_linear") else linear.FusedLinear)(cin, cout).to(DEV)
+    ref = torch.nn.Linear(cin, cout).to(DEV).double()
+    ref.load_state_dict({k: v.double() for k, v in lin.state_dict().items()})
+    parts = [(torch.randn(n, c, generator=g) * 2 + 0.5).to(DEV).requires_grad_(True) for c in widths]
+    xr = torch.cat([p.detach().double() for p in parts], 1).requires_grad_(True)
+    coef = torch.randn(n, cout, generator=g).to(DEV)
+    took = []
+    for cls in (linear._PointLinear, linear._SkinnyLinear, linear._SkinnyLinearParts):
+        monkeypatch.setattr(cls, "apply", staticmethod(lambda *a, _cls=cls, _apply=cls.apply: (took.append(_cls.__name__), _apply(*a))[1]))
+    if site.startswith("row_linear"):
+        y = linear.row_linear(parts[0], lin.weight, lin.bias, **({"min_rows": 0} if "min_rows" in site else {}))
+        assert (y is linear.NOT_SERVED) == (function is None)
+        y = lin(parts[0]) if y is linear.NOT_SERVED else y
+    else:
+        y = lin.forward(parts[0]) if site == "forward" else lin.forward_parts(parts)
+    assert took == ([function] if function else []), took
+    (y * coef).sum().backward()
+    want = ref(xr)
+    (want * coef.double()).sum().backward()
+    pairs = [("y", y, want), ("dx", torch.cat([p.grad for p in parts], 1), xr.grad), ("dw", lin.weight.grad, ref.weight.grad),
+             ("db", lin.bias.grad, ref.bias.grad)]
+    for name, got, exp in pairs:
+        assert got.dtype == torch.float32, name
+        got, exp = got.detach().double(), exp.detach()
+        err = float((got - exp).abs().max()) / float(exp.abs().max())
+        print("%s %s n=%d %s: %.3g" % (site, widths, n, name, err))
+        assert err <= 2e-5, (name, err)
 
 
 # ---- device-side sparse_quantize (SURVEY 8 f1) ---------------------------------------------------------

@@ -914,7 +914,7 @@ def _wgrad_sites():
     """name -> run(ca, cb, dtype, hd): the backward of each of the five Functions, asked for the weight gradient alone, on
     (_WG_N, ca) rows and a (_WG_N, cb) gradient of `dtype`; hd is the half dtype the forward would have noted. -> weight gradient."""
     from types import SimpleNamespace as NS
-    from openpcseg_amd import block_fusion, fused
+    from openpcseg_amd import linear
     rows = lambda c, dtype: torch.ones(_WG_N, c, dtype=dtype)
     ident = lambda: {("_pcs_identity", _WG_N, "cpu"): NS(K=1)}
 
@@ -929,21 +929,21 @@ def _wgrad_sites():
 
     def skinny(ca, cb, dtype, hd):
         ctx = NS(saved_tensors=(rows(ca, dtype), torch.zeros(cb, ca)), km=NS(K=1), hd=hd, needs_input_grad=(False, True, False))
-        return fused._SkinnyLinear.backward(ctx, rows(cb, dtype))[1]
+        return linear._SkinnyLinear.backward(ctx, rows(cb, dtype))[1]
 
     def parts(ca, cb, dtype, hd):
         ctx = NS(saved_tensors=(torch.zeros(cb, ca), rows(ca, dtype)), km=NS(K=1), hd=hd, has_bias=False,
                  needs_input_grad=(True, False, False, False, False))
-        return fused._SkinnyLinearParts.backward(ctx, rows(cb, dtype))[0]
+        return linear._SkinnyLinearParts.backward(ctx, rows(cb, dtype))[0]
 
     def point(ca, cb, dtype, hd):
         ctx = NS(saved_tensors=(rows(ca, dtype), torch.zeros(cb, ca)), hd=hd, has_bias=False, in_dtype=dtype,
                  needs_input_grad=(False, True, False))
-        block_fusion._POINT_MAPS.update(ident())
+        linear._POINT_MAPS.update(ident())
         try:
-            return block_fusion._PointLinear.backward(ctx, rows(cb, dtype))[1]
+            return linear._PointLinear.backward(ctx, rows(cb, dtype))[1]
         finally:
-            block_fusion._POINT_MAPS.clear()
+            linear._POINT_MAPS.clear()
 
     return {"_SparseConv": sparse, "_PointwiseConv": pointwise, "_SkinnyLinear": skinny, "_SkinnyLinearParts": parts, "_PointLinear": point}
 
@@ -997,6 +997,174 @@ def test_weight_gradient_entry_table(monkeypatch):
                 assert one(site, 96, 96, f32, None)[4] is False, site
     finally:
         F.set_wgrad_policy("fp32")
+
+
+# ---- Linear over tall rows: one eligibility rule, one dtype rule for every site (openpcseg_amd/linear.py) ------------------------------
+_TL_ROWS = (4095, 4096, 0)
+_TL_WIDTHS = ((9, 64), (32, 256), (256, 20), (8, 6), (100, 36))
+_TL_PARTS = (((256, 128, 96), 20), ((256, 128, 94), 20))
+_TL_KINDS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp64": torch.float64, "3d": torch.float32}
+_TL_AMP = {"off": None, "bf16": torch.bfloat16}
+_TL_HD = {None: "", torch.bfloat16: "b", torch.float16: "h", torch.float64: "d"}
+_TL_WORKLOAD_SITES = ("cylinder._linear", "spvcnn._merge", "rpvnet._merge")
+
+
+def _tl_home():
+    """Where the family lives, and the one site that is a call rather than a function of its own."""
+    from types import SimpleNamespace as NS
+    from openpcseg_amd import linear
+
+    def spvcnn_parts(lin, parts):   # block_fusion._spvcnn_forward's classifier line
+        out = linear.parts_linear(lin.weight, lin.bias, parts)
+        return lin(torch.cat(parts, dim=1)) if out is linear.NOT_SERVED else out
+    return NS(point=linear._PointLinear, skinny=linear._SkinnyLinear, parts=linear._SkinnyLinearParts, FusedLinear=linear.FusedLinear,
+              devoxelized_linear=linear.devoxelized_linear, spvcnn_parts=spvcnn_parts)
+
+
+def _tall_linear_routes(mp, home):
+    """{site: {(kind, autocast): "codes of the widths at 4095 rows / at 4096 / at 0"}}: which Function each site of DESIGN.md's table
+    takes and the half dtype it is handed. P = _PointLinear, S = _SkinnyLinear, Q = _SkinnyLinearParts, R = the forward-only
+    gather-GEMM of the frozen classifier, each followed by b / h for bf16 / fp16; - = the stock path; !Name = raises."""
+    from types import SimpleNamespace as NS
+    from openpcseg_amd import block_fusion, fused, inference
+    from openpcseg_amd.workloads import cylinder, rpvnet, spvcnn
+    log, marker = [], torch.zeros(1)
+
+    def recorder(code, hd_of):
+        return staticmethod(lambda *a: (log.append(code + _TL_HD[hd_of(a)]), marker)[1])
+
+    mp.setattr(home.point, "apply", recorder("P", lambda a: F._amp_dtype(a[0])))
+    mp.setattr(home.skinny, "apply", recorder("S", lambda a: a[4]))
+    mp.setattr(home.parts, "apply", recorder("Q", lambda a: a[3]))
+    mp.setattr(F, "_run_conv", lambda be, fam, x, w3, km, hd, *a, **kw: (log.append("R" + _TL_HD[hd]), (marker, x, False))[1])
+    mp.setattr(F, "_conv_family", lambda *a, **kw: "fp32")
+    mp.setattr(F, "_identity_map", lambda *a, **kw: "km")
+    mp.setattr(F, "spdevoxelize", lambda v, idx, wts: v)
+    mp.setattr(torch.nn.Linear, "forward", lambda self, x: (log.append("-"), marker)[1])
+    mp.setattr(torch.nn.functional, "linear", lambda x, w, b=None: (log.append("-"), marker)[1])
+    mp.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
+    mp.setattr(torch.Tensor, "float", lambda self: self)   # the stock path's casts: nothing is computed here
+    cat = torch.cat   # the parts' fallback: torch's own shape and dtype rules on one row, the row count of the first part
+    mp.setattr(torch, "cat", lambda ps, dim=0: cat([p[:1] for p in ps], dim=dim).expand(ps[0].shape[0], *[-1] * (ps[0].dim() - 1)))
+    mp.setattr(native, "_BACKEND", NS(bn_apply=None, name="stub"))
+    mp.setattr(block_fusion, "_dense_bn_apply", lambda bn, h, relu: h)
+    for m in (spvcnn, rpvnet):
+        mp.setattr(m, "point_maps", lambda x, z: (None, None))
+    mp.setattr(fused, "point_merge", lambda bn, h, *a: h)
+    mp.setattr(fused, "range_point_merge", lambda bn, h, *a: h)
+    amp = {"dtype": None}
+    mp.setattr(torch, "is_autocast_enabled", lambda *a: amp["dtype"] is not None)
+    mp.setattr(torch, "get_autocast_dtype", lambda *a: amp["dtype"] or torch.float32)
+
+    mods = {}
+
+    def lin_of(cls, cin, cout):
+        if (cls, cin, cout) not in mods:
+            m = mods[(cls, cin, cout)] = cls(cin, cout)
+            m.__dict__["_pcs_orig_class"] = torch.nn.Linear   # what fuse() leaves on a re-classed stock module
+        return mods[(cls, cin, cout)]
+
+    def z_of(x):
+        return NS(F=x, C=None, idx_query=None, weights=None, additional_features=None)
+
+    stock, own = torch.nn.Linear, home.FusedLinear
+    single = {
+        "FusedLinear.forward": lambda x, ci, co: lin_of(own, ci, co).forward(x),
+        "devoxelized_linear": lambda x, ci, co: home.devoxelized_linear(lin_of(stock, ci, co).weight, 0, x, None, None, {}),
+        "FoldedLinear.devoxelized_part": lambda x, ci, co: inference.FoldedLinear(lin_of(own, ci, co)).devoxelized_part(0, x, None, None, cache={}),
+        "FoldedLinear.devoxelized_part, no cache": lambda x, ci, co: inference.FoldedLinear(lin_of(own, ci, co)).devoxelized_part(0, x, None, None),
+        "block_fusion._dense_step": lambda x, ci, co: block_fusion._dense_step(lin_of(stock, ci, co), torch.nn.Identity(), None, x),
+        "block_fusion._dense_linear_forward": lambda x, ci, co: block_fusion._dense_linear_forward(lin_of(stock, ci, co), x),
+        "cylinder._linear": lambda x, ci, co: cylinder._linear(lin_of(stock, ci, co), x),
+        "spvcnn._merge": lambda x, ci, co: spvcnn.SPVCNN._merge(NS(point_transforms=[[lin_of(stock, ci, co), None]]), 0, NS(F=None), z_of(x)),
+        "rpvnet._merge": lambda x, ci, co: rpvnet.RPVNet._merge(NS(point_transforms=[[lin_of(stock, ci, co), None]], grid_sample_mode="bilinear"),
+                                                                0, NS(F=None), z_of(x), None, None),
+    }
+    multi = {
+        "FusedLinear.forward_parts": lambda ps, ci, co: lin_of(own, ci, co).forward_parts(ps),
+        "block_fusion._spvcnn_forward": lambda ps, ci, co: home.spvcnn_parts(lin_of(stock, ci, co), ps),
+    }
+    made = {}
+
+    def rows(kind, n, c, dtype=None):
+        key = (kind, n, c, dtype)
+        if key not in made:
+            made[key] = torch.zeros(1, dtype=dtype or _TL_KINDS[kind]).expand((n, 2, c) if kind == "3d" else (n, c))   # no memory behind it
+        return made[key]
+
+    def one(run, *a):
+        del log[:]
+        try:
+            run(*a)
+        except Exception as e:
+            return "!" + type(e).__name__
+        return "+".join(log)
+
+    table = {}
+    for name, amp_dtype in _TL_AMP.items():
+        amp["dtype"] = amp_dtype
+        for kind in _TL_KINDS:
+            for site, run in single.items():
+                table.setdefault(site, {})[(kind, name)] = " / ".join(
+                    " ".join(one(run, rows(kind, n, ci), ci, co) for ci, co in _TL_WIDTHS) for n in _TL_ROWS)
+        # parts: as above, and "mixed" = an fp32 part in front of bf16 ones (the first dtype that is not fp32 names the call's)
+        for kind in tuple(_TL_KINDS) + ("mixed",):
+            for site, run in multi.items():
+                def parts(n, widths):
+                    if kind == "mixed":
+                        return [rows("fp32", n, c, torch.bfloat16 if i else None) for i, c in enumerate(widths)]
+                    return [rows(kind, n, c) for c in widths]
+                table.setdefault(site, {})[(kind, name)] = " / ".join(
+                    " ".join(one(run, parts(n, ws), sum(ws), co) for ws, co in _TL_PARTS) for n in _TL_ROWS)
+    return table
+
+
+def _tl_table(fp32_off, fp32_amp, bf16, fp64_off=None, fp64_amp=None, d3_off=None, d3_amp=None, every_row=False):
+    """The codes at 4096 rows by (kind, autocast) -> the full table of one site: the same codes at 4095 and 0 rows (every_row: a site
+    without a row floor), else the stock path there. Unnamed kinds: the stock path at every width."""
+    none = " ".join("-" * len(fp32_off.split()))
+    at = {("fp32", "off"): fp32_off, ("fp32", "bf16"): fp32_amp, ("bf16", "off"): bf16, ("bf16", "bf16"): bf16,
+          ("fp64", "off"): fp64_off or none, ("fp64", "bf16"): fp64_amp or none, ("3d", "off"): d3_off or none, ("3d", "bf16"): d3_amp or none}
+    return {k: " / ".join((v if every_row else none, v, v if every_row else none)) for k, v in at.items()}
+
+
+# What the PARENT of linear.py answered (the probe above, run against that tree with the Functions at their old addresses and
+# _spvcnn_forward's pasted block executed from its source), widths in _TL_WIDTHS order / parts in _TL_PARTS order.
+_TL_POINT = ("P P P - P", "Pb Pb Pb - Pb", "Pb Pb Pb - Pb")
+_TL_PARTS_ROUTES = {**_tl_table("Q -", "Qb -", "Qb -"), **{("mixed", a): "- - / Qb - / - -" for a in _TL_AMP},
+                    **{("3d", a): " / ".join(["!RuntimeError !RuntimeError"] * 3) for a in _TL_AMP}}   # torch.cat of the fallback
+_TL_PARENT = {
+    "FusedLinear.forward": _tl_table("- S S - S", "- Sb Sb - Sb", "- Sb Sb - Sb"),
+    "devoxelized_linear": _tl_table("- S S - S", "- S S - S", "- Sb Sb - Sb"),                        # ignores autocast
+    "FoldedLinear.devoxelized_part": _tl_table("- R R - R", "- R R - R", "- Rb Rb - Rb"),             # likewise
+    "FoldedLinear.devoxelized_part, no cache": _tl_table("- S S - S", "- S S - S", "- Sb Sb - Sb"),
+    "block_fusion._dense_step": _tl_table(*_TL_POINT),
+    "block_fusion._dense_linear_forward": _tl_table(*_TL_POINT),
+    # the three workload sites tested neither dtype nor rank: fp64 rows were computed in fp32, a 3-D tensor failed in backward
+    "cylinder._linear": _tl_table(*_TL_POINT, *_TL_POINT[:2], *_TL_POINT[:2]),
+    "spvcnn._merge": _tl_table(*_TL_POINT, *_TL_POINT[:2], *_TL_POINT[:2], every_row=True),
+    "rpvnet._merge": _tl_table(*_TL_POINT, *_TL_POINT[:2], *_TL_POINT[:2], every_row=True),
+    "FusedLinear.forward_parts": _TL_PARTS_ROUTES,
+    "block_fusion._spvcnn_forward": _TL_PARTS_ROUTES,
+}
+
+
+def test_tall_linear_route_table(monkeypatch):
+    """Every site that runs a Linear over tall rows takes the Function, and hands it the half dtype, that it took on the parent of
+    linear.py: rows 4095 / 4096 / 0, widths on and off the 16-byte pieces, fp32 / bf16 / fp64 rows, a 3-D tensor, autocast off / bf16,
+    parts that sum to the weight's width in whole pieces and not. The ONLY answers allowed to differ from the parent's: fp64 rows
+    and 3-D tensors at the three workload sites, which the shared rule now sends to the stock Linear."""
+    with monkeypatch.context() as mp:
+        got = _tall_linear_routes(mp, _tl_home())
+    assert set(got) == set(_TL_PARENT)
+    stock = _tl_table("- - - - -", "- - - - -", "- - - - -")
+    for site, want in _TL_PARENT.items():
+        assert set(got[site]) == set(want), site
+        for key, codes in want.items():
+            if site in _TL_WORKLOAD_SITES and key[0] in ("fp64", "3d"):
+                assert codes != stock[key], (site, key)   # the parent did serve them
+                codes = stock[key]
+            assert got[site][key] == codes, (site, key, got[site][key], codes)
 
 
 # ---- the convolution plan (csrc/conv_plan.h): what the entries launch from and the shape queries answer from ----------------------------

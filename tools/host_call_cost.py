@@ -79,6 +79,19 @@ def main():
         y = bn(conv(s2), relu=True)
         y.F.sum().backward()
     rows.append(("Conv3d + FusedBN forward+backward (autograd)", cost(fb, 200)))
+    # Linear over tall rows: the eligibility rule, the dtype rule and the identity-map lookup in front of each Function (4096 rows)
+    try:
+        from openpcseg_amd.linear import FusedLinear, row_linear
+    except ImportError:   # a tree from before linear.py
+        from openpcseg_amd.block_fusion import _PointLinear
+        from openpcseg_amd.fused import FusedLinear
+        row_linear = lambda x, w, b: _PointLinear.apply(x, w, b)
+    rows4k, lin = torch.randn(4096, 32, device=dev), FusedLinear(32, 20).to(dev)
+    parts3 = [torch.randn(4096, c, device=dev) for c in (16, 8, 8)]
+    with torch.no_grad():
+        rows.append(("row-wise Linear 32 -> 20 forward (no grad)", cost(lambda: row_linear(rows4k, lin.weight, lin.bias))))
+        rows.append(("FusedLinear.forward 32 -> 20 (no grad)", cost(lambda: lin.forward(rows4k))))
+        rows.append(("FusedLinear.forward_parts 16+8+8 -> 20 (no grad)", cost(lambda: lin.forward_parts(parts3))))
     for name, us in rows:
         print("%-48s %8.1f us" % (name, us))
 
