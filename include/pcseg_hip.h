@@ -572,6 +572,34 @@ int pcs_quantize_flags(const int64_t *sorted_keys, int64_t n, int32_t *flags, vo
 int pcs_quantize_emit(const int32_t *flags, const int64_t *rank, const int64_t *perm, const int32_t *coords,
                       int64_t n, int32_t *vox, int64_t *index, int64_t *inverse, void *stream);
 
+/* ---- device-side dataset transform: augmentation, test-time-augmentation votes, voxel coordinates ----
+ * Replaces, for scans resident in HBM, the per-scan NumPy transform of the dataloader workers:
+ *   aug_points             R:tools/utils/common/seg_utils.py:43-100 (rotate :56-69, scale :72-75, flip :78-89, jitter :92-98)
+ *   get_single_sample      R:pcseg/data/dataset/semantickitti/semantickitti_voxel.py:83-114 (augmented xyz stored as float32 = the
+ *                          feature rows; pc_ = round(xyz / voxel_size) as int32; pc_ -= pc_.min(0))
+ *   the ten votes of TTA   R:pcseg/data/dataset/semantickitti/semantickitti_voxel.py:62-69
+ * transform: points (n, c) fp32 contiguous, 3 <= c <= PCS_SCAN_MAX_COLUMNS, the frames one after the other; frame_offsets
+ *   (num_frames + 1) int64 on the device = first row of every frame and n; params (num_votes * num_frames, 8) float64 on the
+ *   device, vote-major: row v * num_frames + f = {cos, sin, scale, sx, sy, jx, jy, jz} of vote v of frame f; 1 <= num_votes <=
+ *   PCS_SCAN_MAX_VOTES. Per row i of frame f and vote v, in float64 and in this order, no multiply-add fused:
+ *     X = x * cos + y * (-sin), Y = x * sin + y * cos, Z = z;  X, Y, Z *= scale;  X *= sx, Y *= sy;  X, Y, Z += jx, jy, jz
+ *   feats (num_votes * n, c) fp32: row v * n + i = {float(X), float(Y), float(Z), the other columns unchanged};
+ *   coords (num_votes * n, 3) int32: rintf(feats / voxel_size), an IEEE float32 division, ties to even;
+ *   mins (num_votes * num_frames, 3) int32: the minimum of coords over the rows of (v, f), written by the call whatever it held
+ *   (INT32_MAX for an empty frame); ws: caller scratch of at least the ws_bytes query's size for the same n, num_frames and
+ *   num_votes (else PCS_EWORKSPACE), 4-byte aligned, contents irrelevant on entry.
+ * shift: coords[v * n + i] -= mins[v * num_frames + frame of i] in place; frames (num_votes * n) int64 = v * num_frames + frame
+ *   of i, the scene vector the batch dedup of pcs_quantize_frame_keys takes.
+ * Offsets outside [0, n] are clamped: no row outside the arrays is addressed. */
+#define PCS_SCAN_MAX_VOTES 16
+#define PCS_SCAN_MAX_COLUMNS 8
+int64_t pcs_scan_transform_ws_bytes(int64_t n, int32_t num_frames, int32_t num_votes);
+int pcs_scan_transform(const float *points, int64_t n, int32_t c, const int64_t *frame_offsets, int32_t num_frames,
+                       const double *params, int32_t num_votes, float voxel_size, float *feats, int32_t *coords,
+                       int32_t *mins, void *ws, int64_t ws_bytes, void *stream);
+int pcs_scan_shift(int32_t *coords, int64_t n, const int64_t *frame_offsets, int32_t num_frames, const int32_t *mins,
+                   int32_t num_votes, int64_t *frames, void *stream);
+
 /* Unique keys + inverse map + CSR row pointers from a STABLY sorted key vector (flags from pcs_quantize_flags, rank =
  * their inclusive scan, perm = the sort's row permutation): uniq (m), inverse (n) = run index of every original row,
  * rowptr (m + 1) = first sorted position of every run (rowptr[m] = n). One pass for what initial_voxelize

@@ -37,7 +37,7 @@ from .fused import FusedBatchNorm
 from .linear import FusedLinear, devoxelized_linear
 from .sparse import SparseTensor
 
-__all__ = ["freeze", "unfreeze", "FoldedConv", "PostAffineConv", "FoldedDense", "SegEvaluator", "point_predict"]
+__all__ = ["freeze", "unfreeze", "FoldedConv", "PostAffineConv", "FoldedDense", "SegEvaluator", "point_predict", "predict_tta"]
 
 _NORMS = (FusedBatchNorm, nn.BatchNorm1d)   # spnn.BatchNorm and the workloads' _BN / _SyncBN are BatchNorm1d / SyncBatchNorm
 _ATTR = "_pcs_folds"
@@ -470,3 +470,65 @@ class SegEvaluator:
             import warnings
             warnings.warn("openpcseg_amd: inverse_map entries pointed outside their scene's rows; those points were not counted")
         return self.metrics(host[:-1].reshape(self.num_class, self.num_class), self.unique_label)
+
+
+# ---- evaluation with test-time augmentation ---------------------------------------------------------------------------------
+def predict_tta(model, raw, num_votes=10, evaluator=None, voxel_size=0.05, rng=np.random, vote_chunk=None, return_logits=False,
+                scale_range=(0.9, 1.1)):
+    """An evaluation of a raw batch resident in HBM under the reference's test-time augmentation (`TTA: True`:
+    R:pcseg/data/dataset/semantickitti/semantickitti_voxel.py:62-69 and :94-110, ten rotated and rescaled votes per frame, collated as ten scenes;
+    R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:445-446 `return_tta` hands out each scene's softmax rows, which are summed
+    here): `transform.tta_params` draws the votes from `rng`, `transform.device_batch` builds them from one read
+    of the scans, the model's eval forward (`point_logits`, the call `predict` makes) runs over `vote_chunk` votes at a time (None:
+    all votes in one forward), and each vote's softmax is added into ONE (n, num_class) fp32 tensor by the prediction tail
+    (native.predict_points on that vote's scenes). The decision is the arg-max after the last vote; `evaluator` (a SegEvaluator)
+    gets its confusion counts from that decision only, once per point. raw: the dict of workloads.synthetic.make_raw_batch, on the device.
+    -> {"pred" (n,) int64, "votes" (n, num_class) fp32, "point_offset": host frame boundaries, "params": the (num_votes *
+    num_frames, 8) table drawn} and with return_logits "logits": per vote the (voxels of that vote's scenes, num_class) fp32 logits."""
+    from . import transform
+    if model.training:
+        raise RuntimeError("predict_tta is an evaluation pass: call model.eval() first")
+    fn = getattr(model, "point_logits", None)
+    if not callable(fn) or isinstance(fn, nn.Module):
+        raise TypeError("openpcseg_amd: predict_tta needs a model with a point_logits(lidar) method (MinkUNet, SPVCNN)")
+    nf = int(raw["num_frames"])
+    off = [int(o) for o in raw["offsets"]]
+    n = off[-1]
+    nv = int(num_votes)
+    chunk = nv if vote_chunk is None else max(1, min(int(vote_chunk), nv))
+    params = transform.tta_params(nf, nv, scale_range=scale_range, rng=rng)
+    be = native.backend()
+    dev = raw["points"].device
+    labels = raw["labels"].long().contiguous() if evaluator is not None else None
+    if evaluator is not None:
+        evaluator._ensure(dev)
+    point_offset = native._h2d(off, torch.int64, dev)
+    votes = pred = bad = None
+    kept = []
+    for v0 in range(0, nv, chunk):
+        k = min(chunk, nv - v0)
+        batch = transform.device_batch(raw, voxel_size, params[v0 * nf:(v0 + k) * nf], votes=k, eval_maps=True)
+        with torch.inference_mode():
+            logits = fn(batch["lidar"]).float().contiguous()
+        if votes is None:
+            if evaluator is not None and logits.shape[1] != evaluator.num_class:
+                raise ValueError("openpcseg_amd: %d logit columns for a %d-class evaluator" % (logits.shape[1], evaluator.num_class))
+            votes = torch.zeros((n, logits.shape[1]), dtype=torch.float32, device=dev)
+            bad = evaluator.bad if evaluator is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+        row_offset = _scene_offsets(batch["lidar"].C[:, -1], k * nf)
+        inverse = batch["inverse_map"].F
+        for j in range(k):
+            last = v0 + j == nv - 1
+            count = last and evaluator is not None
+            pred, _ = be.predict_points(logits, inverse=inverse[j * n:(j + 1) * n], point_offset=point_offset,
+                                        row_offset=row_offset[j * nf:(j + 1) * nf + 1], labels=labels if count else None,
+                                        votes=votes, want_pred=last, hist=evaluator.hist if count else None, bad=bad)
+            if return_logits:
+                kept.append((logits, row_offset, j))
+    if evaluator is not None:
+        evaluator.last_offsets = off
+    out = {"pred": pred, "votes": votes, "point_offset": off, "params": params}
+    if return_logits:
+        bounds = {id(r): r.cpu().tolist() for _, r, _ in kept}   # asked for explicitly: the only read-back, after everything is queued
+        out["logits"] = [lg[bounds[id(r)][j * nf]:bounds[id(r)][(j + 1) * nf]] for lg, r, j in kept]
+    return out

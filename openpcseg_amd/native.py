@@ -108,6 +108,9 @@ SIGNATURES = {
     "pcs_quantize_frame_keys": (c_int32, [_P, _P, c_int64, _P, _P, _P]),
     "pcs_quantize_flags": (c_int32, [_P, c_int64, _P, _P]),
     "pcs_quantize_emit": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
+    "pcs_scan_transform_ws_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "pcs_scan_transform": (c_int32, [_P, c_int64, c_int32, _P, c_int32, _P, c_int32, c_float, _P, _P, _P, _P, c_int64, _P]),
+    "pcs_scan_shift": (c_int32, [_P, c_int64, _P, c_int32, _P, c_int32, _P, _P]),
     "pcs_conv_h_applies": (c_int32, [c_int32, c_int32, c_int32]),
     "pcs_conv_prepared_weights_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "pcs_conv_prepare_weights_h": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
@@ -1309,6 +1312,53 @@ class HipBackend:
         coords = _dev(coords, "coords", torch.int32)
         vox, index, inverse = self._voxel_emit(keys, coords, True, True)
         return torch.cat([vox, frames[index].int()[:, None]], dim=1), index, inverse
+
+    # -- device-side dataset transform (csrc/scantransform.hip) -------------------------------------------
+    MAX_VOTES, MAX_COLUMNS = 16, 8   # PCS_SCAN_MAX_VOTES, PCS_SCAN_MAX_COLUMNS of include/pcseg_hip.h
+
+    def scan_transform(self, points, offsets, params, votes, voxel_size):
+        """points (n, C) fp32 on the device, frame after frame; offsets: the HOST list of num_frames + 1 frame boundaries; params:
+        host (votes * num_frames, 8) float64, vote-major (transform.py) -> (feats (votes * n, C) fp32, coords (votes * n, 3) int32
+        -- not yet shifted --, mins (votes * num_frames, 3) int32, the frame boundaries as an int64 device tensor). The parameter
+        table and the boundaries travel in ONE pinned asynchronous copy (the table's bit patterns as int64); nothing is read back."""
+        import numpy as np
+        points = _dev(points, "points", torch.float32)
+        if points.dim() != 2:
+            raise ValueError("openpcseg_amd: scan_transform wants (n, C) points, got %s" % (tuple(points.shape),))
+        n, c = points.shape
+        nf, v = len(offsets) - 1, int(votes)
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if nf < 1 or params.shape != (v * nf, 8):
+            raise ValueError("openpcseg_amd: scan_transform wants (votes * num_frames, 8) parameters, got %s for %d votes of %d frames"
+                             % (params.shape, v, nf))
+        dev = points.device
+        table = _h2d(params.reshape(-1).view(np.int64).tolist() + [int(o) for o in offsets], torch.int64, dev)
+        par, off = table[:v * nf * 8].view(torch.float64), table[v * nf * 8:]
+        feats = torch.empty((v * n, c), dtype=torch.float32, device=dev)
+        coords = torch.empty((v * n, 3), dtype=torch.int32, device=dev)
+        mins = torch.empty((v * nf, 3), dtype=torch.int32, device=dev)
+        ws_bytes = self.lib.pcs_scan_transform_ws_bytes(n, nf, v)
+        if ws_bytes < 0:
+            _check(-1, "pcs_scan_transform_ws_bytes")
+        ws = torch.empty(max(int(ws_bytes), 4), dtype=torch.uint8, device=dev)
+        _check(self.lib.pcs_scan_transform(_ptr(points), n, c, _ptr(off), nf, _ptr(par), v, float(voxel_size), _ptr(feats), _ptr(coords),
+                                           _ptr(mins), _ptr(ws), ws.numel(), _stream()), "pcs_scan_transform")
+        return feats, coords, mins, off
+
+    def scan_shift(self, coords, mins, frame_offsets, votes):
+        """coords (votes * n, 3) int32 -= the minimum of their (vote, frame), IN PLACE -> frames (votes * n,) int64: the scene
+        vote * num_frames + frame of every row (what hostdata.sparse_quantize_frames takes)."""
+        coords = _dev(coords, "coords", torch.int32)
+        mins = _dev(mins, "mins", torch.int32)
+        frame_offsets = _dev(frame_offsets, "frame_offsets", torch.int64)
+        v, nf = int(votes), frame_offsets.numel() - 1
+        if v < 1 or coords.shape[0] % v or mins.numel() != v * nf * 3:
+            raise ValueError("openpcseg_amd: scan_shift wants votes * n coordinate rows and votes * num_frames minima")
+        n = coords.shape[0] // v
+        frames = torch.empty(v * n, dtype=torch.int64, device=coords.device)
+        _check(self.lib.pcs_scan_shift(_ptr(coords), n, _ptr(frame_offsets), nf, _ptr(mins), v, _ptr(frames), _stream()),
+               "pcs_scan_shift")
+        return frames
 
     def unique_inverse_csr(self, keys):
         """keys (n,) int64 -> (uniq (m,) ascending, inverse (n,) int64, counts (m,) int32); the stable sort behind it is
