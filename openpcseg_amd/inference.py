@@ -34,12 +34,12 @@ from . import functional as F
 from . import modules as spnn
 from . import native
 from .fused import FusedBatchNorm
-from .linear import FusedLinear, devoxelized_linear
+from .linear import devoxelized_linear
 from .sparse import SparseTensor
 
 __all__ = ["freeze", "unfreeze", "FoldedConv", "PostAffineConv", "FoldedDense", "SegEvaluator", "point_predict", "predict_tta"]
 
-_NORMS = (FusedBatchNorm, nn.BatchNorm1d)   # spnn.BatchNorm and the workloads' _BN / _SyncBN are BatchNorm1d / SyncBatchNorm
+_NORMS = (FusedBatchNorm, nn.BatchNorm1d)   # spnn.BatchNorm and the models' _BN / _SyncBN are BatchNorm1d / SyncBatchNorm
 _ATTR = "_pcs_folds"
 
 
@@ -82,42 +82,59 @@ def _bn_affine(bn):
     return s, t
 
 
-class FoldedConv:
-    """conv + the BatchNorm that follows it as one convolution with bias; `relu`: the chain ends in a ReLU."""
+class _FoldRecord:
+    """What a frozen module keeps beside itself for one of its layers, and the one rule for "is it still current": `refresh`
+    stamps the tensors `_sources()` names, and where the stamp moved (or cannot be taken) it calls `_fold()` under no_grad, empties
+    the dict of derived copies and counts. A subclass supplies `_sources()` and `_fold()`; DERIVED names its dict of copies that
+    depend on the sources (None: it keeps none)."""
+    DERIVED = None
+    COUNTED = True   # `folds`: how often the BatchNorm arithmetic ran (tests); a record without any carries no counter
+
+    def __init__(self):
+        self._stamp = None
+        if self.DERIVED:
+            setattr(self, self.DERIVED, {})
+        if self.COUNTED:
+            self.folds = 0
+
+    def _fold(self):
+        pass
+
+    def refresh(self):
+        stamp = _stamp_of(self._sources())
+        if stamp is None or stamp != self._stamp:
+            with torch.no_grad():
+                self._fold()
+            if self.DERIVED:
+                setattr(self, self.DERIVED, {})
+            self._stamp = stamp
+            if self.COUNTED:
+                self.folds += 1
+
+
+class FoldedConv(_FoldRecord):
+    """conv + the BatchNorm that follows it as one convolution with bias; `relu`: the chain ends in a ReLU. `prepared`: the
+    derived copies of `weight` (functional.conv3d_inference), dropped with it."""
+    DERIVED = "prepared"
 
     def __init__(self, conv, bn, relu):
+        super().__init__()
         self.conv, self.bn, self.relu = conv, bn, bool(relu)
-        self._stamp = None
         self.weight = self.bias = None
-        self.prepared = {}   # derived copies of `weight` (functional.conv3d_inference), dropped with it
-        self.folds = 0       # how often the arithmetic ran (tests)
 
     def _sources(self):
-        c, b = self.conv, self.bn
-        return [c.kernel, c.bias, getattr(b, "weight", None), getattr(b, "bias", None), b.running_mean, b.running_var]
+        return [self.conv.kernel, self.conv.bias] + _bn_sources(self.bn)
 
-    def _current(self):
-        return _stamp_of(self._sources())
+    def _fold(self):
+        s, t = _bn_affine(self.bn)
+        if self.conv.bias is not None:
+            t = t + self.conv.bias.detach().double() * s
+        self.weight = (self.conv.kernel.detach().double() * s).float().contiguous()
+        self.bias = t.float().contiguous()
 
     def folded(self):
         """-> (W' fp32, b' fp32, the dict of derived copies), re-folded when a source tensor changed."""
-        stamp = self._current()
-        if stamp is None or stamp != self._stamp:
-            kernel, cbias, gamma, beta, mean, var = self._sources()
-            with torch.no_grad():
-                s = torch.rsqrt(var.detach().double() + self.bn.eps)
-                if gamma is not None:
-                    s = gamma.detach().double() * s
-                shift = -mean.detach().double() * s
-                if beta is not None:
-                    shift = shift + beta.detach().double()
-                if cbias is not None:
-                    shift = shift + cbias.detach().double() * s
-                self.weight = (kernel.detach().double() * s).float().contiguous()
-                self.bias = shift.float().contiguous()
-            self.prepared = {}
-            self._stamp = stamp
-            self.folds += 1
+        self.refresh()
         return self.weight, self.bias, self.prepared
 
     def __call__(self, x, residual=None):
@@ -127,33 +144,29 @@ class FoldedConv:
                                   addend=residual, relu=self.relu, prepared=prepared)
 
 
-class PostAffineConv:
+class PostAffineConv(_FoldRecord):
     """conv -> LeakyReLU(slope) -> BatchNorm (+ residual) as one launch with the BatchNorm as the affine map behind the activation:
     scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, float64 arithmetic stored as fp32; the kernel
-    `W` is used as it is. bn None (UpBlock.up_subm): a plain convolution whose record only keeps the derived weight copies; the
-    `residual` of such a record is the ordinary addend. Re-folded per source-tensor version like FoldedConv."""
+    `W` is used as it is. bn None (UpBlock.up_subm): a plain convolution whose record only keeps the derived weight copies
+    (`prepared`, dropped when the kernel changes); the `residual` of such a record is the ordinary addend."""
+    DERIVED = "prepared"
 
     def __init__(self, conv, bn=None, slope=None):
+        super().__init__()
         self.conv, self.bn, self.slope = conv, bn, (float(slope) if slope is not None else None)
-        self._stamp = None
         self.scale = self.shift = None
-        self.prepared = {}   # derived copies of the kernel (functional.conv3d_inference), dropped when it changes
-        self.folds = 0       # how often the arithmetic ran (tests)
 
     def _sources(self):
         return [self.conv.kernel, self.conv.bias] + (_bn_sources(self.bn) if self.bn is not None else [])
 
+    def _fold(self):
+        if self.bn is not None:
+            s, t = _bn_affine(self.bn)
+            self.scale, self.shift = s.float().contiguous(), t.float().contiguous()
+
     def folded(self):
         """-> (scale fp32, shift fp32, the dict of derived copies), re-folded when a source tensor changed."""
-        stamp = _stamp_of(self._sources())
-        if stamp is None or stamp != self._stamp:
-            if self.bn is not None:
-                with torch.no_grad():
-                    s, t = _bn_affine(self.bn)
-                    self.scale, self.shift = s.float().contiguous(), t.float().contiguous()
-            self.prepared = {}
-            self._stamp = stamp
-            self.folds += 1
+        self.refresh()
         return self.scale, self.shift, self.prepared
 
     def __call__(self, x, residual=None):
@@ -164,35 +177,32 @@ class PostAffineConv:
                                   act_slope=self.slope, post_scale=scale, post_shift=shift)
 
 
-class FoldedDense:
+class FoldedDense(_FoldRecord):
     """nn.Linear with the BatchNorm in front of it (`bn_in`: W diag(s), b + W t) and / or behind it (`bn_out`: diag(s) W, s b + t)
-    folded in, float64 arithmetic stored as fp32, kept per version of the source tensors: the point MLPs of Cylinder3D."""
+    folded in, float64 arithmetic stored as fp32: the point MLPs of Cylinder3D."""
 
     def __init__(self, lin, bn_in=None, bn_out=None):
+        super().__init__()
         self.lin, self.bn_in, self.bn_out = lin, bn_in, bn_out
-        self._stamp = None
         self.weight = self.bias = None
-        self.folds = 0
 
     def _sources(self):
         return [self.lin.weight, self.lin.bias] + [t for bn in (self.bn_in, self.bn_out) if bn is not None for t in _bn_sources(bn)]
 
+    def _fold(self):
+        w = self.lin.weight.detach().double()   # (out, in)
+        b = self.lin.bias.detach().double() if self.lin.bias is not None else torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)
+        if self.bn_in is not None:
+            s, t = _bn_affine(self.bn_in)
+            b = b + w @ t
+            w = w * s[None, :]
+        if self.bn_out is not None:
+            s, t = _bn_affine(self.bn_out)
+            w, b = w * s[:, None], b * s + t
+        self.weight, self.bias = w.float().contiguous(), b.float().contiguous()
+
     def folded(self):
-        stamp = _stamp_of(self._sources())
-        if stamp is None or stamp != self._stamp:
-            with torch.no_grad():
-                w = self.lin.weight.detach().double()   # (out, in)
-                b = self.lin.bias.detach().double() if self.lin.bias is not None else torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)
-                if self.bn_in is not None:
-                    s, t = _bn_affine(self.bn_in)
-                    b = b + w @ t
-                    w = w * s[None, :]
-                if self.bn_out is not None:
-                    s, t = _bn_affine(self.bn_out)
-                    w, b = w * s[:, None], b * s + t
-                self.weight, self.bias = w.float().contiguous(), b.float().contiguous()
-            self._stamp = stamp
-            self.folds += 1
+        self.refresh()
         return self.weight, self.bias
 
     def __call__(self, x):
@@ -200,25 +210,24 @@ class FoldedDense:
         return torch.nn.functional.linear(x, w, b)
 
 
-class FoldedLinear:
+class FoldedLinear(_FoldRecord):
     """The classifier's column blocks (FusedLinear.devoxelized_part) with their (1, cin, cout) gather-GEMM weights and fragment-ordered
-    half copies kept per weight version instead of being transposed and prepared on every forward (`linear.devoxelized_linear`,
-    memo): the logits are bit-identical to the unfrozen classifier's."""
+    half copies kept per weight version (`parts`) instead of being transposed and prepared on every forward
+    (`linear.devoxelized_linear`, memo): the logits are bit-identical to the unfrozen classifier's. No BatchNorm, no arithmetic."""
+    DERIVED, COUNTED = "parts", False
 
     def __init__(self, lin):
-        self.lin, self._stamp, self.parts = lin, None, {}
+        super().__init__()
+        self.lin = lin
+
+    def _sources(self):
+        return [self.lin.weight]
 
     def devoxelized_part(self, col, xf, idx, wts, cache=None):
-        w = self.lin.weight
         if cache is None:   # no per-forward dict for the identity map: the module's own path
             return self.lin.devoxelized_part(col, xf, idx, wts)
-        try:
-            stamp = (w._version, w.data_ptr(), w.device, w.dtype)
-        except RuntimeError:
-            stamp = None
-        if stamp is None or stamp != self._stamp:
-            self.parts, self._stamp = {}, stamp
-        return devoxelized_linear(w, col, xf, idx, wts, cache, memo=self.parts.setdefault((col, xf.shape[1]), {}))
+        self.refresh()
+        return devoxelized_linear(self.lin.weight, col, xf, idx, wts, cache, memo=self.parts.setdefault((col, xf.shape[1]), {}))
 
 
 def active(module):
@@ -263,76 +272,29 @@ def freeze(model):
     workloads.cylinder: the conv -> LeakyReLU -> BatchNorm triples of ResContextBlock / ResBlock / UpBlock become one launch each
     (PostAffineConv), the BatchNorms of the point MLPs fold into their Linear (FoldedDense); ReconNet's three keep running inside
     the gate kernel on the running statistics and are reported as skipped. Anything else is left alone. -> {"folded": number of BatchNorm modules that stop launching, "skipped": [names of BatchNorm modules that keep running]}.
-    Changes no parameter, buffer or state_dict entry; takes effect only in eval mode with grad mode off."""
-    from .workloads import cylinder as cyl
-    from .workloads.minkunet import ConvBlock, MinkUNet, ResBlock
+    Changes no parameter, buffer or state_dict entry; takes effect only in eval mode with grad mode off.
+
+    A module with a frozen path says so itself: `fold_records()` -> (the record dict its forward reads through `active`, the
+    modules it claims: the BatchNorms that stop launching and any child Sequential the plain-Sequential pass must leave alone),
+    or None where its layout is not the expected one."""
     unfreeze(model)
     claimed, folded = set(), 0
 
-    def claim(owner, rec, pairs):
+    def attach(owner, rec, claims):
         nonlocal folded
         owner.__dict__[_ATTR] = rec
-        for conv, bn in pairs:
-            claimed.add(id(bn))
-            folded += 1
+        claimed.update(id(c) for c in claims)
+        folded += sum(1 for c in claims if _is_norm(c))
 
     for m in model.modules():
-        if isinstance(m, ResBlock):
-            ds = m.downsample
-            has_ds = isinstance(ds, nn.Sequential) and len(ds) == 2 and _foldable(ds[0], ds[1])
-            if not (_foldable(m.net[0], m.net[1]) and _foldable(m.net[3], m.net[4]) and (has_ds or isinstance(ds, nn.Identity))):
-                continue
-            rec = {"a": FoldedConv(m.net[0], m.net[1], True), "b": FoldedConv(m.net[3], m.net[4], True),
-                   "ds": FoldedConv(ds[0], ds[1], False) if has_ds else None}
-            claim(m, rec, [(m.net[0], m.net[1]), (m.net[3], m.net[4])] + ([(ds[0], ds[1])] if has_ds else []))
-            claimed.update(id(s) for s in (m.net, ds))
-        elif isinstance(m, ConvBlock):
-            if _foldable(m.net[0], m.net[1]):
-                claim(m, {"net": FoldedConv(m.net[0], m.net[1], True)}, [(m.net[0], m.net[1])])
-                claimed.add(id(m.net))
-        elif isinstance(m, MinkUNet):
-            st = m.stem
-            if _foldable(st[0], st[1]) and _foldable(st[3], st[4]):
-                # SPVCNN and RPVNet (the same trunk, `point_branch`): the classifier reads the merged point features, not devoxelised
-                # voxel scores, and the BatchNorms of the point MLPs keep running (fused.point_merge / fused.range_point_merge with
-                # the running statistics): they end up in `skipped`
-                commuted = isinstance(m.classifier[0], FusedLinear) and not m.point_branch
-                rec = {"stem": [FoldedConv(st[0], st[1], True), FoldedConv(st[3], st[4], True)],
-                       "classifier": FoldedLinear(m.classifier[0]) if commuted else None}
-                claim(m, rec, [(st[0], st[1]), (st[3], st[4])])
-                claimed.add(id(st))
-    for m in model.modules():   # Cylinder3D (workloads.cylinder): conv -> LeakyReLU -> BatchNorm triples, the point MLPs
-        if isinstance(m, (cyl.ResContextBlock, cyl.UpBlock)):
-            rec = {}
-            for cname, aname, bname in m.TRIPLES:
-                conv, act, bn = getattr(m, cname), getattr(m, aname), getattr(m, bname)
-                slope = float(act.negative_slope) if isinstance(act, nn.LeakyReLU) else float("nan")
-                # the ABI reads a slope of 0 as "no activation": only finite slopes > 0 are claimed
-                if _foldable(conv, bn) and np.isfinite(slope) and slope > 0:
-                    rec[cname] = PostAffineConv(conv, bn, slope)
-            if isinstance(m, cyl.UpBlock) and isinstance(m.up_subm, spnn.Conv3d):
-                rec["up_subm"] = PostAffineConv(m.up_subm)   # + skip.F rides as the addend
-            if rec:
-                claim(m, rec, [(f.conv, f.bn) for f in rec.values() if f.bn is not None])
-        elif isinstance(m, cyl.CylinderTS):
-            pp, rec, pairs = m.PPmodel, {}, []
-            shape = [type(l) for l in pp] == [FusedBatchNorm, nn.Linear, FusedBatchNorm, nn.ReLU, nn.Linear, FusedBatchNorm, nn.ReLU,
-                                              nn.Linear, FusedBatchNorm, nn.ReLU, nn.Linear]
-            if shape and all(getattr(pp[i], "running_mean", None) is not None for i in (0, 2, 5, 8)):
-                rec["pp"] = [FoldedDense(pp[1], bn_in=pp[0], bn_out=pp[2]), FoldedDense(pp[4], bn_out=pp[5]), FoldedDense(pp[7], bn_out=pp[8])]
-                pairs += [(pp[1], pp[0]), (pp[1], pp[2]), (pp[4], pp[5]), (pp[7], pp[8])]
-            cd = getattr(m, "change_dim", None)
-            if cd is not None and len(cd) == 3 and isinstance(cd[0], nn.Linear) and _is_norm(cd[1]) and isinstance(cd[2], nn.LeakyReLU) \
-                    and getattr(cd[1], "running_mean", None) is not None:
-                rec["cd"] = FoldedDense(cd[0], bn_out=cd[1])
-                pairs.append((cd[0], cd[1]))
-            if rec:
-                claim(m, rec, pairs)
+        plan = m.fold_records() if callable(getattr(m, "fold_records", None)) else None
+        if plan:
+            attach(m, *plan)
     for m in model.modules():
         if isinstance(m, nn.Sequential) and type(m).forward is nn.Sequential.forward and id(m) not in claimed:
             groups = _groups(m)
             if groups:
-                claim(m, {"chain": [FoldedConv(c, b, r) for c, b, r in groups]}, [(c, b) for c, b, _ in groups])
+                attach(m, {"chain": [FoldedConv(c, b, r) for c, b, r in groups]}, [b for _, b, _ in groups])
                 m.__dict__["forward"] = _SequentialForward(m)
     skipped = [name for name, m in model.named_modules() if _is_norm(m) and id(m) not in claimed]
     return {"folded": folded, "skipped": skipped}
@@ -368,18 +330,30 @@ def point_predict(logits, batch, votes=None, hist=None, bad=None):
     votes (sum kept points, c) fp32: += softmax of every point's row, then decides (the reference's return_tta, summed);
     hist (c, c) int64: += confusion counts of labels in [0, c). -> (pred (sum kept points,) int64 on the device, host list of the
     (n_scenes + 1) offsets into it, bad flag (1,) int32 on the device: an inverse index pointed outside its scene)."""
-    be = native.backend()
     logits = logits.float().contiguous()
-    dev = logits.device
+    maps, labels, kept = _batch_maps(batch, logits.device)
+    pred, bad = native.backend().predict_points(logits, labels=labels if hist is not None else None, votes=votes, hist=hist, bad=bad, **maps)
+    return pred, kept, bad
+
+
+def scene_sizes(num_points):
+    """A batch's "num_points" (tensor, array, list or None) -> host list of ints, or None."""
+    if num_points is None:
+        return None
+    if isinstance(num_points, torch.Tensor):
+        num_points = num_points.cpu()   # host data in every loader of the reference; a device tensor costs a read-back
+    return [int(v) for v in np.asarray(num_points).reshape(-1)]
+
+
+def _batch_maps(batch, dev):
+    """The batch of `point_predict` as the tail kernel wants it -> ({"inverse", "point_offset", "row_offset"} on the device, the
+    labels of the kept points or None, the host offsets of the kept points or None where no `num_points` says them)."""
     inv = batch["inverse_map"]
     inverse = inv.F.to(dev).long().reshape(-1)
     labels = batch["targets_mapped"].F.to(dev).long().reshape(-1) if batch.get("targets_mapped") is not None else None
     n = inverse.numel()
-    num_points = batch.get("num_points")
+    num_points = scene_sizes(batch.get("num_points"))
     if num_points is not None:
-        if isinstance(num_points, torch.Tensor):
-            num_points = num_points.cpu()   # host data in every loader of the reference; a device tensor costs a read-back
-        num_points = [int(v) for v in np.asarray(num_points).reshape(-1)]
         ns = len(num_points)
     elif batch.get("offset") is not None:
         ns, num_points = len(batch["offset"]), None
@@ -406,9 +380,19 @@ def point_predict(logits, batch, votes=None, hist=None, bad=None):
         inverse = torch.where(inside, inverse[src], torch.full_like(src, -1))
         labels = labels[src] if labels is not None else None
         point_offset = kept_dev
-    pred, bad = be.predict_points(logits, inverse=inverse, point_offset=point_offset, row_offset=row_offset,
-                                  labels=labels if hist is not None else None, votes=votes, hist=hist, bad=bad)
-    return pred, kept, bad
+    return {"inverse": inverse, "point_offset": point_offset, "row_offset": row_offset}, labels, kept
+
+
+def predict_output(logits, batch, evaluator=None, votes=None):
+    """Eval logits -> what the models' `predict` returns: {"logits" fp32, "point_predict", "point_offset"}, through `evaluator`
+    (a SegEvaluator, which also counts) or the plain tail."""
+    logits = logits.float()
+    if evaluator is not None:
+        pred = evaluator.update(logits, batch, votes=votes)
+        offsets = evaluator.last_offsets
+    else:
+        pred, offsets, _ = point_predict(logits, batch, votes=votes)
+    return {"logits": logits, "point_predict": pred, "point_offset": offsets}
 
 
 class SegEvaluator:
@@ -430,15 +414,26 @@ class SegEvaluator:
                 self.hist = torch.zeros((self.num_class, self.num_class), dtype=torch.int64, device=device)
                 self.bad = torch.zeros(1, dtype=torch.int32, device=device)
 
-    def update(self, logits, batch, votes=None):
-        """hist[label][pred] += 1 over the batch's points (labels: batch["targets_mapped"]). -> pred (flat, on the device)."""
+    def tail(self, logits, labels, offsets, count=True, **maps):
+        """One launch of the prediction tail on this evaluator's behalf: native predict_points(logits, **maps), with
+        hist[label][pred] += 1 over `labels` when `count`, and the out-of-scene flag OR-ed into `bad`. labels None: nothing to count,
+        the evaluator's tensors are neither made nor passed. `offsets` (host) become `last_offsets`. -> pred (or None: want_pred)."""
         if logits.shape[1] != self.num_class:
             raise ValueError("openpcseg_amd: %d logit columns for a %d-class evaluator" % (logits.shape[1], self.num_class))
+        if labels is not None:
+            self._ensure(logits.device)
+        count = count and labels is not None
+        pred, _ = native.backend().predict_points(logits.float().contiguous(), labels=labels if count else None,
+                                                  hist=self.hist if count else None, bad=self.bad if labels is not None else None, **maps)
+        self.last_offsets = offsets
+        return pred
+
+    def update(self, logits, batch, votes=None):
+        """hist[label][pred] += 1 over the batch's points (labels: batch["targets_mapped"]). -> pred (flat, on the device)."""
         if batch.get("targets_mapped") is None:
             raise ValueError("openpcseg_amd: SegEvaluator.update needs batch['targets_mapped']")
-        self._ensure(logits.device)
-        pred, self.last_offsets, _ = point_predict(logits, batch, votes=votes, hist=self.hist, bad=self.bad)
-        return pred
+        maps, labels, kept = _batch_maps(batch, logits.device)
+        return self.tail(logits, labels, kept, votes=votes, **maps)
 
     def merge(self, other):
         """Add another evaluator's counts (what a multi-rank evaluation would all-reduce)."""
@@ -500,10 +495,8 @@ def predict_tta(model, raw, num_votes=10, evaluator=None, voxel_size=0.05, rng=n
     be = native.backend()
     dev = raw["points"].device
     labels = raw["labels"].long().contiguous() if evaluator is not None else None
-    if evaluator is not None:
-        evaluator._ensure(dev)
     point_offset = native._h2d(off, torch.int64, dev)
-    votes = pred = bad = None
+    votes = pred = bad = None   # bad: the flag of a run without evaluator, made by the first launch
     kept = []
     for v0 in range(0, nv, chunk):
         k = min(chunk, nv - v0)
@@ -511,22 +504,18 @@ def predict_tta(model, raw, num_votes=10, evaluator=None, voxel_size=0.05, rng=n
         with torch.inference_mode():
             logits = fn(batch["lidar"]).float().contiguous()
         if votes is None:
-            if evaluator is not None and logits.shape[1] != evaluator.num_class:
-                raise ValueError("openpcseg_amd: %d logit columns for a %d-class evaluator" % (logits.shape[1], evaluator.num_class))
             votes = torch.zeros((n, logits.shape[1]), dtype=torch.float32, device=dev)
-            bad = evaluator.bad if evaluator is not None else torch.zeros(1, dtype=torch.int32, device=dev)
         row_offset = _scene_offsets(batch["lidar"].C[:, -1], k * nf)
         inverse = batch["inverse_map"].F
         for j in range(k):
             last = v0 + j == nv - 1
-            count = last and evaluator is not None
-            pred, _ = be.predict_points(logits, inverse=inverse[j * n:(j + 1) * n], point_offset=point_offset,
-                                        row_offset=row_offset[j * nf:(j + 1) * nf + 1], labels=labels if count else None,
-                                        votes=votes, want_pred=last, hist=evaluator.hist if count else None, bad=bad)
+            maps = {"inverse": inverse[j * n:(j + 1) * n], "point_offset": point_offset, "row_offset": row_offset[j * nf:(j + 1) * nf + 1]}
+            if evaluator is not None:   # every vote's flag goes to the evaluator, the counts come from the last decision only
+                pred = evaluator.tail(logits, labels, off, count=last, votes=votes, want_pred=last, **maps)
+            else:
+                pred, bad = be.predict_points(logits, votes=votes, want_pred=last, bad=bad, **maps)
             if return_logits:
                 kept.append((logits, row_offset, j))
-    if evaluator is not None:
-        evaluator.last_offsets = off
     out = {"pred": pred, "votes": votes, "point_offset": off, "params": params}
     if return_logits:
         bounds = {id(r): r.cpu().tolist() for _, r, _ in kept}   # asked for explicitly: the only read-back, after everything is queued

@@ -67,6 +67,18 @@ def _cab(conv, bn, x, residual=None, want_skip=False, frozen=None):
     return (y, xs) if want_skip else y
 
 
+def _fold_triples(block):
+    """openpcseg_amd.freeze: {conv name: inference.PostAffineConv} over the block's TRIPLES (conv, LeakyReLU, BatchNorm names), the
+    record `_cab(frozen=)` reads. The ABI reads a slope of 0 as "no activation": only finite slopes > 0 are claimed."""
+    rec = {}
+    for cname, aname, bname in block.TRIPLES:
+        conv, act, bn = getattr(block, cname), getattr(block, aname), getattr(block, bname)
+        slope = float(act.negative_slope) if isinstance(act, nn.LeakyReLU) else float("nan")
+        if inference._foldable(conv, bn) and np.isfinite(slope) and slope > 0:
+            rec[cname] = inference.PostAffineConv(conv, bn, slope)
+    return rec
+
+
 def _conv(cin, cout, ks, stride=1, transposed=False, bias=False):
     return spnn.Conv3d(cin, cout, kernel_size=ks, stride=stride, bias=bias, transposed=transposed)
 
@@ -81,6 +93,10 @@ class ResContextBlock(nn.Module):       # cylinder_ts.py:88-155
         self.conv1_2, self.act1_2, self.bn0_2 = _conv(cout, cout, self.second), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
         self.conv2, self.act2, self.bn1 = _conv(cin, cout, self.second), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
         self.conv3, self.act3, self.bn2 = _conv(cout, cout, self.first), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
+
+    def fold_records(self):
+        rec = _fold_triples(self)
+        return (rec, [f.bn for f in rec.values()]) if rec else None
 
     def forward(self, x):
         fz = (inference.active(self) or {}).get
@@ -112,6 +128,12 @@ class UpBlock(nn.Module):               # cylinder_ts.py:253-334
         self.conv2, self.act2, self.bn2 = _conv(cout, cout, (3, 1, 3)), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
         self.conv3, self.act3, self.bn3 = _conv(cout, cout, 3), nn.LeakyReLU(), FusedBatchNorm(cout, sync=dist)
         self.up_subm = _conv(cout, cout, 3, stride=2 if height_pooling else (2, 2, 1), transposed=True)
+
+    def fold_records(self):
+        rec = _fold_triples(self)
+        if isinstance(self.up_subm, spnn.Conv3d):
+            rec["up_subm"] = inference.PostAffineConv(self.up_subm)   # + skip.F rides as the addend
+        return (rec, [f.bn for f in rec.values() if f.bn is not None]) if rec else None
 
     def forward(self, x, skip):
         fz = (inference.active(self) or {}).get
@@ -188,6 +210,22 @@ class CylinderTS(nn.Module):
         self._bn_layers = [m for m in self.modules() if isinstance(m, FusedBatchNorm)]
         for m in self._bn_layers:
             m.counted_by_parent = True
+
+    def fold_records(self):
+        """openpcseg_amd.freeze: {"pp": PPmodel's three Linear layers with the four BatchNorms around them folded in (`_point_mlp`),
+        "cd": change_dim's Linear with its BatchNorm (`forward`)}, each where the layout is the constructor's."""
+        pp, cd, dense = self.PPmodel, getattr(self, "change_dim", None), inference.FoldedDense
+        rec, norms = {}, []
+        tracked = lambda bn: getattr(bn, "running_mean", None) is not None
+        layout = [FusedBatchNorm, nn.Linear] + [FusedBatchNorm, nn.ReLU, nn.Linear] * 3
+        if [type(l) for l in pp] == layout and all(tracked(pp[i]) for i in (0, 2, 5, 8)):
+            rec["pp"] = [dense(pp[1], bn_in=pp[0], bn_out=pp[2]), dense(pp[4], bn_out=pp[5]), dense(pp[7], bn_out=pp[8])]
+            norms += [pp[0], pp[2], pp[5], pp[8]]
+        if cd is not None and len(cd) == 3 and isinstance(cd[0], nn.Linear) and inference._is_norm(cd[1]) and tracked(cd[1]) \
+                and isinstance(cd[2], nn.LeakyReLU):
+            rec["cd"] = dense(cd[0], bn_out=cd[1])
+            norms.append(cd[1])
+        return (rec, norms) if rec else None
 
     def _point_mlp(self, x):
         pp = self.PPmodel
@@ -266,9 +304,8 @@ class CylinderTS(nn.Module):
             rows = F.sphashquery(F.sphash(pc.int()), F.sphash(out["logit_coords"]))
             labels = batch["point_label"].long() if (evaluator is not None and batch.get("point_label") is not None) else None
             frame = pc[:, -1].long()
-            num_points = batch.get("num_points")
+            num_points = inference.scene_sizes(batch.get("num_points"))
             if num_points is not None:
-                num_points = [int(v) for v in np.asarray(num_points.cpu() if isinstance(num_points, torch.Tensor) else num_points).reshape(-1)]
                 counts = torch.bincount(frame, minlength=len(num_points))
                 if sum(num_points) != pc.shape[0]:   # `[:num_points[idx]]`: a frame keeps the head of its points
                     start = torch.cumsum(counts, 0) - counts
@@ -279,16 +316,14 @@ class CylinderTS(nn.Module):
             else:
                 offsets = [0] + torch.cumsum(torch.bincount(frame), 0).cpu().tolist()   # the one read-back of a batch without num_points
             be = native.backend()
-            if logits.is_cuda and hasattr(be, "predict_points"):
-                hist = bad = None
-                if labels is not None:
-                    evaluator._ensure(logits.device)
-                    hist, bad = evaluator.hist, evaluator.bad
-                pred, _ = be.predict_points(logits, inverse=rows.contiguous(), labels=labels if hist is not None else None, hist=hist, bad=bad)
-            else:
+            if not (logits.is_cuda and hasattr(be, "predict_points")):   # a backend without the tail kernel: the rows' arg-max on the host path
                 pred = logits[rows].argmax(1)
-            if evaluator is not None:
-                evaluator.last_offsets = offsets
+                if evaluator is not None:
+                    evaluator.last_offsets = offsets
+            elif evaluator is not None:
+                pred = evaluator.tail(logits, labels, offsets, inverse=rows.contiguous())
+            else:
+                pred, _ = be.predict_points(logits, inverse=rows.contiguous())
         return {"logits": logits, "logit_coords": out["logit_coords"], "point_predict": pred, "point_offset": offsets}
 
 

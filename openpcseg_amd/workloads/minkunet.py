@@ -78,6 +78,12 @@ class ConvBlock(nn.Module):
                                  _norm(cout, dist), spnn.ReLU(True))
         _link(self.net[0], self.net[1])
 
+    def fold_records(self):
+        """openpcseg_amd.freeze: {"net": conv + BatchNorm + ReLU as one launch}."""
+        conv, bn = self.net[0], self.net[1]
+        if inference._foldable(conv, bn):
+            return {"net": inference.FoldedConv(conv, bn, True)}, [bn, self.net]
+
     def forward(self, x, cat_with=None):
         folds = inference.active(self)
         if folds is not None:   # openpcseg_amd.freeze: conv + bias + ReLU in one launch; the decoder concat is torch.cat
@@ -98,6 +104,15 @@ class ResBlock(nn.Module):
         self.relu = spnn.ReLU(True)
         _link(self.net[0], self.net[1])
         _link(self.net[3], self.net[4])
+
+    def fold_records(self):
+        """openpcseg_amd.freeze: {"a", "b": the two conv + BatchNorm (+ ReLU) chains, "ds": the 1x1x1 downsample's or None}."""
+        net, ds = self.net, self.downsample
+        fold, ok = inference.FoldedConv, inference._foldable
+        has_ds = isinstance(ds, nn.Sequential) and len(ds) == 2 and ok(ds[0], ds[1])
+        if ok(net[0], net[1]) and ok(net[3], net[4]) and (has_ds or isinstance(ds, nn.Identity)):
+            rec = {"a": fold(net[0], net[1], True), "b": fold(net[3], net[4], True), "ds": fold(ds[0], ds[1], False) if has_ds else None}
+            return rec, [net[1], net[4], net, ds] + ([ds[1]] if has_ds else [])
 
     def forward(self, x):
         folds = inference.active(self)
@@ -155,6 +170,17 @@ class MinkUNet(nn.Module):
         self._bn_layers = [m for m in self.modules() if isinstance(m, FusedBatchNorm)]
         for m in self._bn_layers:
             m.counted_by_parent = True
+
+    def fold_records(self):
+        """openpcseg_amd.freeze: {"stem": its two chains, "classifier": the prepared voxel-side classifier or None}. With a point
+        branch (SPVCNN, RPVNet) the classifier reads the merged point features, not devoxelised voxel scores, and the BatchNorms
+        of the point MLPs keep running (fused.point_merge / fused.range_point_merge on the running statistics): `skipped`."""
+        st = self.stem
+        if inference._foldable(st[0], st[1]) and inference._foldable(st[3], st[4]):
+            commuted = isinstance(self.classifier[0], FusedLinear) and not self.point_branch
+            rec = {"stem": [inference.FoldedConv(st[0], st[1], True), inference.FoldedConv(st[3], st[4], True)],
+                   "classifier": inference.FoldedLinear(self.classifier[0]) if commuted else None}
+            return rec, [st[1], st[4], st]
 
     def _stem(self, x):
         folds = inference.active(self)
@@ -225,13 +251,7 @@ class MinkUNet(nn.Module):
         if self.training:
             raise RuntimeError("MinkUNet.predict is an evaluation pass: call model.eval() first")
         with torch.inference_mode():
-            logits = self.point_logits(batch["lidar"]).float()
-            if evaluator is not None:
-                pred = evaluator.update(logits, batch, votes=votes)
-                offsets = evaluator.last_offsets
-            else:
-                pred, offsets, _ = inference.point_predict(logits, batch, votes=votes)
-        return {"logits": logits, "point_predict": pred, "point_offset": offsets}
+            return inference.predict_output(self.point_logits(batch["lidar"]), batch, evaluator, votes)
 
     def forward(self, batch):
         logits = self.point_logits(batch["lidar"])

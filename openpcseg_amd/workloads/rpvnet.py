@@ -195,13 +195,7 @@ class RPVNet(MinkUNet):
         if self.training:
             raise RuntimeError("RPVNet.predict is an evaluation pass: call model.eval() first")
         with torch.inference_mode():
-            logits = self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"]).float()
-            if evaluator is not None:
-                pred = evaluator.update(logits, batch, votes=votes)
-                offsets = evaluator.last_offsets
-            else:
-                pred, offsets, _ = inference.point_predict(logits, batch, votes=votes)
-        return {"logits": logits, "point_predict": pred, "point_offset": offsets}
+            return inference.predict_output(self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"]), batch, evaluator, votes)
 
     def forward(self, batch):
         logits = self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"])

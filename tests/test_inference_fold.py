@@ -1,7 +1,8 @@
 """Inference mode (openpcseg_amd.freeze): BatchNorm folded into the convolutions, bias + residual + ReLU in the write-back.
 
 CPU part (-m "not gpu"): the fold arithmetic per block and for a whole small model on the pure-PyTorch backend against float64 /
-the oracle backend; freeze leaves state_dict alone, is ignored in train / grad mode, re-folds when a source tensor changes.
+the oracle backend; freeze leaves state_dict alone, is ignored in train / grad mode, re-folds when a source tensor changes
+(the one currency rule, held once per record class and source tensor).
 GPU part (-m gpu): every layer shape of the MinkUNet workload in one launch against the oracle's conv_fwd on the folded weights;
 model level: no BatchNorm call is left, fp32 / bf16 / fp16 errors of the frozen model are bounded by those of the unfrozen one.
 
@@ -252,6 +253,69 @@ def _records(module):
         for f in (v if isinstance(v, list) else [v]):
             if hasattr(f, "folds"):
                 yield f
+
+
+def _tiny_records():
+    """One record of each class on 8 -> 16 channels, with the call that uses it."""
+    from openpcseg_amd import inference, linear
+    from openpcseg_amd import modules as spnn
+    from openpcseg_amd.fused import FusedBatchNorm
+    conv = lambda: spnn.Conv3d(8, 16, 3, bias=True)
+    g = torch.Generator().manual_seed(1)
+    xf, idx, wts = torch.randn(30, 8, generator=g), torch.randint(0, 30, (50, 8), generator=g).int(), torch.rand(50, 8, generator=g)
+    folded = lambda rec: rec.folded()
+    return [(inference.FoldedConv(conv(), FusedBatchNorm(16), True), folded),
+            (inference.PostAffineConv(conv(), FusedBatchNorm(16), 0.01), folded),
+            (inference.FoldedDense(torch.nn.Linear(8, 16), bn_in=FusedBatchNorm(8), bn_out=FusedBatchNorm(16)), folded),
+            (inference.FoldedLinear(linear.FusedLinear(8, 16)), lambda rec: rec.devoxelized_part(0, xf, idx, wts, cache={}))]
+
+
+def _fold_token(rec):
+    """What changes exactly when the record folded: its counter, or for FoldedLinear (not counted) a mark in its `parts` memo."""
+    return rec.folds if hasattr(rec, "folds") else rec.parts.setdefault("mark", object())
+
+
+def test_one_currency_rule_for_every_record_class(cpu_be):
+    """FoldedConv, PostAffineConv, FoldedDense, FoldedLinear, and every source tensor each of them names: an in-place change and a
+    new storage re-fold exactly once at the next use; sources without a version counter fold on every use; a re-fold empties
+    `prepared` (FoldedLinear: drops `parts`)."""
+    seen = 0
+    for rec, use in _tiny_records():
+        sources = [t for t in rec._sources() if t is not None]
+        assert len(sources) == {"FoldedConv": 6, "PostAffineConv": 6, "FoldedDense": 10, "FoldedLinear": 1}[type(rec).__name__]
+        assert hasattr(rec, "folds") == (type(rec).__name__ != "FoldedLinear")
+        use(rec)
+        for t in sources:
+            for change in ("in place", "storage"):
+                before = _fold_token(rec)
+                use(rec)
+                assert _fold_token(rec) is before or _fold_token(rec) == before   # current: nothing folds
+                if hasattr(rec, "prepared"):
+                    rec.prepared["copy"] = "stale"
+                if change == "in place":
+                    with torch.no_grad():
+                        t.mul_(1.5)
+                else:
+                    t.data = t.data.clone()
+                use(rec)
+                after = _fold_token(rec)
+                assert (after == before + 1) if hasattr(rec, "folds") else (after is not before), (type(rec).__name__, change)
+                assert getattr(rec, "prepared", {}) == {}
+                use(rec)
+                assert _fold_token(rec) is after or _fold_token(rec) == after   # and not again
+                seen += 1
+    assert seen == 2 * (6 + 6 + 10 + 1)
+    with torch.inference_mode():
+        made = _tiny_records()
+    for rec, use in made:   # inference tensors track no version: every use folds
+        tokens = []
+        for _ in range(3):
+            use(rec)
+            tokens.append(_fold_token(rec))
+        if hasattr(rec, "folds"):
+            assert tokens == [1, 2, 3], type(rec).__name__
+        else:
+            assert tokens[0] is not tokens[1] and tokens[1] is not tokens[2]
 
 
 def test_freeze_plain_sequential_and_unknown_modules(cpu_be):
