@@ -689,6 +689,25 @@ int pcs_voxel_label_vote(const int64_t *inverse, const int64_t *labels, int64_t 
 int pcs_rows_argmax_gather_f32(const float *logits, int64_t m, int32_t c, const int64_t *inverse, int64_t n,
                                int64_t *out, void *stream);
 
+/* ---- the cylinder dataset's transform of a raw batch (csrc/cylscan.hip; added under ABI v12, additive) ------------------
+ * Replaces, for scans resident in HBM, what R:pcseg/data/dataset/semantickitti/semantickitti_cylinder.py:104-160 does per frame
+ * and per vote in the dataloader workers (waymo_cylinder.py is the same code): aug_points (:115-142, R:tools/utils/common/
+ * seg_utils.py:43-100) stored back as float32, cart2polar (:144), the degrees (:145), the partition (:146-153) and the point
+ * features (:158-160); the ten votes of :92-99 from ONE read of the scan. One launch, no workspace, no host read.
+ *   points, frame_offsets, params, num_votes: as pcs_scan_transform (params vote-major, row v * num_frames + f); 3 <= c <=
+ *   PCS_SCAN_MAX_COLUMNS, 1 <= num_votes <= PCS_SCAN_MAX_VOTES, 1 <= num_frames <= 65535. space_min3 / space_max3 / grid3:
+ *   HOST values as pcs_cylinder_partition_f32 (grid >= 2, max > min, else PCS_EINVAL).
+ * Per row i of frame f and vote v, output row v * n + i:
+ *   (x', y', z') = the affine map of pcs_scan_transform: float64, that order, no multiply-add fused, one rounding to float32;
+ *   [rho, phi in degrees, z'], the cell and its centre = the arithmetic of pcs_cylinder_partition_f32 applied to (x', y', z');
+ *   feat (num_votes * n, 8 + c - 3) fp32 = [centre (3), rho, phi, z', x', y', the other columns unchanged];
+ *   coord (num_votes * n, 3) int32 = the cell; scenes (num_votes * n) int64 = v * num_frames + f.
+ * Offsets outside [0, n] are clamped: nothing outside the num_votes * n rows is addressed; an empty frame writes nothing;
+ * n == 0 launches nothing. */
+int pcs_cylinder_scan_batch_f32(const float *points, int64_t n, int32_t c, const int64_t *frame_offsets, int32_t num_frames,
+                                const double *params, int32_t num_votes, const double *space_min3, const double *space_max3,
+                                const int32_t *grid3, float *feat, int32_t *coord, int64_t *scenes, void *stream);
+
 /* ---- prediction tail of an evaluation pass (csrc/predict.hip; added under ABI v12, additive) --------------------------
  * The reference's eval tail (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:436-455, scoring R:infer.py:35-52) for a
  * whole batch in one launch, no host synchronisation. logits: (m, c) rows of the batch, c <= 64. For point i of scene b
@@ -761,6 +780,10 @@ void pcs_debug_convh_ws(int32_t mode, int32_t ru, int32_t rs);
 void pcs_debug_conv_plan(int32_t kind, int32_t dtype, int32_t cin, int32_t cout, int32_t K, int32_t tile_rows, int32_t flags,
                          int32_t out[12]);
 void pcs_debug_wgrad_interleave(int32_t mode);
+/* store form of pcs_cylinder_scan_batch_f32 (tools/cylinder_input_bench.py): -1 = environment (PCS_CYLSCAN_STORE, default 2),
+ * 0 = features and cells staged in LDS and written as contiguous ranges, 1 = every lane stores its own rows, 2 = features staged,
+ * cells direct */
+void pcs_debug_cylscan_store(int32_t form);
 
 #ifdef __cplusplus
 }

@@ -15,15 +15,12 @@
 // of a cell face may land in the neighbouring cell (tests/test_cylinder_frontend.py bounds exactly that).
 #include <math.h>
 
+#include "cyl_cell.h"
 #include "pcs_common.h"
 
 using namespace pcs;
 
 namespace {
-
-struct CylCfg {
-  double lo[3], hi[3], interval[3];
-};
 
 __global__ void __launch_bounds__(256) cyl_partition_kernel(const float *__restrict__ pts, int64_t n, int stride, CylCfg cfg,
                                                             float *__restrict__ polar, int32_t *__restrict__ coord,
@@ -32,23 +29,9 @@ __global__ void __launch_bounds__(256) cyl_partition_kernel(const float *__restr
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float *p = pts + i * stride;
     const float x = p[0], y = p[1], z = p[2];
-    // cart2polar (:19-22), float32 like NumPy on a float32 scan
-    const float rho = sqrtf(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)));
-    const float phi = (float)atan2((double)y, (double)x);
-    // xyz_pol[:, 1] / np.pi * 180. (:145): float32 array with Python scalars -> float32 arithmetic
-    const float deg = __fmul_rn(__fdiv_rn(phi, 3.14159265358979323846f), 180.0f);
-    const float pol[3] = {rho, deg, z};
+    float pol[3], centre[3];
     int idx[3];
-    float centre[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      // np.clip(float32, int64 bounds) -> float64; (c - min) / intervals; floor; astype(int) (:153)
-      double c = (double)pol[d];
-      c = c < cfg.lo[d] ? cfg.lo[d] : (c > cfg.hi[d] ? cfg.hi[d] : c);
-      idx[d] = (int)floor((c - cfg.lo[d]) / cfg.interval[d]);
-      // (point_coord.astype(float32) + 0.5) * intervals + min_bound (:157), float64, stored as float32 (:165)
-      centre[d] = (float)(((double)((float)idx[d] + 0.5f)) * cfg.interval[d] + cfg.lo[d]);
-    }
+    cyl_cell(x, y, z, cfg, pol, idx, centre);   // cyl_cell.h: the one definition of the partition arithmetic
     if (polar) { polar[i * 3 + 0] = pol[0]; polar[i * 3 + 1] = pol[1]; polar[i * 3 + 2] = pol[2]; }
     coord[i * 3 + 0] = idx[0]; coord[i * 3 + 1] = idx[1]; coord[i * 3 + 2] = idx[2];
     if (feat) {  // [cell centre (3), polar (3), x, y, extras...] (:159)
@@ -121,12 +104,7 @@ extern "C" int pcs_cylinder_partition_f32(const float *points, int64_t n, int32_
                                           float *feat, void *stream) {
   if (n < 0 || row_stride < 3 || !space_min3 || !space_max3 || !grid3) { set_error("pcs_cylinder_partition_f32: bad args"); return PCS_EINVAL; }
   CylCfg cfg;
-  for (int d = 0; d < 3; ++d) {
-    if (grid3[d] < 2 || !(space_max3[d] > space_min3[d])) { set_error("pcs_cylinder_partition_f32: grid must be >= 2 and max > min"); return PCS_EINVAL; }
-    cfg.lo[d] = space_min3[d];
-    cfg.hi[d] = space_max3[d];
-    cfg.interval[d] = (space_max3[d] - space_min3[d]) / (double)(grid3[d] - 1);  // crop_range / (grid - 1) (:151)
-  }
+  if (!cyl_cfg(space_min3, space_max3, grid3, cfg)) { set_error("pcs_cylinder_partition_f32: grid must be >= 2 and max > min"); return PCS_EINVAL; }
   if (n == 0) return PCS_OK;
   if (!points || !coord) { set_error("pcs_cylinder_partition_f32: null pointer"); return PCS_EINVAL; }
   hipLaunchKernelGGL(cyl_partition_kernel, dim3(stream_grid(n, 256)), dim3(256), 0, as_stream(stream), points, n, row_stride,

@@ -19,32 +19,18 @@
 #include <math.h>
 
 #include "pcs_common.h"
+#include "scan_affine.h"
 
 using namespace pcs;
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kScanBlock;
 constexpr int kMaxExtra = PCS_SCAN_MAX_COLUMNS - 3;
 
 __device__ __forceinline__ int wave_min(int v) {
   for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
   return v;
-}
-
-// One row under one parameter row. Contraction is switched off for this body: a fused multiply-add skips the rounding of the
-// product that NumPy's float64 arithmetic performs, and the float32 result can then differ in its last bit.
-__device__ __forceinline__ void affine_row(float x, float y, float z, const double *__restrict__ p, float &fx, float &fy, float &fz) {
-#pragma clang fp contract(off)
-  const double c = p[0], s = p[1], scale = p[2];
-  const double xd = (double)x, yd = (double)y;
-  const double a = xd * c, b = yd * (-s);
-  const double d = xd * s, e = yd * c;
-  double X = a + b, Y = d + e, Z = (double)z;
-  X = X * scale; Y = Y * scale; Z = Z * scale;
-  X = X * p[3]; Y = Y * p[4];
-  X = X + p[5]; Y = Y + p[6]; Z = Z + p[7];
-  fx = (float)X; fy = (float)Y; fz = (float)Z;
 }
 
 __global__ void __launch_bounds__(kBlock) scan_fill_kernel(int32_t *__restrict__ dst, int count, int32_t value) {
@@ -181,14 +167,6 @@ __global__ void __launch_bounds__(kBlock) scan_shift_kernel(int32_t *__restrict_
   }
 }
 
-// workgroups along a frame: `chip` workgroups shared among the other grid axes, never more than the rows can use
-int frame_grid(int64_t n, int64_t per_row, int64_t others, int64_t chip) {
-  int64_t g = chip / others;
-  const int64_t most = ceil_div(n * per_row, kBlock);
-  if (g > most) g = most;
-  return (int)(g < 1 ? 1 : g);
-}
-
 // the transform's: 256 CUs x 4 workgroups of the light instances (<= 4 votes), x 2 of the heavy ones (2 waves per SIMD fit)
 int transform_grid(int64_t n, int num_frames, int num_votes) { return frame_grid(n, 1, num_frames, num_votes <= 4 ? 1024 : 512); }
 
@@ -202,10 +180,6 @@ void launch_transform(bool row16, dim3 grid, hipStream_t st, const float *pts, i
   else
     hipLaunchKernelGGL((scan_transform_kernel<VB, false>), grid, dim3(kBlock), 0, st, pts, n, C, fo, F, params, V, voxel, feats, coords,
                        mins, counters, partials);
-}
-
-bool scan_sizes_ok(int64_t n, int32_t num_frames, int32_t num_votes) {
-  return n >= 0 && num_votes >= 1 && num_votes <= PCS_SCAN_MAX_VOTES && num_frames >= 1 && num_frames <= 65535;
 }
 
 }  // namespace

@@ -6,6 +6,8 @@ Same names, argument meaning and outputs as
   voxelize_with_label   R:...semantickitti_cylinder.py:31-45
   cylinder_sample       the body of get_single_sample, R:...semantickitti_cylinder.py:144-173 (after augmentation)
   map_voxel_predictions R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:441-453 (`out[scene][inv].argmax(1)`)
+  device_batch          get_single_sample incl. its augmentation / TTA branch + collate_batch(_tta), R:...semantickitti_cylinder.py:92-265,
+                        for every frame and vote of a raw batch at once (pcs_cylinder_scan_batch_f32)
 Device tensors in, device tensors out (pcs_cylinder_partition_f32, pcs_quantize_*, pcs_voxel_label_vote,
 pcs_rows_argmax_gather_f32); there is no CPU path -- NumPy callers keep the reference's own dataset code.
 
@@ -60,6 +62,63 @@ def cylinder_sample(point, point_label, cylinder_space_min, cylinder_space_max, 
     return {"point_feature": point_feature, "point_coord": coord.float(), "point_label": point_label.reshape(-1).long(),
             "voxel_feature": voxel_feature, "voxel_coord": voxel_coord.long(), "voxel_label": voxel_label,
             "inverse_map": inverse_map, "num_points": torch.tensor([point.shape[0]], device=point.device)}
+
+
+def device_batch(raw, space_min, space_max, grid_size, num_classes=20, params=None, votes=1, labels=True, check=True):
+    """The cylinder dataset's transform + collate of a raw batch resident in HBM, for `votes` augmented
+    copies of every frame from one read of the scans: get_single_sample (R:...semantickitti_cylinder.py:104-174) of every frame
+    and vote, then collate_batch / collate_batch_tta (:176-265). raw: the dict `workloads.synthetic.make_raw_batch` returns, its
+    tensors on the device; params: host (votes * num_frames, 8) float64, vote-major (transform.draw_train_params / tta_params with
+    the config's scale_range -- the cylinder configs default to (0.95, 1.05)), None = the identity.
+    -> the dict `workloads.cylinder.cylinder_batch` makes of per-frame `cylinder_sample`s, over votes * num_frames scenes (scene
+    v * num_frames + f = vote v of frame f): point_feature, point_coord (float32, scene last), point_label, voxel_feature,
+    voxel_coord (int64, scene last; per scene in sparse_quantize's order, which CylinderTS._refine_rows pairs rows by),
+    voxel_label, inverse_map (per scene), offset (int32, on the device), num_points (host). labels=False leaves the label vote
+    and "voxel_label" out (an evaluation needs neither).
+    One launch for the transform, one dedup and one label vote for the whole batch. Host reads: the voxel count (inside
+    sparse_quantize_frames) and, with labels and check, the one label-range flag (IndexError as voxelize_with_label raises it);
+    check=False hands the device flag back under "bad" instead."""
+    import numpy as np
+
+    from .hostdata import sparse_quantize_frames
+    from .transform import identity_params
+    pts = raw["points"]
+    if not (isinstance(pts, torch.Tensor) and pts.is_cuda):
+        raise RuntimeError("openpcseg_amd: `points` must be a HIP device tensor (got %s); the MI355X backend has no CPU path -- "
+                           "the reference's dataset code is the host form" % (getattr(pts, "device", type(pts)),))
+    off = [int(o) for o in raw["offsets"]]
+    nf, v, n = int(raw["num_frames"]), int(votes), pts.shape[0]
+    if len(off) != nf + 1:
+        raise ValueError("openpcseg_amd: %d frame boundaries for %d frames" % (len(off), nf))
+    if any(off[i + 1] <= off[i] for i in range(nf)):
+        raise ValueError("openpcseg_amd: an empty frame has no voxels to collate (the reference fails on it too)")
+    if off[0] != 0 or off[-1] != n:
+        raise ValueError("openpcseg_amd: the frame boundaries must cover the %d rows of `points`" % n)
+    if params is None:
+        params = identity_params(v * nf)
+    be = native.backend()
+    feat, coord, scenes = be.cylinder_scan_batch(pts, off, params, v, space_min, space_max, grid_size)
+    vox, index, inverse = sparse_quantize_frames(coord, scenes, v * nf)
+    counts = torch.zeros(v * nf + 1, dtype=torch.int64, device=pts.device)
+    counts.scatter_add_(0, vox[:, 3].long() + 1, torch.ones(vox.shape[0], dtype=torch.int64, device=pts.device))
+    first = torch.cumsum(counts, 0)   # first voxel row of every scene, then the total
+    out = {"point_feature": feat, "point_coord": torch.cat([coord, scenes.int()[:, None]], dim=1).float(),
+           # the cell centre of a voxel IS the cell centre of its representative point: its point_feature row (:155-157)
+           "voxel_feature": feat.index_select(0, index), "voxel_coord": vox.long(), "inverse_map": inverse - first[scenes],
+           "offset": first[1:].int(), "num_points": np.array([off[f + 1] - off[f] for _ in range(v) for f in range(nf)])}
+    point_label = raw.get("labels")
+    if point_label is not None:
+        point_label = point_label.reshape(-1).long()
+        out["point_label"] = point_label if v == 1 else point_label.repeat(v)   # row v * n + i carries the label of point i
+    if labels:
+        if point_label is None:
+            raise ValueError("openpcseg_amd: cylinder.device_batch(labels=True) needs raw['labels']")
+        out["voxel_label"], bad = be.voxel_label_vote(inverse, out["point_label"], vox.shape[0], num_classes, IGNORE_VOTE_LABEL)
+        if not check:
+            out["bad"] = bad
+        elif int(bad.item()):
+            raise IndexError("cylinder.device_batch: a point label is outside [0, %d) (and is not %d)" % (num_classes, IGNORE_VOTE_LABEL))
+    return out
 
 
 def map_voxel_predictions(out, inverse_map, num_points=None):

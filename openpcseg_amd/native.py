@@ -130,6 +130,7 @@ SIGNATURES = {
     "pcs_conv_wgrad_h": (c_int32, [_P, c_int32, _P, c_int32, _P, c_int32, _P, _P, c_int32, _P, _P, c_size_t, c_int32, _P]),
     "pcs_unique_emit": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
     "pcs_cylinder_partition_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "pcs_cylinder_scan_batch_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "pcs_voxel_label_vote": (c_int32, [_P, _P, c_int64, c_int64, c_int32, c_int64, _P, _P, _P, _P]),
     "pcs_rows_argmax_gather_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "pcs_predict_points_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
@@ -141,6 +142,7 @@ SIGNATURES = {
     "pcs_debug_wgrad_interleave": (None, [c_int32]),
     "pcs_debug_conv_plan": (None, [c_int32] * 7 + [_P]),             # host only: the route's plan for a call (tests read it)
     "pcs_debug_pointvoxel_h_inflight": (None, [c_int32]),
+    "pcs_debug_cylscan_store": (None, [c_int32]),
 }
 
 class _WeightJob(ctypes.Structure):   # pcs_weight_job of include/pcseg_hip.h
@@ -1316,24 +1318,29 @@ class HipBackend:
     # -- device-side dataset transform (csrc/scantransform.hip) -------------------------------------------
     MAX_VOTES, MAX_COLUMNS = 16, 8   # PCS_SCAN_MAX_VOTES, PCS_SCAN_MAX_COLUMNS of include/pcseg_hip.h
 
+    def _scan_args(self, what, points, offsets, params, votes):
+        """What the entries over a raw batch share -> (points, n, c, num_frames, votes, params on the device, frame boundaries on
+        the device): the parameter table and the boundaries travel in ONE pinned asynchronous copy (the table's bit patterns as int64)."""
+        import numpy as np
+        points = _dev(points, "points", torch.float32)
+        if points.dim() != 2:
+            raise ValueError("openpcseg_amd: %s wants (n, C) points, got %s" % (what, tuple(points.shape)))
+        n, c = points.shape
+        nf, v = len(offsets) - 1, int(votes)
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if nf < 1 or params.shape != (v * nf, 8):
+            raise ValueError("openpcseg_amd: %s wants (votes * num_frames, 8) parameters, got %s for %d votes of %d frames"
+                             % (what, params.shape, v, nf))
+        table = _h2d(params.reshape(-1).view(np.int64).tolist() + [int(o) for o in offsets], torch.int64, points.device)
+        return points, n, c, nf, v, table[:v * nf * 8].view(torch.float64), table[v * nf * 8:]
+
     def scan_transform(self, points, offsets, params, votes, voxel_size):
         """points (n, C) fp32 on the device, frame after frame; offsets: the HOST list of num_frames + 1 frame boundaries; params:
         host (votes * num_frames, 8) float64, vote-major (transform.py) -> (feats (votes * n, C) fp32, coords (votes * n, 3) int32
         -- not yet shifted --, mins (votes * num_frames, 3) int32, the frame boundaries as an int64 device tensor). The parameter
         table and the boundaries travel in ONE pinned asynchronous copy (the table's bit patterns as int64); nothing is read back."""
-        import numpy as np
-        points = _dev(points, "points", torch.float32)
-        if points.dim() != 2:
-            raise ValueError("openpcseg_amd: scan_transform wants (n, C) points, got %s" % (tuple(points.shape),))
-        n, c = points.shape
-        nf, v = len(offsets) - 1, int(votes)
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        if nf < 1 or params.shape != (v * nf, 8):
-            raise ValueError("openpcseg_amd: scan_transform wants (votes * num_frames, 8) parameters, got %s for %d votes of %d frames"
-                             % (params.shape, v, nf))
+        points, n, c, nf, v, par, off = self._scan_args("scan_transform", points, offsets, params, votes)
         dev = points.device
-        table = _h2d(params.reshape(-1).view(np.int64).tolist() + [int(o) for o in offsets], torch.int64, dev)
-        par, off = table[:v * nf * 8].view(torch.float64), table[v * nf * 8:]
         feats = torch.empty((v * n, c), dtype=torch.float32, device=dev)
         coords = torch.empty((v * n, 3), dtype=torch.int32, device=dev)
         mins = torch.empty((v * nf, 3), dtype=torch.int32, device=dev)
@@ -1393,6 +1400,22 @@ class HipBackend:
                                                    _ptr(feat), _stream()),
                "pcs_cylinder_partition_f32")
         return polar, coord, feat
+
+    def cylinder_scan_batch(self, points, offsets, params, votes, space_min, space_max, grid_size):
+        """The cylinder dataset's transform of a raw batch in one launch (csrc/cylscan.hip): points (n, C) fp32 on the device, frame
+        after frame; offsets, params, votes as scan_transform -> (feat (votes * n, 8 + C - 3) fp32, coord (votes * n, 3) int32,
+        scenes (votes * n,) int64 = vote * num_frames + frame). Nothing is read back."""
+        points, n, c, nf, v, par, off = self._scan_args("cylinder_scan_batch", points, offsets, params, votes)
+        lo = (c_double * 3)(*[float(x) for x in space_min])
+        hi = (c_double * 3)(*[float(x) for x in space_max])
+        grid = (c_int32 * 3)(*[int(x) for x in grid_size])
+        dev = points.device
+        feat = torch.empty((v * n, 8 + c - 3), dtype=torch.float32, device=dev)
+        coord = torch.empty((v * n, 3), dtype=torch.int32, device=dev)
+        scenes = torch.empty(v * n, dtype=torch.int64, device=dev)
+        _check(self.lib.pcs_cylinder_scan_batch_f32(_ptr(points), n, c, _ptr(off), nf, _ptr(par), v, lo, hi, grid, _ptr(feat), _ptr(coord),
+                                                    _ptr(scenes), _stream()), "pcs_cylinder_scan_batch_f32")
+        return feat, coord, scenes
 
     def voxel_label_vote(self, inverse, labels, m, num_classes, ignore_label):
         """-> (voxel_labels (m,) int64, bad (1,) int32 device flag: a counted label was out of range)."""
