@@ -708,6 +708,35 @@ int pcs_cylinder_scan_batch_f32(const float *points, int64_t n, int32_t c, const
                                 const double *params, int32_t num_votes, const double *space_min3, const double *space_max3,
                                 const int32_t *grid3, float *feat, int32_t *coord, int64_t *scenes, void *stream);
 
+/* ---- the fusion dataset's range view of a collated batch (csrc/rangeproj.hip; added under ABI v12, additive) -------------
+ * Replaces, for voxel rows resident in HBM, get_range_image of R:pcseg/data/dataset/semantickitti/semantickitti_fusion.py:64-114
+ * (waymo_fusion.py is the same code) and the range_pxpy table of its collates (:198-245): the projection of every scene's
+ * deduplicated voxel rows onto an H x W image with a per-scene azimuthal cut, "the last row that hits a pixel wins".
+ *   feats (n, c) fp32, c >= 5: [x, y, z, reflectivity, ring, ...]; scenes (n,) int32: the scene of every row, rows of a scene
+ *   contiguous and in the collate's order; cuts32 (S,) fp32 ON THE DEVICE: float32((u - 0.5) * 2 pi) of the scene's
+ *   np.random.rand() value u, rounded once on the host; S scenes, H >= 2, W >= 2, S * H * W < 2^31, 0 <= n < 2^31.
+ * pcs_range_project_f32, per row i (all float32, no multiply-add fused, each operation rounded on its own):
+ *   yaw = float32(atan2(double(y), double(-x))) + cuts32[scene];  yaw = remainder(yaw, float32(2 pi)) - float32(pi)  (NumPy's
+ *   remainder: fmodf, + float32(2 pi) when negative);  ix = rint(0.5 * (yaw / float32(pi) + 1) * (W - 1)), iy = rint(ring),
+ *   ties to even;  pxpy[i] = (float(scene), float(2 (ix / (W - 1) - 0.5)), float(2 (iy / (H - 1) - 0.5))), the last two in
+ *   float64 from the rounded integers;  winner[scene][iy][ix] = max(winner[..], i)  (atomic; independent of the order the
+ *   atomics retire in, and equal to the reference's last write because a scene's rows ascend).
+ *   winner (S * H * W) int32 is set to -1 and bad[0] to 0 by the entry itself (two hipMemsetAsync on `stream`). A row whose
+ *   x, y or ring is not finite, whose iy is outside [0, H - 1] or whose scene is outside [0, S) sets bad[0] = 1, writes its
+ *   pxpy row and touches no pixel (the reference asserts on a ring > H - 1 and wraps a negative one).
+ * pcs_range_image_fill_f32: winner -> image (S, 5, H, W) fp32, pixel-major. A pixel whose winner is w in [0, n):
+ *   channel 0 = float32(25 (double(1.0f / depth) - 0.4)), depth = sqrtf((x x + y y) + z z) in float32;
+ *   channel 1 = float32(20 (double(reflectivity) - 0.5));  channels 2..4 = x, y, z.  Any other pixel: (-10, -10, 0, 0, 0).
+ *   Four pixels per lane and 16-byte stores where W % 4 == 0 and winner / image are 16-byte aligned, one pixel per lane otherwise.
+ * pcs_range_project_ws_bytes: the bytes of `winner`, or -1 on sizes the entries refuse. Sizes are checked before any pointer:
+ * bad sizes give PCS_EINVAL also with null pointers; n == 0 with valid sizes projects nothing (the winner is still cleared
+ * when it is given). Nothing allocates, nothing is read back. */
+int64_t pcs_range_project_ws_bytes(int32_t num_scenes, int32_t H, int32_t W);
+int pcs_range_project_f32(const float *feats, int64_t n, int32_t c, const int32_t *scenes, const float *cuts32, int32_t num_scenes,
+                          int32_t H, int32_t W, int32_t *winner, float *pxpy, int32_t *bad, void *stream);
+int pcs_range_image_fill_f32(const int32_t *winner, const float *feats, int64_t n, int32_t c, int32_t num_scenes, int32_t H,
+                             int32_t W, float *image, void *stream);
+
 /* ---- prediction tail of an evaluation pass (csrc/predict.hip; added under ABI v12, additive) --------------------------
  * The reference's eval tail (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:436-455, scoring R:infer.py:35-52) for a
  * whole batch in one launch, no host synchronisation. logits: (m, c) rows of the batch, c <= 64. For point i of scene b

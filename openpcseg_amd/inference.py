@@ -487,11 +487,24 @@ def predict_tta(model, raw, num_votes=10, evaluator=None, voxel_size=0.05, rng=n
     if not callable(fn) or isinstance(fn, nn.Module):
         raise TypeError("openpcseg_amd: predict_tta needs a model with a point_logits(lidar) method (MinkUNet, SPVCNN)")
     nf = int(raw["num_frames"])
+    params = transform.tta_params(nf, int(num_votes), scale_range=scale_range, rng=rng)
+    return vote_loop(raw, num_votes, vote_chunk, evaluator, return_logits,
+                     lambda v0, k: transform.device_batch(raw, voxel_size, params[v0 * nf:(v0 + k) * nf], votes=k, eval_maps=True),
+                     lambda batch: fn(batch["lidar"]), {"params": params})
+
+
+def vote_loop(raw, num_votes, vote_chunk, evaluator, return_logits, batch_of, logits_of, drawn):
+    """The voted evaluation `predict_tta` and `RPVNet.predict_tta` share: batch_of(v0, k) -> the device batch of votes v0 .. v0 + k
+    (a `transform.device_batch(..., eval_maps=True)` dict: scene j * num_frames + f = vote v0 + j of frame f), logits_of(batch) ->
+    the eval logits over batch["lidar"]'s rows (called under inference_mode). Per vote one launch of the prediction tail adds the
+    softmax of every point's row into one (n, num_class) tensor; the decision and the evaluator's counts come from the last vote's
+    launch only. drawn: the tables the caller drew, handed back. -> {"pred", "votes", "point_offset", **drawn} and with
+    return_logits "logits" (see predict_tta)."""
+    nf = int(raw["num_frames"])
     off = [int(o) for o in raw["offsets"]]
     n = off[-1]
     nv = int(num_votes)
     chunk = nv if vote_chunk is None else max(1, min(int(vote_chunk), nv))
-    params = transform.tta_params(nf, nv, scale_range=scale_range, rng=rng)
     be = native.backend()
     dev = raw["points"].device
     labels = raw["labels"].long().contiguous() if evaluator is not None else None
@@ -500,9 +513,9 @@ def predict_tta(model, raw, num_votes=10, evaluator=None, voxel_size=0.05, rng=n
     kept = []
     for v0 in range(0, nv, chunk):
         k = min(chunk, nv - v0)
-        batch = transform.device_batch(raw, voxel_size, params[v0 * nf:(v0 + k) * nf], votes=k, eval_maps=True)
+        batch = batch_of(v0, k)
         with torch.inference_mode():
-            logits = fn(batch["lidar"]).float().contiguous()
+            logits = logits_of(batch).float().contiguous()
         if votes is None:
             votes = torch.zeros((n, logits.shape[1]), dtype=torch.float32, device=dev)
         row_offset = _scene_offsets(batch["lidar"].C[:, -1], k * nf)
@@ -516,7 +529,7 @@ def predict_tta(model, raw, num_votes=10, evaluator=None, voxel_size=0.05, rng=n
                 pred, bad = be.predict_points(logits, votes=votes, want_pred=last, bad=bad, **maps)
             if return_logits:
                 kept.append((logits, row_offset, j))
-    out = {"pred": pred, "votes": votes, "point_offset": off, "params": params}
+    out = {"pred": pred, "votes": votes, "point_offset": off, **drawn}
     if return_logits:
         bounds = {id(r): r.cpu().tolist() for _, r, _ in kept}   # asked for explicitly: the only read-back, after everything is queued
         out["logits"] = [lg[bounds[id(r)][j * nf]:bounds[id(r)][(j + 1) * nf]] for lg, r, j in kept]

@@ -131,6 +131,9 @@ SIGNATURES = {
     "pcs_unique_emit": (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
     "pcs_cylinder_partition_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "pcs_cylinder_scan_batch_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "pcs_range_project_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "pcs_range_project_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "pcs_range_image_fill_f32": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "pcs_voxel_label_vote": (c_int32, [_P, _P, c_int64, c_int64, c_int32, c_int64, _P, _P, _P, _P]),
     "pcs_rows_argmax_gather_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "pcs_predict_points_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
@@ -150,7 +153,7 @@ class _WeightJob(ctypes.Structure):   # pcs_weight_job of include/pcseg_hip.h
                 ("transpose", c_int32), ("nctt", c_int32), ("nt16", c_int32), ("ns", c_int32), ("first_block", c_int64)]
 
 
-ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
+ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_range_project_* / pcs_range_image_fill_f32, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
 _lib = None
 
 
@@ -1417,6 +1420,38 @@ class HipBackend:
                                                     _ptr(scenes), _stream()), "pcs_cylinder_scan_batch_f32")
         return feat, coord, scenes
 
+    # -- the fusion dataset's range view (csrc/rangeproj.hip) -----------------------------------------------
+    def range_project(self, feats, scenes, cuts, num_scenes, hw=(64, 2048)):
+        """The range view of a collated batch (rangeview.py): feats (n, c >= 5) fp32 voxel rows [x, y, z,
+        reflectivity, ring, ...], scenes (n,) the scene of every row (a scene's rows contiguous, in the collate's order), cuts: HOST
+        (num_scenes,) float64 np.random.rand() values -> (image (num_scenes, 5, H, W) fp32, pxpy (n, 3) fp32 = (scene, px, py), bad
+        (1,) int32 device flag: a row was not finite or its ring outside [0, H - 1]; it touched no pixel). The cuts are rounded to
+        float32 on the host and travel in one pinned asynchronous copy; nothing is read back."""
+        from .rangeview import cut_value
+        feats = _dev(feats, "feats", torch.float32)
+        if feats.dim() != 2 or feats.shape[1] < 5:
+            raise ValueError("openpcseg_amd: range_project wants (n, c >= 5) rows [x, y, z, reflectivity, ring], got %s" % (tuple(feats.shape),))
+        scenes = _dev(scenes.int(), "scenes", torch.int32)
+        n, c = feats.shape
+        s, (h, w) = int(num_scenes), (int(v) for v in hw)
+        cuts32 = cut_value(cuts).reshape(-1)
+        if scenes.numel() != n or cuts32.shape[0] != s:
+            raise ValueError("openpcseg_amd: range_project wants one scene per row and one cut per scene (%d rows, %d scene entries, "
+                             "%d scenes, %d cuts)" % (n, scenes.numel(), s, cuts32.shape[0]))
+        ws_bytes = self.lib.pcs_range_project_ws_bytes(s, h, w)
+        if ws_bytes < 0:
+            _check(-1, "pcs_range_project_ws_bytes")
+        dev = feats.device
+        cuts_dev = _h2d(cuts32.tolist(), torch.float32, dev)   # float32 -> Python float -> float32 is exact
+        winner = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+        pxpy = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        image = torch.empty((s, 5, h, w), dtype=torch.float32, device=dev)
+        _check(self.lib.pcs_range_project_f32(_ptr(feats), n, c, _ptr(scenes), _ptr(cuts_dev), s, h, w, _ptr(winner), _ptr(pxpy), _ptr(bad),
+                                              _stream()), "pcs_range_project_f32")
+        _check(self.lib.pcs_range_image_fill_f32(_ptr(winner), _ptr(feats), n, c, s, h, w, _ptr(image), _stream()), "pcs_range_image_fill_f32")
+        return image, pxpy, bad
+
     def voxel_label_vote(self, inverse, labels, m, num_classes, ignore_label):
         """-> (voxel_labels (m,) int64, bad (1,) int32 device flag: a counted label was out of range)."""
         inverse = _dev(inverse, "inverse_map", torch.int64)
@@ -1518,3 +1553,8 @@ def backend():
 def predict_points(logits, **kw):
     """backend().predict_points: the device prediction tail (see HipBackend.predict_points)."""
     return backend().predict_points(logits, **kw)
+
+
+def range_project(feats, scenes, cuts, num_scenes, hw=(64, 2048)):
+    """backend().range_project: the fusion dataset's range view of a collated batch (see HipBackend.range_project)."""
+    return backend().range_project(feats, scenes, cuts, num_scenes, hw)

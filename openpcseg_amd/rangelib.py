@@ -92,7 +92,11 @@ def _frames_in_order(pxpy, b):
         ok = ((f >= 0) & (f < b) & (f == torch.floor(f))).all() & (f[1:] >= f[:-1]).all()
         if not pxpy.is_cuda:
             return bool(ok.item())
-        flag = _FLAG_POOL.pop() if _FLAG_POOL else torch.empty((), dtype=torch.bool).pin_memory()
+        if _FLAG_POOL:
+            flag = _FLAG_POOL.pop()
+        else:
+            with torch.inference_mode(False):   # an ordinary tensor also when first made inside an evaluation pass: the pool outlives it,
+                flag = torch.empty((), dtype=torch.bool).pin_memory()   # and an inference tensor refuses copy_ outside inference mode
         flag.copy_(ok, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()

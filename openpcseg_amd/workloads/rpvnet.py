@@ -16,6 +16,7 @@ and to the range image (rangelib.point_to_range). The range branch stays on torc
 LeakyReLU, AvgPool2d, PixelShuffle: MIOpen's path, not this package's) and keeps the reference's Dropout2d(0.2) modules.
 mk34 = NUM_LAYER [2, 3, 4, 6, 2, 2, 2, 2], cr 1.75, IN_FEATURE_DIM 5 (R:tools/cfgs/fusion/semantic_kitti/rpvnet_mk34_cr17_5.yaml).
 """
+import numpy as np
 import torch
 from torch import nn
 
@@ -196,6 +197,27 @@ class RPVNet(MinkUNet):
             raise RuntimeError("RPVNet.predict is an evaluation pass: call model.eval() first")
         with torch.inference_mode():
             return inference.predict_output(self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"]), batch, evaluator, votes)
+
+    def predict_tta(self, raw, num_votes=10, evaluator=None, vote_chunk=None, scale_range=(0.9, 1.1), rng=np.random, hw=(64, 2048),
+                    return_logits=False):
+        """An evaluation of a raw batch resident in HBM under the fusion dataset's test-time augmentation (`TTA: True`:
+        R:pcseg/data/dataset/semantickitti/semantickitti_fusion.py:116-126 and :148-164, ten rotated and rescaled votes per frame,
+        each with a range view under a cut of its own, collated as ten scenes by collate_batch_tta). `rangeview.tta_params` draws
+        the votes and their cuts from `rng` in the reference's order, `rangeview.device_batch(..., eval_maps=True)` builds
+        `vote_chunk` of them at a time from one read of the scans (None: all votes in one forward; voxel size = the model's
+        `pres`), and the loop of `inference.predict_tta` sums every vote's softmax rows and decides after the last one; `evaluator`
+        (a SegEvaluator) counts that decision once per point. raw: the dict of workloads.synthetic.make_fusion_raw_batch, on the
+        device. -> the keys of inference.predict_tta plus "cuts": the (num_votes * num_frames,) np.random.rand() values drawn."""
+        from .. import rangeview
+        if self.training:
+            raise RuntimeError("RPVNet.predict_tta is an evaluation pass: call model.eval() first")
+        nf = int(raw["num_frames"])
+        params, cuts = rangeview.tta_params(nf, int(num_votes), scale_range=scale_range, rng=rng)
+        return inference.vote_loop(
+            raw, num_votes, vote_chunk, evaluator, return_logits,
+            lambda v0, k: rangeview.device_batch(raw, self.pres, params[v0 * nf:(v0 + k) * nf], cuts[v0 * nf:(v0 + k) * nf], votes=k,
+                                                 eval_maps=True, hw=hw),
+            lambda batch: self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"]), {"params": params, "cuts": cuts})
 
     def forward(self, batch):
         logits = self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"])

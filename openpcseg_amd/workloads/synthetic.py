@@ -67,6 +67,24 @@ def make_raw_batch(seeds, n_points=None, num_classes=20):
             "offsets": [0] + np.cumsum([p.shape[0] for p in pts]).tolist()}   # host-side frame boundaries (known when the scans are uploaded)
 
 
+def scan_rings(n_points=None):
+    """The ring (0 .. N_RINGS - 1, float32) of every row of make_scan(seed, n_points): the scan is ring-major, N_AZ rays per ring,
+    and the subsampling keeps the rays make_scan keeps."""
+    ring = np.arange(N_RINGS * N_AZ, dtype=np.int64) // N_AZ
+    if n_points is not None and n_points < ring.shape[0]:
+        ring = ring[np.linspace(0, ring.shape[0] - 1, n_points).astype(np.int64)]
+    return ring.astype(np.float32)
+
+
+def make_fusion_raw_batch(seeds, n_points=None, num_classes=20):
+    """make_raw_batch for the fusion (RPVNet) dataset: the same scans, labels and boundaries, "points" (sum n_i, 5) fp32 with the
+    ring of every ray in the fifth column (the `xyzret` rows the reference's range view projects by)."""
+    raw = make_raw_batch(seeds, n_points, num_classes)
+    ring = torch.from_numpy(np.tile(scan_rings(n_points), len(seeds)))
+    raw["points"] = torch.cat([raw["points"], ring[:, None]], dim=1)
+    return raw
+
+
 def device_collate(raw, voxel_size=0.05):
     """Dataset transform + sparse_quantize + sparse_collate_fn of a raw batch resident in HBM, bit-exact
     with voxelize_scan / make_batch on the host: round(xyz / voxel) -> shift every frame to >= 0
