@@ -737,6 +737,53 @@ int pcs_range_project_f32(const float *feats, int64_t n, int32_t c, const int32_
 int pcs_range_image_fill_f32(const int32_t *winner, const float *feats, int64_t n, int32_t c, int32_t num_scenes, int32_t H,
                              int32_t W, float *image, void *stream);
 
+/* ---- PolarMix / LaserMix of two raw batches (csrc/scanmix.hip; added under ABI v12, additive) ---------------------------
+ * Replaces, for scans resident in HBM, the mixing of two scans in R:pcseg/data/dataset/semantickitti/semantickitti.py:117-170
+ * (polarmix of PolarMix_semantickitti.py, lasermix_aug of LaserMix_semantickitti.py, get_kitti_points_ringID :86-96).
+ *   points1 (n1, 4) fp32 / labels1 (n1) int64 / frame_offsets1 (F + 1) int64: the batch, frame after frame; points2 / labels2 /
+ *   frame_offsets2: the partner scans, frame f of one mixes with frame f of the other. n1, n2 >= 0, n1 + 4 n2 < 2^31,
+ *   1 <= F <= 65535. Offsets outside [0, n] are clamped: nothing outside the rows is addressed.
+ *   plan (F, PCS_MIX_PLAN_STRIDE) float64 ON THE DEVICE, per frame [mode, alpha, beta, swap, paste, T, t_0 .. t_{T-1}, 0 ...]:
+ *     mode 0: the mixed frame is scan 1 unchanged (no mixing, and LaserMix as the reference computes it);
+ *     mode 1: PolarMix. alpha, beta: the sector's edges as float32 values. A row is inside the sector when swap != 0 and
+ *       alpha < yaw < beta, yaw = -float32(atan2(double(y), double(x))), all in float32. paste != 0 appends the instance rows;
+ *     mode 2: LaserMix over bands. T <= 5 descending thresholds in radians; band = the number of thresholds with inc <= t,
+ *       inc = atan2(double(z), sqrt(double(x)^2 + double(y)^2)), no multiply-add fused.
+ *   classes (num_classes) int64 ON THE DEVICE, num_classes <= PCS_MIX_MAX_CLASSES, distinct: the instance classes in paste order.
+ *   omega (2, 8) float64 ON THE DEVICE: parameter rows of pcs_scan_transform's affine map, (cos w, sin w, 1, 1, 1, 0, 0, 0).
+ * Rows of a mixed frame, in this order (PCS_MIX_BUCKETS counted buckets, each in scan order):
+ *   mode 1: bucket 0 = scan 1 outside the sector; bucket 1 = scan 2 inside it; bucket 2 + k = scan 2 with label classes[k];
+ *           then buckets 2 .. 9 again under omega row 0, and again under omega row 1 (xyz through the affine map: float64, no
+ *           multiply-add fused, one rounding; column 3 and the label copied);
+ *   mode 2: bucket b = band b, from scan 1 where b is even, from scan 2 where b is odd;  mode 0: bucket 0 = scan 1.
+ * pcs_scan_mix_count: ws (pcs_scan_mix_ws_bytes) <- the per-workgroup bases, totals (F, PCS_MIX_BUCKETS) int32 <- the bucket
+ *   sizes, frame_base (F + 1) int64 <- the first mixed row of every frame and, last, the number of mixed rows m (the sum of a
+ *   frame's totals, buckets 2 .. 9 counted three times in mode 1). Three launches, no atomics, nothing read back: the caller
+ *   reads `totals` (or frame_base[F]) to size the output.
+ * pcs_scan_mix_place: the same inputs, ws / totals / frame_base as the count left them -> out_points (m, c_out) fp32, columns
+ *   0 .. 3 written (4 <= c_out <= PCS_SCAN_MAX_COLUMNS; 16-byte stores where c_out == 4 and the rows are aligned), out_labels
+ *   (m) int64. Every store is checked against m. The order of the output is a pure function of the input.
+ * pcs_scan_ring_f32: column 4 of points (m, c >= 5) <- get_kitti_points_ringID per frame of frame_base: proj = 0.5 (yaw /
+ *   float32(pi) + 1) in float32 with yaw = -float32(atan2(double(y), double(-x))); row i flags when it is not the first of its
+ *   frame, proj[i] < 0.2 and proj[i - 1] > 0.8; ring = min(the flags up to i inside the frame, 63). ws: pcs_scan_ring_ws_bytes(m).
+ * Sizes are checked before any pointer: bad sizes give PCS_EINVAL (-1 from the *_ws_bytes queries) also with null pointers. */
+#define PCS_MIX_BUCKETS 10
+#define PCS_MIX_MAX_CLASSES 8
+#define PCS_MIX_PLAN_STRIDE 16
+int64_t pcs_scan_mix_ws_bytes(int64_t n1, int64_t n2, int32_t num_frames);
+int pcs_scan_mix_count(const float *points1, int64_t n1, const int64_t *frame_offsets1, const float *points2,
+                       const int64_t *labels2, int64_t n2, const int64_t *frame_offsets2, int32_t num_frames, const double *plan,
+                       const int64_t *classes, int32_t num_classes, void *ws, int64_t ws_bytes, int32_t *totals,
+                       int64_t *frame_base, void *stream);
+int pcs_scan_mix_place(const float *points1, const int64_t *labels1, int64_t n1, const int64_t *frame_offsets1,
+                       const float *points2, const int64_t *labels2, int64_t n2, const int64_t *frame_offsets2,
+                       int32_t num_frames, const double *plan, const int64_t *classes, int32_t num_classes, const double *omega,
+                       const void *ws, int64_t ws_bytes, const int32_t *totals, const int64_t *frame_base, int64_t m, int32_t c_out,
+                       float *out_points, int64_t *out_labels, void *stream);
+int64_t pcs_scan_ring_ws_bytes(int64_t m);
+int pcs_scan_ring_f32(float *points, int64_t m, int32_t c, const int64_t *frame_base, int32_t num_frames, void *ws,
+                      int64_t ws_bytes, void *stream);
+
 /* ---- prediction tail of an evaluation pass (csrc/predict.hip; added under ABI v12, additive) --------------------------
  * The reference's eval tail (R:pcseg/model/segmentor/voxel/minkunet/minkunet.py:436-455, scoring R:infer.py:35-52) for a
  * whole batch in one launch, no host synchronisation. logits: (m, c) rows of the batch, c <= 64. For point i of scene b

@@ -134,6 +134,12 @@ SIGNATURES = {
     "pcs_range_project_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "pcs_range_project_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "pcs_range_image_fill_f32": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "pcs_scan_mix_ws_bytes": (c_int64, [c_int64, c_int64, c_int32]),
+    "pcs_scan_mix_count": (c_int32, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int32, _P, _P, c_int32, _P, c_int64, _P, _P, _P]),
+    "pcs_scan_mix_place": (c_int32, [_P, _P, c_int64, _P, _P, _P, c_int64, _P, c_int32, _P, _P, c_int32, _P, _P, c_int64, _P, _P, c_int64,
+                                     c_int32, _P, _P, _P]),
+    "pcs_scan_ring_ws_bytes": (c_int64, [c_int64]),
+    "pcs_scan_ring_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int32, _P, c_int64, _P]),
     "pcs_voxel_label_vote": (c_int32, [_P, _P, c_int64, c_int64, c_int32, c_int64, _P, _P, _P, _P]),
     "pcs_rows_argmax_gather_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "pcs_predict_points_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
@@ -153,7 +159,7 @@ class _WeightJob(ctypes.Structure):   # pcs_weight_job of include/pcseg_hip.h
                 ("transpose", c_int32), ("nctt", c_int32), ("nt16", c_int32), ("ns", c_int32), ("first_block", c_int64)]
 
 
-ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_range_project_* / pcs_range_image_fill_f32, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
+ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_scan_mix_* / pcs_scan_ring_*, pcs_range_project_* / pcs_range_image_fill_f32, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
 _lib = None
 
 
@@ -1451,6 +1457,58 @@ class HipBackend:
                                               _stream()), "pcs_range_project_f32")
         _check(self.lib.pcs_range_image_fill_f32(_ptr(winner), _ptr(feats), n, c, s, h, w, _ptr(image), _stream()), "pcs_range_image_fill_f32")
         return image, pxpy, bad
+
+    # -- PolarMix / LaserMix of two raw batches (csrc/scanmix.hip) -------------------------------------------
+    def scan_mix(self, points1, labels1, offsets1, points2, labels2, offsets2, plan, omega, classes, ring=False):
+        """The mixed raw batch of scanmix.device_mix: points (n, 4) fp32 / labels (n,) int64 on the device,
+        offsets: HOST lists of num_frames + 1 boundaries; plan: host (num_frames, PCS_MIX_PLAN_STRIDE) float64 (scanmix.device_plan),
+        omega: host (2, 8) float64 parameter rows, classes: host list of <= 8 distinct labels
+        -> (points (m, 4 + ring) fp32, labels (m,) int64, the HOST list of the mixed frames' boundaries).
+        The plan, omega, the classes and both sets of boundaries travel in ONE pinned asynchronous copy (the float64 words as
+        their int64 bit patterns); ONE host read: the (num_frames, 10) bucket counts, which size the output."""
+        import numpy as np
+        points1, points2 = _dev(points1, "points", torch.float32), _dev(points2, "partner points", torch.float32)
+        labels1, labels2 = _dev(labels1, "labels", torch.int64), _dev(labels2, "partner labels", torch.int64)
+        n1, n2, nf = points1.shape[0], points2.shape[0], len(offsets1) - 1
+        plan = np.ascontiguousarray(plan, dtype=np.float64)
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        classes = [int(c) for c in classes]
+        if nf < 1 or len(offsets2) != nf + 1 or plan.shape != (nf, 16) or omega.shape != (2, 8) or len(classes) > 8:
+            raise ValueError("openpcseg_amd: scan_mix wants num_frames + 1 boundaries per batch, a (num_frames, 16) plan, (2, 8) omega rows "
+                             "and at most 8 classes")
+        dev = points1.device
+        words = (plan.reshape(-1).view(np.int64).tolist() + omega.reshape(-1).view(np.int64).tolist() + classes + [0] * (8 - len(classes))
+                 + [int(o) for o in offsets1] + [int(o) for o in offsets2])
+        table = _h2d(words, torch.int64, dev)
+        a = nf * 16
+        plan_d, omega_d, cls_d = table[:a].view(torch.float64), table[a:a + 16].view(torch.float64), table[a + 16:a + 24]
+        off1_d, off2_d = table[a + 24:a + 25 + nf], table[a + 25 + nf:]
+        ws_bytes = self.lib.pcs_scan_mix_ws_bytes(n1, n2, nf)
+        if ws_bytes < 0:
+            _check(-1, "pcs_scan_mix_ws_bytes")
+        ws = torch.empty(max(int(ws_bytes), 4), dtype=torch.uint8, device=dev)
+        totals = torch.empty((nf, 10), dtype=torch.int32, device=dev)
+        frame_base = torch.empty(nf + 1, dtype=torch.int64, device=dev)
+        _check(self.lib.pcs_scan_mix_count(_ptr(points1), n1, _ptr(off1_d), _ptr(points2), _ptr(labels2), n2, _ptr(off2_d), nf, _ptr(plan_d),
+                                           _ptr(cls_d), len(classes), _ptr(ws), ws.numel(), _ptr(totals), _ptr(frame_base), _stream()),
+               "pcs_scan_mix_count")
+        counts = totals.cpu().numpy().astype(np.int64)   # the one host read
+        rows = counts.sum(1) + np.where(plan[:, 0] == 1, 2 * counts[:, 2:].sum(1), 0)
+        offsets = [0] + np.cumsum(rows).tolist()
+        m, c_out = offsets[-1], 5 if ring else 4
+        out = torch.empty((m, c_out), dtype=torch.float32, device=dev)
+        out_labels = torch.empty(m, dtype=torch.int64, device=dev)
+        _check(self.lib.pcs_scan_mix_place(_ptr(points1), _ptr(labels1), n1, _ptr(off1_d), _ptr(points2), _ptr(labels2), n2, _ptr(off2_d), nf,
+                                           _ptr(plan_d), _ptr(cls_d), len(classes), _ptr(omega_d), _ptr(ws), ws.numel(), _ptr(totals),
+                                           _ptr(frame_base), m, c_out, _ptr(out), _ptr(out_labels), _stream()), "pcs_scan_mix_place")
+        if ring and m:
+            ring_bytes = self.lib.pcs_scan_ring_ws_bytes(m)
+            if ring_bytes < 0:
+                _check(-1, "pcs_scan_ring_ws_bytes")
+            ring_ws = torch.empty(max(int(ring_bytes), 4), dtype=torch.uint8, device=dev)
+            _check(self.lib.pcs_scan_ring_f32(_ptr(out), m, c_out, _ptr(frame_base), nf, _ptr(ring_ws), ring_ws.numel(), _stream()),
+                   "pcs_scan_ring_f32")
+        return out, out_labels, offsets
 
     def voxel_label_vote(self, inverse, labels, m, num_classes, ignore_label):
         """-> (voxel_labels (m,) int64, bad (1,) int32 device flag: a counted label was out of range)."""

@@ -67,6 +67,12 @@ def make_raw_batch(seeds, n_points=None, num_classes=20):
             "offsets": [0] + np.cumsum([p.shape[0] for p in pts]).tolist()}   # host-side frame boundaries (known when the scans are uploaded)
 
 
+def make_partner_raw_batch(seeds, n_points=None, num_classes=20, seed_shift=1000):
+    """The partner scans of make_raw_batch(seeds, ...) for scanmix.device_mix (what `annos_another` is to the reference's loader):
+    frame i is the scan and the labels of seed seeds[i] + seed_shift, another scene of the same shape."""
+    return make_raw_batch([s + seed_shift for s in seeds], n_points, num_classes)
+
+
 def scan_rings(n_points=None):
     """The ring (0 .. N_RINGS - 1, float32) of every row of make_scan(seed, n_points): the scan is ring-major, N_AZ rays per ring,
     and the subsampling keeps the rays make_scan keeps."""
