@@ -822,6 +822,60 @@ typedef struct {
 int64_t pcs_weights_multi_plan(pcs_weight_job *jobs_host, int32_t n_jobs);
 int pcs_weights_multi(const pcs_weight_job *jobs_dev, int32_t n_jobs, int64_t total_blocks, void *stream);
 
+/* ---- the tail of a training step in two launches (still v12, additive; csrc/steptail.hip) ---------------------------------
+ * scaler.unscale_ -> clip_grad_norm_(params, max_norm) -> scaler.step(SGD(momentum, weight_decay, nesterov)) -> scaler.update
+ * of R:train.py:367-372 / R:pcseg/optim/__init__.py:15-34 over one job table: a job is one fp32 parameter tensor with its
+ * gradient and (with momentum) its momentum buffer. A workgroup covers PCS_STEP_BLOCK_ELEMS elements of one job.
+ *   plan  : HOST. Checks the jobs against `hyper` (group index, 4-byte alignment, buf present exactly when the group's
+ *           mu != 0, non-null p / g unless numel == 0), fills first_block, returns the work-block count (-1 + pcs_last_error on
+ *           a bad job). The planned table is copied to the device by the caller.
+ *   norm  : one read of every g. Sum of squares in double; a workgroup sweeps work blocks b, b + grid, ... (grid = min(total_blocks,
+ *           2048)), leaves one partial in `ws`, and the workgroup that draws the last ticket folds the partials in a fixed order:
+ *           bit-reproducible, no float atomics. Writes `record` (8 DEVICE floats):
+ *             [0] total_norm = float(sqrt(double sum)) of the gradients as they are stored (scaled, under a scaler)
+ *             [1] inv_scale  = float(1.0 / double(*scale)); 1 when scale == NULL
+ *             [2] coef       = min(max_norm / (total_norm * inv_scale + 1e-6f), 1.0f) in fp32, a NaN kept (torch's clamp);
+ *                              1 when max_norm < 0 (no clipping)
+ *             [3] found_inf  = 1.0f when any gradient value was inf or NaN, else 0.0f
+ *             [4] total_norm * inv_scale: the norm of the unscaled gradients, what clip_grad_norm_ returns
+ *             [5..7] 0
+ *           and then, with scale != NULL, torch.amp.GradScaler.update's rule on the DEVICE words *scale / *growth_tracker:
+ *           found_inf -> scale *= backoff, tracker = 0; else ++tracker, and when it equals growth_interval scale *= growth
+ *           (kept when the product is not finite) and tracker = 0. The record holds the scale from BEFORE the update.
+ *           ws: PCS_STEP_WS_BYTES(total_blocks) bytes whose first 4 are zero before the first launch (the kernel leaves them
+ *           zero). An empty table is PCS_EINVAL.
+ *   apply : per element, one fp32 rounding per operation, nothing contracted:
+ *             g1 = g * inv_scale;  g2 = g1 * coef;  d = g2 + wd * p;
+ *             mu != 0:  buf = mu * buf + d;  d = nesterov ? d + mu * buf : buf;
+ *             p = p + (-lr) * d
+ *           record == NULL: inv_scale = coef = 1 (plain SGD, one launch). skip_on_inf != 0 (a scaler is in play; wants a
+ *           record): when found_inf is set nothing is written, p and buf keep their bits. g is NEVER written: unlike torch,
+ *           the gradients stay scaled and unclipped. `hyper` is a HOST struct and travels by value in the kernel arguments.
+ *           16-byte loads and stores for a job whose p, g, buf are 16-byte aligned, element-wise otherwise and at a job's end. */
+#define PCS_STEP_BLOCK_ELEMS 4096
+#define PCS_STEP_MAX_GROUPS 8
+#define PCS_STEP_WS_BYTES(total_blocks) (16 + 12 * (int64_t)(total_blocks))
+typedef struct {
+  float *p;
+  const float *g;
+  float *buf;          /* NULL exactly when the group's mu == 0 */
+  int64_t numel;
+  int32_t group;       /* index into pcs_step_hyper */
+  int32_t reserved;
+  int64_t first_block; /* filled by the plan call */
+} pcs_step_job;
+typedef struct {
+  float lr[PCS_STEP_MAX_GROUPS], wd[PCS_STEP_MAX_GROUPS], mu[PCS_STEP_MAX_GROUPS];
+  int32_t nesterov[PCS_STEP_MAX_GROUPS];
+  int32_t n_groups;
+} pcs_step_hyper;
+int64_t pcs_step_plan(pcs_step_job *jobs_host, int32_t n_jobs, const pcs_step_hyper *hyper);
+int pcs_step_norm(const pcs_step_job *jobs_dev, int32_t n_jobs, int64_t total_blocks, float max_norm, float *scale,
+                  int32_t *growth_tracker, double growth_factor, double backoff_factor, int32_t growth_interval, void *ws,
+                  int64_t ws_bytes, float *record, void *stream);
+int pcs_step_apply(const pcs_step_job *jobs_dev, int32_t n_jobs, int64_t total_blocks, const pcs_step_hyper *hyper,
+                   const float *record, int32_t skip_on_inf, void *stream);
+
 /* ---- Lovasz-softmax of the training criterion (the timed step's loss tail) -----------------
  * lovasz_softmax(probas, labels, classes='present', per_image=False, ignore) of
  * R:tools/utils/common/lovasz_losses.py:158-204 (+ lovasz_grad :23-35, flatten_probas :207-228) as the reference's

@@ -8,6 +8,7 @@ operator API that PJLab-ADG/OpenPCSeg's segmentors call.
 """
 from .sparse import SparseTensor, PointTensor, cat, fapply, get_kernel_offsets, make_ntuple  # noqa: F401
 from .compat import install_as_torchsparse, install_reference_aliases  # noqa: F401
+from . import optim  # noqa: F401  (FusedSGD, LossScaler: the training-step tail on the device)
 
 
 def fuse(model, criterion=True, glue=True, forward=True):

@@ -278,7 +278,8 @@ class _WeightPrep:
     already handed out in it is asked for again -- the next forward has started -- and the first request of a new pass
     re-prepares every known copy from the live weights, whatever happened to them in between: an optimizer step, `load_state_dict`,
     but also writes the autograd version counter does not see (`w.data.copy_()`, `w.data = t`, EMA / SWA swaps,
-    `vector_to_parameters`, multi-tensor optimizers writing through raw pointers). Inside a pass a copy is additionally refreshed
+    `vector_to_parameters`, and `openpcseg_amd.optim.FusedSGD`, the multi-tensor optimizer whose kernels write the weights through
+    raw pointers: it is a torch.optim.Optimizer, so the post-step hook below ends the pass for it too). Inside a pass a copy is additionally refreshed
     when the parameter's version counter or storage address changed. A training step pays the one launch it always paid
     (the optimizer made everything stale anyway); inference pays one ~0.1 ms launch per forward. `invalidate()` forces a refresh.
     What the pass rule does NOT see: a SECOND model written through `.data` after the first model's pass began and run before any

@@ -145,6 +145,9 @@ SIGNATURES = {
     "pcs_predict_points_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
     "pcs_weights_multi_plan": (c_int64, [_P, c_int32]),
     "pcs_weights_multi": (c_int32, [_P, c_int32, c_int64, _P]),
+    "pcs_step_plan": (c_int64, [_P, c_int32, _P]),
+    "pcs_step_norm": (c_int32, [_P, c_int32, c_int64, c_float, _P, _P, c_double, c_double, c_int32, _P, c_int64, _P, _P]),
+    "pcs_step_apply": (c_int32, [_P, c_int32, c_int64, _P, _P, c_int32, _P]),
     "pcs_lovasz_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int64]),
     "pcs_lovasz_softmax_f32": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int64, _P, _P, _P, c_int64, _P]),
     "pcs_debug_convh_ws": (None, [c_int32, c_int32, c_int32]),       # measurement switches (A/B tools), not part of the contract
@@ -159,7 +162,21 @@ class _WeightJob(ctypes.Structure):   # pcs_weight_job of include/pcseg_hip.h
                 ("transpose", c_int32), ("nctt", c_int32), ("nt16", c_int32), ("ns", c_int32), ("first_block", c_int64)]
 
 
-ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_scan_mix_* / pcs_scan_ring_*, pcs_range_project_* / pcs_range_image_fill_f32, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
+STEP_BLOCK_ELEMS = 4096   # PCS_STEP_BLOCK_ELEMS: the elements of a parameter tensor one workgroup of the step tail covers
+STEP_MAX_GROUPS = 8       # PCS_STEP_MAX_GROUPS
+
+
+class _StepJob(ctypes.Structure):   # pcs_step_job of include/pcseg_hip.h
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("buf", c_void_p), ("numel", c_int64), ("group", c_int32), ("reserved", c_int32),
+                ("first_block", c_int64)]
+
+
+class _StepHyper(ctypes.Structure):   # pcs_step_hyper of include/pcseg_hip.h
+    _fields_ = [("lr", c_float * STEP_MAX_GROUPS), ("wd", c_float * STEP_MAX_GROUPS), ("mu", c_float * STEP_MAX_GROUPS),
+                ("nesterov", c_int32 * STEP_MAX_GROUPS), ("n_groups", c_int32)]
+
+
+ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_step_plan / pcs_step_norm / pcs_step_apply, pcs_scan_mix_* / pcs_scan_ring_*, pcs_range_project_* / pcs_range_image_fill_f32, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
 _lib = None
 
 
@@ -941,6 +958,52 @@ class HipBackend:
             hit = (sig, host.to(jobs[0][0].device, non_blocking=True), int(blocks), host)
             self._wm_table = hit
         _check(self.lib.pcs_weights_multi(_ptr(hit[1]), len(jobs), hit[2], _stream()), "pcs_weights_multi")
+
+    def step_tail(self, cache, jobs, hyper, record=None, max_norm=None, scaler=None):
+        """The tail of a training step over `jobs` = [(p, g, buf or None, group)] (fp32 contiguous device tensors; the caller
+        has checked that) with `hyper` = [(lr, weight_decay, momentum, nesterov)] per group (csrc/steptail.hip): with `record`
+        (8 device floats) the norm launch -- clip coefficient for `max_norm`, overflow flag, and for `scaler` = (scale,
+        growth_tracker, growth_factor, backoff_factor, growth_interval) the unscale factor and GradScaler.update's rule on the
+        two device words -- then the apply launch, which a scaler lets skip an overflowed step. Without `record` the apply launch
+        alone. No host synchronisation. `cache` (a dict the caller keeps) holds the device copy of the job table and the norm's
+        workspace while the pointers stay the same; a changed table goes over through pinned memory, non-blocking."""
+        if not jobs:
+            return
+        if not 1 <= len(hyper) <= STEP_MAX_GROUPS:
+            raise ValueError("openpcseg_amd: step_tail takes 1 .. %d groups" % STEP_MAX_GROUPS)
+        hy = _StepHyper()
+        hy.n_groups = len(hyper)
+        for i, (lr, wd, mu, nesterov) in enumerate(hyper):
+            hy.lr[i], hy.wd[i], hy.mu[i], hy.nesterov[i] = lr, wd, mu, int(bool(nesterov))
+        dev = jobs[0][0].device
+        sig = (tuple((p.data_ptr(), g.data_ptr(), 0 if b is None else b.data_ptr(), p.numel(), grp) for p, g, b, grp in jobs),
+               tuple(h[2] != 0 for h in hyper), str(dev))
+        hit = cache.get("table")
+        if hit is None or hit[0] != sig:
+            arr = (_StepJob * len(jobs))()
+            for j, (pp, gp, bp, n, grp) in zip(arr, sig[0]):
+                j.p, j.g, j.buf, j.numel, j.group = pp or None, gp or None, bp or None, n, grp
+            blocks = self.lib.pcs_step_plan(ctypes.byref(arr), len(jobs), ctypes.byref(hy))
+            if blocks < 0:
+                _check(-1, "pcs_step_plan")
+            host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory()
+            ws = cache.get("ws")
+            if ws is None or ws.numel() < 16 + 12 * blocks or ws.device != dev:
+                ws = torch.zeros(16 + 12 * int(blocks), dtype=torch.uint8, device=dev)   # PCS_STEP_WS_BYTES; the ticket starts at 0
+                cache["ws"] = ws
+            hit = (sig, host.to(dev, non_blocking=True), int(blocks), host)
+            cache["table"] = hit
+        table, blocks = hit[1], hit[2]
+        if blocks == 0:
+            return
+        if record is not None:
+            ws = cache["ws"]
+            scale, tracker, growth, backoff, interval = scaler if scaler is not None else (None, None, 1.0, 1.0, 0)
+            _check(self.lib.pcs_step_norm(_ptr(table), len(jobs), blocks, -1.0 if max_norm is None else float(max_norm), _ptr(scale),
+                                          _ptr(tracker), float(growth), float(backoff), int(interval), _ptr(ws), ws.numel(),
+                                          _ptr(record), _stream()), "pcs_step_norm")
+        _check(self.lib.pcs_step_apply(_ptr(table), len(jobs), blocks, ctypes.byref(hy), _ptr(record),
+                                       int(scaler is not None), _stream()), "pcs_step_apply")
 
     def conv_wgrad(self, fa, fb, kmap, a_col, split=False):
         """gW[k] = sum_{pairs of k} fa[pair[a_col]]^T (x) fb[pair[1-a_col]] -> (K, ca, cb). split=True: the operands go
