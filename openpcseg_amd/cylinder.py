@@ -80,39 +80,23 @@ def device_batch(raw, space_min, space_max, grid_size, num_classes=20, params=No
     check=False hands the device flag back under "bad" instead."""
     import numpy as np
 
-    from .hostdata import sparse_quantize_frames
+    from .hostdata import raw_frames, scene_points, scene_row_offsets, sparse_quantize_frames, vote_labels
     from .transform import identity_params
-    pts = raw["points"]
-    if not (isinstance(pts, torch.Tensor) and pts.is_cuda):
-        raise RuntimeError("openpcseg_amd: `points` must be a HIP device tensor (got %s); the MI355X backend has no CPU path -- "
-                           "the reference's dataset code is the host form" % (getattr(pts, "device", type(pts)),))
-    off = [int(o) for o in raw["offsets"]]
-    nf, v, n = int(raw["num_frames"]), int(votes), pts.shape[0]
-    if len(off) != nf + 1:
-        raise ValueError("openpcseg_amd: %d frame boundaries for %d frames" % (len(off), nf))
-    if any(off[i + 1] <= off[i] for i in range(nf)):
-        raise ValueError("openpcseg_amd: an empty frame has no voxels to collate (the reference fails on it too)")
-    if off[0] != 0 or off[-1] != n:
-        raise ValueError("openpcseg_amd: the frame boundaries must cover the %d rows of `points`" % n)
+    pts, point_label, off, nf, _ = raw_frames(raw, "cylinder.device_batch", "the reference's dataset code", need_labels=labels)
+    v = int(votes)
     if params is None:
         params = identity_params(v * nf)
     be = native.backend()
     feat, coord, scenes = be.cylinder_scan_batch(pts, off, params, v, space_min, space_max, grid_size)
     vox, index, inverse = sparse_quantize_frames(coord, scenes, v * nf)
-    counts = torch.zeros(v * nf + 1, dtype=torch.int64, device=pts.device)
-    counts.scatter_add_(0, vox[:, 3].long() + 1, torch.ones(vox.shape[0], dtype=torch.int64, device=pts.device))
-    first = torch.cumsum(counts, 0)   # first voxel row of every scene, then the total
+    first = scene_row_offsets(vox[:, 3], v * nf)   # first voxel row of every scene, then the total
     out = {"point_feature": feat, "point_coord": torch.cat([coord, scenes.int()[:, None]], dim=1).float(),
            # the cell centre of a voxel IS the cell centre of its representative point: its point_feature row (:155-157)
            "voxel_feature": feat.index_select(0, index), "voxel_coord": vox.long(), "inverse_map": inverse - first[scenes],
-           "offset": first[1:].int(), "num_points": np.array([off[f + 1] - off[f] for _ in range(v) for f in range(nf)])}
-    point_label = raw.get("labels")
+           "offset": first[1:].int(), "num_points": np.array(scene_points(off, v))}
     if point_label is not None:
-        point_label = point_label.reshape(-1).long()
-        out["point_label"] = point_label if v == 1 else point_label.repeat(v)   # row v * n + i carries the label of point i
+        out["point_label"] = vote_labels(point_label.long(), v)
     if labels:
-        if point_label is None:
-            raise ValueError("openpcseg_amd: cylinder.device_batch(labels=True) needs raw['labels']")
         out["voxel_label"], bad = be.voxel_label_vote(inverse, out["point_label"], vox.shape[0], num_classes, IGNORE_VOTE_LABEL)
         if not check:
             out["bad"] = bad

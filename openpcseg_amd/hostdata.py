@@ -3,13 +3,16 @@ a15), and -- for scans already resident in HBM (a device tensor in) -- on the MI
 kernels (section 8 f1). Same signatures and ordering contract as
   sparse_quantize / ravel_hash   TS:torchsparse/utils/quantize.py:9-46
   sparse_collate(_fn)            TS:torchsparse/utils/collate.py:11-59
+and the host side that the device input builders share: `raw_frames`, the one reader of a raw batch,
+`scene_row_offsets`, `scene_points`, `vote_labels`.
 """
 import numpy as np
 import torch
 
 from .sparse import SparseTensor
 
-__all__ = ["ravel_hash", "sparse_quantize", "sparse_quantize_frames", "sparse_collate", "sparse_collate_fn"]
+__all__ = ["ravel_hash", "sparse_quantize", "sparse_quantize_frames", "sparse_collate", "sparse_collate_fn", "raw_frames",
+           "scene_row_offsets", "scene_points", "vote_labels"]
 
 
 def ravel_hash(x):
@@ -90,6 +93,60 @@ def sparse_quantize_frames(coords, frames, num_frames):
         c = coords.long() - lo
         key = ((f * ext[0] + c[:, 0]) * ext[1] + c[:, 1]) * ext[2] + c[:, 2]
     return be.quantize_sorted_keys(key, coords, f)
+
+
+# ---- raw batches resident in HBM -------------------------------------------------------------------------
+_COLUMNS = ("x", "y", "z", "reflectivity", "ring")
+
+
+def raw_frames(raw, caller, host_form, min_columns=3, exact_columns=False, allow_empty=False, need_labels=False):
+    """The one reader of a raw batch -- the dict `workloads.synthetic.make_raw_batch` returns with its tensors on the device:
+    "points" (n, C) fp32 frame after frame, "labels" (n,) (optional unless need_labels), "offsets": the host frame boundaries,
+    "num_frames" -- for the device builders and the voted evaluations.
+    -> (points, labels flattened or None, off: host list of ints, num_frames, n).
+    caller: its name in the messages; host_form: where the device refusal points a caller with host data; min_columns (exactly
+    that many with exact_columns): the columns the caller reads; allow_empty: whether a frame without rows passes (the builders
+    refuse it as the reference fails on it; the mixer takes it). Every refusal comes before any launch, the device check last."""
+    pts, labels = raw["points"], raw.get("labels")
+    shape = tuple(getattr(pts, "shape", ()))
+    if len(shape) != 2 or (shape[1] != min_columns if exact_columns else shape[1] < min_columns):
+        raise ValueError("openpcseg_amd: %s wants (n, %s%d) points [%s], got %s"
+                         % (caller, "" if exact_columns else "C >= ", min_columns, ", ".join(_COLUMNS[:min_columns]), shape))
+    off, nf, n = [int(o) for o in raw["offsets"]], int(raw["num_frames"]), shape[0]
+    if labels is not None:
+        labels = labels.reshape(-1)
+    if len(off) != nf + 1 or off[0] != 0 or off[-1] != n or any(off[i + 1] < off[i] for i in range(nf)) or (
+            labels is not None and labels.shape[0] != n):
+        raise ValueError("openpcseg_amd: %s wants %d frame boundaries for its %d frames, ascending from 0 to the %d rows of its points "
+                         "and labels, got %s" % (caller, nf + 1, nf, n, off))
+    if not allow_empty and any(off[i + 1] == off[i] for i in range(nf)):
+        raise ValueError("openpcseg_amd: %s: an empty frame has no rows to voxelise (the reference fails on it too)" % caller)
+    if need_labels and labels is None:
+        raise ValueError("openpcseg_amd: %s needs raw['labels']" % caller)
+    for what, t in (("points", pts), ("labels", labels)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError("openpcseg_amd: `%s` of %s must be a HIP device tensor (got %s); the MI355X backend has no CPU path -- "
+                               "%s is the host form" % (what, caller, getattr(t, "device", type(t)), host_form))
+    return pts, labels, off, nf, n
+
+
+def scene_row_offsets(scene_col, num_scenes):
+    """(num_scenes + 1) int64 prefix offsets of the rows of every scene, from the scene column (values in [0, num_scenes)): entry s
+    is the first row of scene s, the last one the total. On the column's device, nothing read back."""
+    col = scene_col.long()
+    counts = torch.zeros(num_scenes + 1, dtype=torch.int64, device=col.device)
+    counts[1:].scatter_add_(0, col, torch.ones_like(col))
+    return torch.cumsum(counts, 0)
+
+
+def scene_points(off, votes):
+    """The host "num_points" list of votes * num_frames scenes, scene v * num_frames + f = vote v of frame f."""
+    return [off[f + 1] - off[f] for _ in range(votes) for f in range(len(off) - 1)]
+
+
+def vote_labels(labels, votes):
+    """Labels for votes * n rows: row v * n + i carries the label of point i."""
+    return labels if votes == 1 else labels.repeat(votes)
 
 
 def sparse_collate(inputs):

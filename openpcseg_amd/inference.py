@@ -26,6 +26,8 @@ so it does not commute into the weights (and a fold into the next sparse convolu
 that exist). There the BatchNorm rides in the same launch as a per-column affine map behind the activation (`PostAffineConv`,
 PCS_EP_POST_AFFINE): W stays what it is, the write-back computes leaky(conv + bias) * s + t (+ residual), one rounding on the store.
 """
+import functools
+
 import numpy as np
 import torch
 from torch import nn
@@ -34,6 +36,7 @@ from . import functional as F
 from . import modules as spnn
 from . import native
 from .fused import FusedBatchNorm
+from .hostdata import raw_frames, scene_row_offsets
 from .linear import devoxelized_linear
 from .sparse import SparseTensor
 
@@ -314,11 +317,8 @@ def unfreeze(model):
 
 # ---- prediction tail ------------------------------------------------------------------------------------------------
 def _scene_offsets(batch_col, n_scenes):
-    """(n_scenes + 1) int64 prefix offsets of the rows of each scene, from the batch column; on the device, no read-back."""
-    col = batch_col.long().clamp(0, n_scenes - 1)
-    counts = torch.zeros(n_scenes + 1, dtype=torch.int64, device=col.device)
-    counts.scatter_add_(0, col + 1, torch.ones_like(col))
-    return torch.cumsum(counts, 0)
+    """hostdata.scene_row_offsets of a batch column that comes from outside: clamped to the scenes the host side of the batch names."""
+    return scene_row_offsets(batch_col.long().clamp(0, n_scenes - 1), n_scenes)
 
 
 def point_predict(logits, batch, votes=None, hist=None, bad=None):
@@ -486,51 +486,62 @@ def predict_tta(model, raw, num_votes=10, evaluator=None, voxel_size=0.05, rng=n
     fn = getattr(model, "point_logits", None)
     if not callable(fn) or isinstance(fn, nn.Module):
         raise TypeError("openpcseg_amd: predict_tta needs a model with a point_logits(lidar) method (MinkUNet, SPVCNN)")
-    nf = int(raw["num_frames"])
-    params = transform.tta_params(nf, int(num_votes), scale_range=scale_range, rng=rng)
-    return vote_loop(raw, num_votes, vote_chunk, evaluator, return_logits,
-                     lambda v0, k: transform.device_batch(raw, voxel_size, params[v0 * nf:(v0 + k) * nf], votes=k, eval_maps=True),
-                     lambda batch: fn(batch["lidar"]), {"params": params})
+    return vote_loop(raw, "predict_tta", num_votes, vote_chunk, evaluator, return_logits,
+                     lambda nf, nv: {"params": transform.tta_params(nf, nv, scale_range=scale_range, rng=rng)},
+                     lambda part, k: transform.device_batch(raw, voxel_size, part["params"], votes=k, eval_maps=True),
+                     lambda batch, v0, scene_votes: scene_votes(batch, fn(batch["lidar"])))
 
 
-def vote_loop(raw, num_votes, vote_chunk, evaluator, return_logits, batch_of, logits_of, drawn):
-    """The voted evaluation `predict_tta` and `RPVNet.predict_tta` share: batch_of(v0, k) -> the device batch of votes v0 .. v0 + k
-    (a `transform.device_batch(..., eval_maps=True)` dict: scene j * num_frames + f = vote v0 + j of frame f), logits_of(batch) ->
-    the eval logits over batch["lidar"]'s rows (called under inference_mode). Per vote one launch of the prediction tail adds the
-    softmax of every point's row into one (n, num_class) tensor; the decision and the evaluator's counts come from the last vote's
-    launch only. drawn: the tables the caller drew, handed back. -> {"pred", "votes", "point_offset", **drawn} and with
-    return_logits "logits" (see predict_tta)."""
-    nf = int(raw["num_frames"])
-    off = [int(o) for o in raw["offsets"]]
-    n = off[-1]
+def vote_loop(raw, caller, num_votes, vote_chunk, evaluator, return_logits, draw, batch_of, logits_of):
+    """The voted evaluation of every model (`predict_tta`, `RPVNet.predict_tta`, `CylinderTS.predict_tta`).
+    Per vote one launch of the prediction tail adds the softmax of every point's row into one (n, num_class) tensor; the decision
+    and the evaluator's counts come from the last vote's launch only. draw(num_frames, num_votes) -> {name: vote-major table},
+    handed back; batch_of(part, k) -> the device batch of k votes from their rows `part` of every table (scene j * num_frames + f
+    = the chunk's vote j of frame f); logits_of(batch, v0, scene_votes), under inference_mode -> (fp32 contiguous logits, vote)
+    with vote(j) -> (the tail's keywords that find vote v0 + j's points in the logits, keep) and keep() -> {name: tensor}: what
+    return_logits keeps of that vote, called after the loop. scene_votes(batch, logits) is that pair for a
+    `transform.device_batch(..., eval_maps=True)` dict and logits over batch["lidar"]'s rows.
+    -> {"pred", "votes", "point_offset", **the tables drawn} and with return_logits a list per kept name (see predict_tta)."""
+    pts, labels, off, nf, n = raw_frames(raw, caller, "a model's `predict` on a host-built batch", need_labels=evaluator is not None)
     nv = int(num_votes)
     chunk = nv if vote_chunk is None else max(1, min(int(vote_chunk), nv))
+    drawn = draw(nf, nv)
     be = native.backend()
-    dev = raw["points"].device
-    labels = raw["labels"].long().contiguous() if evaluator is not None else None
-    point_offset = native._h2d(off, torch.int64, dev)
+    dev = pts.device
+    labels = labels.long().contiguous() if evaluator is not None else None
+    point_offset = functools.lru_cache(None)(lambda: native._h2d(off, torch.int64, dev))   # one upload, for callers of scene_votes
+
+    def scene_votes(batch, logits):
+        logits = logits.float().contiguous()
+        row_offset = _scene_offsets(batch["lidar"].C[:, -1], len(batch["num_points"]))
+        bounds = functools.lru_cache(None)(lambda: row_offset.cpu().tolist())   # asked for explicitly: the chunk's only read-back
+        inverse = batch["inverse_map"].F
+
+        def vote(j):
+            maps = {"inverse": inverse[j * n:(j + 1) * n], "point_offset": point_offset(), "row_offset": row_offset[j * nf:(j + 1) * nf + 1]}
+            return maps, lambda: {"logits": logits[bounds()[j * nf]:bounds()[(j + 1) * nf]]}
+        return logits, vote
+
     votes = pred = bad = None   # bad: the flag of a run without evaluator, made by the first launch
     kept = []
     for v0 in range(0, nv, chunk):
         k = min(chunk, nv - v0)
-        batch = batch_of(v0, k)
+        batch = batch_of({name: table[v0 * nf:(v0 + k) * nf] for name, table in drawn.items()}, k)
         with torch.inference_mode():
-            logits = logits_of(batch).float().contiguous()
+            logits, vote = logits_of(batch, v0, scene_votes)
         if votes is None:
             votes = torch.zeros((n, logits.shape[1]), dtype=torch.float32, device=dev)
-        row_offset = _scene_offsets(batch["lidar"].C[:, -1], k * nf)
-        inverse = batch["inverse_map"].F
         for j in range(k):
             last = v0 + j == nv - 1
-            maps = {"inverse": inverse[j * n:(j + 1) * n], "point_offset": point_offset, "row_offset": row_offset[j * nf:(j + 1) * nf + 1]}
+            maps, keep = vote(j)
             if evaluator is not None:   # every vote's flag goes to the evaluator, the counts come from the last decision only
                 pred = evaluator.tail(logits, labels, off, count=last, votes=votes, want_pred=last, **maps)
             else:
                 pred, bad = be.predict_points(logits, votes=votes, want_pred=last, bad=bad, **maps)
             if return_logits:
-                kept.append((logits, row_offset, j))
+                kept.append(keep)
     out = {"pred": pred, "votes": votes, "point_offset": off, **drawn}
-    if return_logits:
-        bounds = {id(r): r.cpu().tolist() for _, r, _ in kept}   # asked for explicitly: the only read-back, after everything is queued
-        out["logits"] = [lg[bounds[id(r)][j * nf]:bounds[id(r)][(j + 1) * nf]] for lg, r, j in kept]
+    for keep in kept:
+        for name, t in keep().items():
+            out.setdefault(name, []).append(t)
     return out

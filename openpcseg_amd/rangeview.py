@@ -10,16 +10,17 @@ The range view projects the frame's DEDUPLICATED voxel rows (lidar.F, not the ra
 azimuth shifted by a random cut, row from the ring, pixel collisions resolved by "the last row wins" (NumPy fancy assignment).
 `range_view_host` restates get_range_image line by line in NumPy with the cut passed in -- the host path and the yardstick of
 csrc/rangeproj.hip --, `draw_train_params` / `tta_params` make the reference's draws in its call order (the cut is the ONE
-np.random.rand() behind each frame's augmentation), `device_batch` runs the whole transform on the device.
+np.random.rand() behind each frame's augmentation; under TTA the loop is transform._tta_draws), `device_batch` runs the whole
+transform on the device, on a raw batch (hostdata.raw_frames) with the ring in column 4.
 
 The kernel's arctan2 is a double one rounded once to float32 (atan="double", the rule of csrc/cyl_cell.h); NumPy's float32
 arctan2 (atan="numpy32", the reference's) differs from it by an ulp in about a third of the values, which moves a row to the
 neighbouring column about once in 70 000 rows. Everything else is the same arithmetic bit for bit.
 """
 import numpy as np
-import torch
 
 from . import transform
+from .hostdata import raw_frames, scene_row_offsets
 
 __all__ = ["HW", "range_view_host", "cut_value", "draw_train_params", "tta_params", "device_batch"]
 
@@ -91,18 +92,7 @@ def tta_params(num_frames, num_votes=10, scale_range=(0.9, 1.1), rng=np.random):
     """(params (num_votes * num_frames, 8), cuts (num_votes * num_frames,)), vote-major (row v * num_frames + f). The draws run in
     __getitem__ order: frame by frame, vote by vote, each vote's scale draw followed by its cut. As in transform.tta_params the
     range the reference scales by is the CONFIGURED one (the TTA branch sets `scale_aug_range` but passes `scale_range`)."""
-    if not 1 <= num_votes <= len(transform.TTA_ANGLES):
-        raise ValueError("openpcseg_amd: test-time augmentation has %d rotations, got num_votes=%d" % (len(transform.TTA_ANGLES), num_votes))
-    params = transform.identity_params(num_votes * num_frames)
-    cuts = np.empty(num_votes * num_frames, dtype=np.float64)
-    for f in range(num_frames):
-        for v in range(num_votes):
-            theta = transform.TTA_ANGLES[v] * np.pi / 8.0
-            row = params[v * num_frames + f]
-            row[0], row[1] = np.cos(theta), np.sin(theta)
-            row[2] = rng.uniform(scale_range[0], scale_range[1])
-            cuts[v * num_frames + f] = rng.rand()
-    return params, cuts
+    return transform._tta_draws(num_frames, num_votes, scale_range, rng, cut=True)
 
 
 def device_batch(raw, voxel_size=0.05, params=None, cuts=None, votes=1, eval_maps=False, hw=HW, check=True):
@@ -115,25 +105,18 @@ def device_batch(raw, voxel_size=0.05, params=None, cuts=None, votes=1, eval_map
     check: the flag of a ring outside [0, H - 1] / a row that is not finite is read (one extra host read) and raises ValueError;
     check=False hands the device flag back under "bad" (such a row keeps its pxpy row and touches no pixel)."""
     from . import native
-    pts = raw["points"]
-    if not (isinstance(pts, torch.Tensor) and pts.is_cuda):
-        raise RuntimeError("openpcseg_amd: `points` must be a HIP device tensor (got %s); the MI355X backend has no CPU path -- "
-                           "range_view_host is the host form" % (getattr(pts, "device", type(pts)),))
-    if pts.dim() != 2 or pts.shape[1] < 5:
-        raise ValueError("openpcseg_amd: rangeview.device_batch wants (n, C >= 5) points [x, y, z, reflectivity, ring], got %s" % (tuple(pts.shape),))
-    scenes = int(votes) * int(raw["num_frames"])
+    nf = raw_frames(raw, "rangeview.device_batch", "range_view_host", min_columns=5, need_labels=True)[3]
+    scenes = int(votes) * nf
     if cuts is None:
         cuts = np.full(scenes, 0.5)
     cuts = np.asarray(cuts, dtype=np.float64).reshape(-1)
     if cuts.shape[0] != scenes:
-        raise ValueError("openpcseg_amd: %d cuts for %d votes of %d frames" % (cuts.shape[0], int(votes), int(raw["num_frames"])))
+        raise ValueError("openpcseg_amd: %d cuts for %d votes of %d frames" % (cuts.shape[0], int(votes), nf))
     out = transform.device_batch(raw, voxel_size, params, votes=votes, eval_maps=eval_maps)
     lidar = out["lidar"]
     scene_col = lidar.C[:, 3]
     image, pxpy, bad = native.backend().range_project(lidar.F, scene_col, cuts, scenes, hw)
-    counts = torch.zeros(scenes, dtype=torch.int64, device=pts.device)
-    counts.scatter_add_(0, scene_col.long(), torch.ones(scene_col.shape[0], dtype=torch.int64, device=pts.device))
-    out.update(range_image=image, range_pxpy=pxpy, offset=torch.cumsum(counts, 0).int())
+    out.update(range_image=image, range_pxpy=pxpy, offset=scene_row_offsets(scene_col, scenes)[1:].int())
     if not check:
         out["bad"] = bad
     elif int(bad.item()):

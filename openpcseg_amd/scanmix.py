@@ -8,7 +8,8 @@ scans that `SemkittiDataset.__getitem__` performs under AUGMENT = 'GlobalAugment
 
 `draw_omega`, `draw_mix_plan` and `draw_train_plan` make the reference's draws in its call order (`choice(2, 1)` comes first in
 EVERY frame, ahead of aug_points' draws), `mix_scan_host` / `ring_ids_host` restate the arithmetic in NumPy -- the host path and
-the yardstick of csrc/scanmix.hip --, `device_mix` runs it on the device for a whole batch and hands back a raw batch that
+the yardstick of csrc/scanmix.hip --, `device_mix` runs it on the device for a whole batch (two raw batches read by
+hostdata.raw_frames: exactly four columns, empty input frames allowed) and hands back a raw batch that
 `transform.device_batch`, `cylinder.device_batch` and `rangeview.device_batch` take unchanged.
 
 LaserMix as the reference wrote it returns the first scan unchanged: its band thresholds are degrees (-6.7 / pi * 180 = -383.9)
@@ -21,9 +22,9 @@ is a double one rounded once (atan="double", the rule of csrc/cyl_cell.h and csr
 about a third of the values and move a row across a sector edge about twice in 1e8 tests.
 """
 import numpy as np
-import torch
 
 from . import transform
+from .hostdata import raw_frames
 
 __all__ = ["INSTANCE_CLASSES", "LASERMIX_BANDS", "POLARMIX", "LASERMIX", "NO_MIX", "draw_omega", "draw_mix_plan", "draw_train_plan",
            "mix_scan_host", "ring_ids_host", "device_mix"]
@@ -243,21 +244,6 @@ def device_plan(plan, lasermix="reference"):
     return out
 
 
-def _device_raw(raw, name):
-    pts, labels = raw["points"], raw["labels"]
-    for t, what in ((pts, "points"), (labels, "labels")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError("openpcseg_amd: `%s` of `%s` must be a HIP device tensor (got %s); the MI355X backend has no CPU path -- "
-                               "mix_scan_host is the host form" % (what, name, getattr(t, "device", type(t))))
-    if pts.dim() != 2 or pts.shape[1] != 4:
-        raise ValueError("openpcseg_amd: device_mix wants (n, 4) points [x, y, z, reflectivity] in `%s`, got %s" % (name, tuple(pts.shape)))
-    off, nf = [int(o) for o in raw["offsets"]], int(raw["num_frames"])
-    if len(off) != nf + 1 or off[0] != 0 or off[-1] != pts.shape[0] or labels.numel() != pts.shape[0] or any(
-            off[i + 1] < off[i] for i in range(nf)):
-        raise ValueError("openpcseg_amd: the frame boundaries of `%s` must cover the %d rows of its points and labels" % (name, pts.shape[0]))
-    return pts, labels.reshape(-1), off, nf
-
-
 def device_mix(raw, partner, plan, omega, ring=False, instance_classes=INSTANCE_CLASSES, lasermix="reference"):
     """mix_scan_host(atan="double") of every frame of a raw batch resident in HBM. raw, partner: dicts as
     `workloads.synthetic.make_raw_batch` returns them, tensors on the device, the same number of frames (frame f of `partner` is
@@ -268,8 +254,9 @@ def device_mix(raw, partner, plan, omega, ring=False, instance_classes=INSTANCE_
     One host read: the ten bucket counts of every frame, which size the output and make `offsets`. The plan, omega, the classes and
     both sets of frame boundaries travel in one pinned asynchronous copy. A mixed frame without rows raises ValueError."""
     from . import native
-    p1, l1, off1, nf = _device_raw(raw, "raw")
-    p2, l2, off2, nf2 = _device_raw(partner, "partner")
+    form = dict(host_form="mix_scan_host", min_columns=4, exact_columns=True, allow_empty=True, need_labels=True)
+    p1, l1, off1, nf, _ = raw_frames(raw, "device_mix's `raw`", **form)
+    p2, l2, off2, nf2, _ = raw_frames(partner, "device_mix's `partner`", **form)
     if nf != nf2:
         raise ValueError("openpcseg_amd: device_mix wants as many partner frames as frames, got %d and %d" % (nf2, nf))
     plan = _check_plan(plan, nf)

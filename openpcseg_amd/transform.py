@@ -11,6 +11,8 @@ point` after the augmentation), divided by the voxel size in float32, rounded ha
 frame's minimum. `draw_train_params` / `tta_params` draw the eight numbers from a NumPy generator in the reference's call order,
 `transform_scan_host` is the arithmetic in NumPy (the host path, and the yardstick of csrc/scantransform.hip), `device_batch` runs
 it on the device for every vote from one read of the scans and hands back what `collate_batch` / `collate_batch_tta` would.
+What a raw batch is, and the host bookkeeping shared with the other device builders (`raw_frames`, `scene_row_offsets`,
+`scene_points`, `vote_labels`), is hostdata.py's; `_tta_draws` is the one loop behind this module's and rangeview.py's `tta_params`.
 
 The float64 contract is the reference's arithmetic with the rotation ON (every shipped config): without a rotation aug_points
 never leaves float32 (a float32 array times a Python float stays float32 in NumPy), which this module does not restate.
@@ -18,7 +20,7 @@ never leaves float32 (a float32 array times a Python float stays float32 in NumP
 import numpy as np
 import torch
 
-from .hostdata import sparse_quantize_frames
+from .hostdata import raw_frames, scene_points, scene_row_offsets, sparse_quantize_frames, vote_labels
 from .sparse import SparseTensor
 
 __all__ = ["TTA_ANGLES", "identity_params", "draw_train_params", "tta_params", "transform_scan_host", "device_batch"]
@@ -59,16 +61,25 @@ def tta_params(num_frames, num_votes=10, scale_range=(0.9, 1.1), rng=np.random):
     reference's loader visits them (semantickitti_voxel.py:62-69: all votes of one index before the next).
     The TTA branch (semantickitti_voxel.py:94-110) sets `scale_aug_range = [0.95, 1.05]` but passes `scale_range`: the range the
     reference actually scales by is the CONFIGURED one, and that behaviour is kept -- `scale_range` here is that configured range."""
+    return _tta_draws(num_frames, num_votes, scale_range, rng, cut=False)[0]
+
+
+def _tta_draws(num_frames, num_votes, scale_range, rng, cut):
+    """The draws of test-time augmentation, for tta_params here and in rangeview.py -> (params, cuts), vote-major. The order is
+    the contract: frame by frame, vote by vote, the vote's scale and -- cut: the fusion dataset -- ONE rng.rand() behind it."""
     if not 1 <= num_votes <= len(TTA_ANGLES):
         raise ValueError("openpcseg_amd: test-time augmentation has %d rotations, got num_votes=%d" % (len(TTA_ANGLES), num_votes))
-    out = identity_params(num_votes * num_frames)
+    params = identity_params(num_votes * num_frames)
+    cuts = np.empty(num_votes * num_frames if cut else 0, dtype=np.float64)
     for f in range(num_frames):
         for v in range(num_votes):
             theta = TTA_ANGLES[v] * np.pi / 8.0
-            row = out[v * num_frames + f]
+            row = params[v * num_frames + f]
             row[0], row[1] = np.cos(theta), np.sin(theta)
             row[2] = rng.uniform(scale_range[0], scale_range[1])
-    return out
+            if cut:
+                cuts[v * num_frames + f] = rng.rand()
+    return params, cuts
 
 
 def transform_scan_host(points, params_row, voxel_size):
@@ -95,35 +106,18 @@ def transform_scan_host(points, params_row, voxel_size):
     return out, pc
 
 
-def _frame_bounds(raw):
-    off = [int(o) for o in raw["offsets"]]
-    nf = int(raw["num_frames"])
-    if len(off) != nf + 1:
-        raise ValueError("openpcseg_amd: %d frame boundaries for %d frames" % (len(off), nf))
-    if any(off[i + 1] <= off[i] for i in range(nf)):
-        raise ValueError("openpcseg_amd: an empty frame has no minimum to shift by (the reference fails on it too)")
-    return off, nf
-
-
 def device_batch(raw, voxel_size=0.05, params=None, votes=1, eval_maps=False):
     """Dataset transform + sparse_quantize + collate of a raw batch resident in HBM, for `votes` augmented copies of every frame
-    from one read of the scans. raw: the dict `workloads.synthetic.make_raw_batch` returns, its tensors on the device ("points"
-    (n, C) fp32 frame after frame, "labels" (n,), "offsets": host frame boundaries, "num_frames"); params: host (votes *
-    num_frames, 8) float64, vote-major (draw_train_params / tta_params), None = the identity.
+    from one read of the scans. raw: a raw batch as hostdata.raw_frames reads it (the dict `workloads.synthetic.make_raw_batch`
+    returns, its tensors on the device), labels included; params: host (votes * num_frames, 8) float64, vote-major
+    (draw_train_params / tta_params), None = the identity.
     -> {"lidar", "targets"}: SparseTensors over the voxels of votes * num_frames scenes, scene v * num_frames + f = vote v of
     frame f -- what collate_batch (votes = 1) / collate_batch_tta would hand the model. With eval_maps also "targets_mapped" and
     "inverse_map" (SparseTensors over all votes * n points; inverse_map.F = the row of every point inside its own scene) and
     "num_points" (host list, per scene). One host read (the voxel count, inside sparse_quantize_frames)."""
     from . import native
-    pts, labels = raw["points"], raw["labels"]
-    if not (isinstance(pts, torch.Tensor) and pts.is_cuda):
-        raise RuntimeError("openpcseg_amd: `points` must be a HIP device tensor (got %s); the MI355X backend has no CPU path -- "
-                           "transform_scan_host is the host form" % (getattr(pts, "device", type(pts)),))
-    off, nf = _frame_bounds(raw)
+    pts, labels, off, nf, n = raw_frames(raw, "transform.device_batch", "transform_scan_host", need_labels=True)
     v = int(votes)
-    n = pts.shape[0]
-    if off[0] != 0 or off[-1] != n:
-        raise ValueError("openpcseg_amd: the frame boundaries must cover the %d rows of `points`" % n)
     if params is None:
         params = identity_params(v * nf)
     be = native.backend()
@@ -134,10 +128,8 @@ def device_batch(raw, voxel_size=0.05, params=None, votes=1, eval_maps=False):
     out = {"lidar": SparseTensor(feats[index], vox), "targets": SparseTensor(labels[src], vox)}
     if eval_maps:
         pc = torch.cat([coords, scenes.int()[:, None]], dim=1)
-        counts = torch.zeros(v * nf + 1, dtype=torch.int64, device=pts.device)
-        counts.scatter_add_(0, vox[:, 3].long() + 1, torch.ones(vox.shape[0], dtype=torch.int64, device=pts.device))
-        first = torch.cumsum(counts, 0)   # first voxel row of every scene
-        out["targets_mapped"] = SparseTensor(labels if v == 1 else labels.repeat(v), pc)
+        first = scene_row_offsets(vox[:, 3], v * nf)   # first voxel row of every scene
+        out["targets_mapped"] = SparseTensor(vote_labels(labels, v), pc)
         out["inverse_map"] = SparseTensor(inverse - first[scenes], pc)
-        out["num_points"] = [off[f + 1] - off[f] for _ in range(v) for f in range(nf)]
+        out["num_points"] = scene_points(off, v)
     return out

@@ -27,6 +27,7 @@ from .. import functional as F
 from .. import fused, inference, native
 from .. import modules as spnn
 from ..fused import FusedBatchNorm
+from ..hostdata import raw_frames
 from ..linear import NOT_SERVED, row_linear
 from ..scatter import scatter_max
 from ..sparse import SparseTensor
@@ -335,7 +336,7 @@ class CylinderTS(nn.Module):
         `cylinder.device_batch(labels=False)` builds `vote_chunk` of them at a time from one read of the scans (None: all votes in
         one forward), the eval forward runs over the chunk, ONE hash query of the chunk's points against `logit_coords` gives
         every point its global row (as `predict` does), and per vote one launch of the prediction tail adds softmax(that row)
-        into ONE (n, num_class) fp32 tensor. The reference's forward_ensemble hands out raw per-scene logits and leaves the summing
+        into ONE (n, num_class) fp32 tensor (`inference.vote_loop`, the loop of every model's voted evaluation). The reference's forward_ensemble hands out raw per-scene logits and leaves the summing
         to its caller; summing softmax rows is the rule `inference.predict_tta` follows, and it is kept here. The decision is the
         arg-max after the last vote; `evaluator` (a SegEvaluator) gets its confusion counts from that decision only, once per
         point. -> the keys of inference.predict_tta: {"pred" (n,) int64, "votes" (n, num_class) fp32, "point_offset": host frame
@@ -345,44 +346,27 @@ class CylinderTS(nn.Module):
         from .. import cylinder, transform
         if self.training:
             raise RuntimeError("CylinderTS.predict_tta is an evaluation pass: call model.eval() first")
-        nf = int(raw["num_frames"])
-        off = [int(o) for o in raw["offsets"]]
-        n, nv = off[-1], int(num_votes)
-        chunk = nv if vote_chunk is None else max(1, min(int(vote_chunk), nv))
-        params = transform.tta_params(nf, nv, scale_range=scale_range, rng=rng)
-        be = native.backend()
-        dev = raw["points"].device
-        labels = raw["labels"].long().contiguous() if evaluator is not None else None
-        votes = pred = bad = None   # bad: the flag of a run without evaluator, made by the first launch
-        kept_logits, kept_coords = [], []
-        for v0 in range(0, nv, chunk):
-            k = min(chunk, nv - v0)
-            batch = cylinder.device_batch(raw, space_min, space_max, grid_size, self.num_class, params[v0 * nf:(v0 + k) * nf], votes=k,
-                                          labels=False)
-            with torch.inference_mode():
-                out = self.forward(batch)
-                logits = out["logits"].float().contiguous()
-                rows = F.sphashquery(F.sphash(batch["point_coord"].int()), F.sphash(out["logit_coords"])).contiguous()
-            if votes is None:
-                votes = torch.zeros((n, logits.shape[1]), dtype=torch.float32, device=dev)
-            for j in range(k):
-                last = v0 + j == nv - 1
-                rows_v = rows[j * n:(j + 1) * n]   # global rows of the logits: no offsets
-                if evaluator is not None:   # every vote's flag goes to the evaluator, the counts come from the last decision only
-                    pred = evaluator.tail(logits, labels, off, count=last, inverse=rows_v, votes=votes, want_pred=last)
-                else:
-                    pred, bad = be.predict_points(logits, inverse=rows_v, votes=votes, want_pred=last, bad=bad)
-                if return_logits:
-                    lc = out["logit_coords"]
+        nf, n = raw_frames(raw, "CylinderTS.predict_tta", "`predict` on a host-built batch")[3:]
+
+        def logits_of(batch, v0, _):
+            out = self.forward(batch)
+            logits, lc = out["logits"].float().contiguous(), out["logit_coords"]
+            rows = F.sphashquery(F.sphash(batch["point_coord"].int()), F.sphash(lc)).contiguous()
+
+            def vote(j):
+                def keep():   # the vote's logits by mask, their scene re-based from the chunk to the evaluation
                     mine = (lc[:, -1] >= j * nf) & (lc[:, -1] < (j + 1) * nf)
                     coords = lc[mine].clone()
                     coords[:, -1] += v0 * nf
-                    kept_logits.append(logits[mine])
-                    kept_coords.append(coords)
-        ret = {"pred": pred, "votes": votes, "point_offset": off, "params": params}
-        if return_logits:
-            ret["logits"], ret["logit_coords"] = kept_logits, kept_coords
-        return ret
+                    return {"logits": logits[mine], "logit_coords": coords}
+                return {"inverse": rows[j * n:(j + 1) * n]}, keep   # global rows of the logits: no offsets
+            return logits, vote
+
+        return inference.vote_loop(
+            raw, "CylinderTS.predict_tta", num_votes, vote_chunk, evaluator, return_logits,
+            lambda nf, nv: {"params": transform.tta_params(nf, nv, scale_range=scale_range, rng=rng)},
+            lambda part, k: cylinder.device_batch(raw, space_min, space_max, grid_size, self.num_class, part["params"], votes=k, labels=False),
+            logits_of)
 
 
 def cylinder_batch(samples):

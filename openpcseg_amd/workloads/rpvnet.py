@@ -211,13 +211,11 @@ class RPVNet(MinkUNet):
         from .. import rangeview
         if self.training:
             raise RuntimeError("RPVNet.predict_tta is an evaluation pass: call model.eval() first")
-        nf = int(raw["num_frames"])
-        params, cuts = rangeview.tta_params(nf, int(num_votes), scale_range=scale_range, rng=rng)
         return inference.vote_loop(
-            raw, num_votes, vote_chunk, evaluator, return_logits,
-            lambda v0, k: rangeview.device_batch(raw, self.pres, params[v0 * nf:(v0 + k) * nf], cuts[v0 * nf:(v0 + k) * nf], votes=k,
-                                                 eval_maps=True, hw=hw),
-            lambda batch: self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"]), {"params": params, "cuts": cuts})
+            raw, "RPVNet.predict_tta", num_votes, vote_chunk, evaluator, return_logits,
+            lambda nf, nv: dict(zip(("params", "cuts"), rangeview.tta_params(nf, nv, scale_range=scale_range, rng=rng))),
+            lambda part, k: rangeview.device_batch(raw, self.pres, part["params"], part["cuts"], votes=k, eval_maps=True, hw=hw),
+            lambda batch, v0, scene_votes: scene_votes(batch, self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"])))
 
     def forward(self, batch):
         logits = self.point_logits(batch["lidar"], batch["range_image"], batch["range_pxpy"])

@@ -12,7 +12,7 @@ import torch
 
 from openpcseg_amd import native
 from openpcseg_amd import transform as T
-from openpcseg_amd.hostdata import sparse_quantize
+from openpcseg_amd.hostdata import raw_frames, sparse_quantize
 from transform_cases import N_TRAIN, N_VOTES, Fixture, host_batch, raw_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -87,7 +87,7 @@ def test_empty_frame_raises():
         T.transform_scan_host(np.zeros((0, 4), dtype=np.float32), T.identity_params(1)[0], 0.05)
     raw = raw_of([np.ones((5, 4), dtype=np.float32), np.zeros((0, 4), dtype=np.float32), np.ones((3, 4), dtype=np.float32)])
     with pytest.raises(ValueError, match="empty frame"):
-        T._frame_bounds(raw)
+        raw_frames(raw, "transform.device_batch", "transform_scan_host")
 
 
 def test_host_batch_layout(fx):
