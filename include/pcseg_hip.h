@@ -737,6 +737,52 @@ int pcs_range_project_f32(const float *feats, int64_t n, int32_t c, const int32_
 int pcs_range_image_fill_f32(const int32_t *winner, const float *feats, int64_t n, int32_t c, int32_t num_scenes, int32_t H,
                              int32_t W, float *image, void *stream);
 
+/* ---- the range-view dataset's scan and its KNN label vote (csrc/rangescan.hip; added under ABI v12, additive) -----------------
+ * Replaces, for raw scans resident in HBM, LaserScan.do_range_projection + SemLaserScan.do_label_projection of
+ * R:pcseg/data/dataset/semantickitti/laserscan.py:174-238, :389-400, prepare_input_label_semantic_with_mask + generate_label of
+ * R:pcseg/data/dataset/semantickitti/semantickitti_rv.py:284-334, and KNN.forward of R:pcseg/model/segmentor/range/utils.py:291-341.
+ *   points (n, c) fp32, c >= 4: [x, y, z, remission, ...] frame after frame; frame_offsets (F + 1) int64 ON THE DEVICE, ascending
+ *   from 0 to n; labels (n) int64 or NULL (the semantic id is label & 0xFFFF); lut (lut_size) int64 ON THE DEVICE or lut_size = 0:
+ *   an id below lut_size goes through the table, any other stays; F frames, H >= 1, W >= 1, F * H * W < 2^31, 0 <= n < 2^31.
+ *   fov_down_abs, fov_total: float32(|fov_down|) and float32(|fov_down| + |fov_up|) in radians, rounded once on the host.
+ * pcs_range_scan_f32, launch 1, per point i of frame f (all float32, no multiply-add fused, each operation rounded on its own,
+ * sqrt and divisions correctly rounded):
+ *   depth = sqrt((x x + y y) + z z);  yaw = -float32(atan2(double(y), double(x)));  pitch = float32(asin(double(z / depth)));
+ *   proj_x[i] = clamp(floor(0.5 (yaw / float32(pi) + 1) W), 0, W - 1);  proj_y[i] = clamp(floor((1 - (pitch + fov_down_abs) /
+ *   fov_total) H), 0, H - 1);  unproj_range[i] = depth;  winner[f][proj_y][proj_x] = min(winner[..], float bits of depth << 32 |
+ *   index within the frame) (one 64-bit atomic): the pixel goes to the smallest depth, among equal depths to the smallest index,
+ *   whatever order the atomics retire in. A row whose x, y, z or depth is not finite, whose depth is zero or whose float32
+ *   |z / depth| exceeds 1 (z * z in the subnormals: no pitch) sets bad[0] = 1, gets
+ *   proj_x = proj_y = -1 and touches no pixel. winner is set to all ones and bad[0] to 0 by the entry (two hipMemsetAsync).
+ * Launch 2, per pixel with winner row r (index idx within its frame):
+ *   scan (F, 6, H, W) fp32 = [x / 50, y / 50, z / 3, remission, depth / 80, mask];  label_rv (F, H, W) int64 = the (mapped)
+ *   semantic id (0 without labels);  mask_rv (F, H, W) fp32 = mask_hit ? 1 : (idx > 0 ? 1 : 0) (the reference's proj_idx > 0);
+ *   proj_idx (F, H, W) int32 = idx.  An empty pixel: x = y = z = remission = depth = -1 before the divisions, mask 0, label 0,
+ *   proj_idx -1.
+ * pcs_range_scan_ws_bytes: the bytes of `winner` (8 per pixel), or -1 on sizes the entry refuses.
+ * pcs_range_knn_vote, one launch, per point i of scene b (point_offset (B + 1) int64 ON THE DEVICE), u = unproj_range[i]:
+ *   the search x search window around (proj_y[i], proj_x[i]) of proj_range (B, H, W) fp32 and proj_argmax (B, H, W) int64, range 0
+ *   and label 0 outside the image (no azimuthal wrap); a negative range becomes +inf, the centre's range u;
+ *   distance_k = |range_k - u| * weights_host[k]  (weights_host: search^2 HOST floats, 1 - the normalised gaussian, row-major;
+ *   they travel by value in the kernel arguments); the knn first candidates in ascending (distance, k) vote with their label,
+ *   those with distance > cutoff (cutoff > 0) for an extra bin; pred[i] = the class of 1 .. num_class - 1 with the most votes, the
+ *   lowest on equal counts (1 when none has any). A label outside [0, num_class), tested on all 64 bits, takes its place among
+ *   the nearest and votes for nothing. One point per lane: 0 <= n < 2^31. A point whose pixel is outside
+ *   the image (proj_x < 0: the scan's bad rows) gets pred = 0 and is not counted.
+ *   hist (num_class, num_class) int64 or NULL: hist[labels[i]][pred[i]] += 1 for labels in [0, num_class); needs labels (n).
+ *   Accumulates: integer sums, exact and run-to-run identical.
+ *   search in {3, 5, 7}, 1 <= knn <= search^2, cutoff >= 0 (0 = off), 2 <= num_class <= 64: anything else is PCS_EINVAL.
+ * Sizes are checked before any pointer: bad sizes give PCS_EINVAL also with null pointers. Nothing allocates, nothing is read back. */
+int64_t pcs_range_scan_ws_bytes(int32_t num_frames, int32_t H, int32_t W);
+int pcs_range_scan_f32(const float *points, int64_t n, int32_t c, const int64_t *frame_offsets, int32_t num_frames,
+                       const int64_t *labels, const int64_t *lut, int32_t lut_size, int32_t H, int32_t W, float fov_down_abs,
+                       float fov_total, int32_t mask_hit, void *winner, float *scan, int64_t *label_rv, float *mask_rv,
+                       int32_t *proj_idx, int32_t *proj_x, int32_t *proj_y, float *unproj_range, int32_t *bad, void *stream);
+int pcs_range_knn_vote(const float *proj_range, const int64_t *proj_argmax, int32_t num_scenes, int32_t H, int32_t W,
+                       const float *unproj_range, const int32_t *proj_x, const int32_t *proj_y, int64_t n,
+                       const int64_t *point_offset, int32_t search, int32_t knn, float cutoff, const float *weights_host,
+                       int32_t num_class, const int64_t *labels, int64_t *hist, int64_t *pred, void *stream);
+
 /* ---- PolarMix / LaserMix of two raw batches (csrc/scanmix.hip; added under ABI v12, additive) ---------------------------
  * Replaces, for scans resident in HBM, the mixing of two scans in R:pcseg/data/dataset/semantickitti/semantickitti.py:117-170
  * (polarmix of PolarMix_semantickitti.py, lasermix_aug of LaserMix_semantickitti.py, get_kitti_points_ringID :86-96).

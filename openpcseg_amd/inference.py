@@ -428,6 +428,19 @@ class SegEvaluator:
         self.last_offsets = offsets
         return pred
 
+    def counters(self, num_class, device, offsets, count=True):
+        """For a prediction tail that counts inside its OWN launch (rangescan.predict's KNN vote, where `tail` serves predict_points):
+        checks the class count, records `offsets` (host) as `last_offsets` and hands out the (num_class, num_class) int64 histogram
+        to add hist[label][pred] into, made on `device` at first use. count=False (nothing to count, e.g. no labels): None, and
+        the evaluator's tensors are not made."""
+        if int(num_class) != self.num_class:
+            raise ValueError("openpcseg_amd: %d classes for a %d-class evaluator" % (int(num_class), self.num_class))
+        self.last_offsets = offsets
+        if not count:
+            return None
+        self._ensure(device)
+        return self.hist
+
     def update(self, logits, batch, votes=None):
         """hist[label][pred] += 1 over the batch's points (labels: batch["targets_mapped"]). -> pred (flat, on the device)."""
         if batch.get("targets_mapped") is None:

@@ -134,6 +134,11 @@ SIGNATURES = {
     "pcs_range_project_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "pcs_range_project_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "pcs_range_image_fill_f32": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "pcs_range_scan_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "pcs_range_scan_f32": (c_int32, [_P, c_int64, c_int32, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, c_int32,
+                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pcs_range_knn_vote": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P, c_int32, c_int32, c_float, _P, c_int32,
+                                     _P, _P, _P, _P]),
     "pcs_scan_mix_ws_bytes": (c_int64, [c_int64, c_int64, c_int32]),
     "pcs_scan_mix_count": (c_int32, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int32, _P, _P, c_int32, _P, c_int64, _P, _P, _P]),
     "pcs_scan_mix_place": (c_int32, [_P, _P, c_int64, _P, _P, _P, c_int64, _P, c_int32, _P, _P, c_int32, _P, _P, c_int64, _P, _P, c_int64,
@@ -176,7 +181,7 @@ class _StepHyper(ctypes.Structure):   # pcs_step_hyper of include/pcseg_hip.h
                 ("nesterov", c_int32 * STEP_MAX_GROUPS), ("n_groups", c_int32)]
 
 
-ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_step_plan / pcs_step_norm / pcs_step_apply, pcs_scan_mix_* / pcs_scan_ring_*, pcs_range_project_* / pcs_range_image_fill_f32, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
+ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_step_plan / pcs_step_norm / pcs_step_apply, pcs_scan_mix_* / pcs_scan_ring_*, pcs_range_project_* / pcs_range_image_fill_f32, pcs_range_scan_* / pcs_range_knn_vote, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
 _lib = None
 
 
@@ -1520,6 +1525,82 @@ class HipBackend:
                                               _stream()), "pcs_range_project_f32")
         _check(self.lib.pcs_range_image_fill_f32(_ptr(winner), _ptr(feats), n, c, s, h, w, _ptr(image), _stream()), "pcs_range_image_fill_f32")
         return image, pxpy, bad
+
+    # -- the range-view dataset's scan and its KNN vote (csrc/rangescan.hip) ---------------------------------
+    def range_scan(self, points, offsets, labels, hw, fov_consts, label_lut=None, mask_hit=False):
+        """The range-view scan of a raw batch (rangescan.py): points (n, c >= 4) fp32, offsets: HOST list of
+        num_frames + 1 boundaries, labels (n,) int64 or None, fov_consts = (float32 |fov_down|, float32 total) in radians,
+        label_lut: host table or None -> dict of scan_rv (F, 6, H, W) fp32, label_rv (F, H, W) int64, mask_rv (F, H, W) fp32,
+        proj_idx (F, H, W) int32, proj_x / proj_y (n,) int32, unproj_range (n,) fp32, bad (1,) int32 device flag. The boundaries
+        and the table travel in ONE pinned asynchronous copy; nothing is read back."""
+        points = _dev(points, "points", torch.float32)
+        if points.dim() != 2 or points.shape[1] < 4:
+            raise ValueError("openpcseg_amd: range_scan wants (n, c >= 4) rows [x, y, z, remission], got %s" % (tuple(points.shape),))
+        if labels is not None:
+            labels = _dev(labels, "labels", torch.int64)
+        n, c = points.shape
+        nf, (h, w) = len(offsets) - 1, (int(v) for v in hw)
+        ws_bytes = self.lib.pcs_range_scan_ws_bytes(nf, h, w)
+        if ws_bytes < 0:
+            _check(-1, "pcs_range_scan_ws_bytes")
+        dev = points.device
+        lut = [] if label_lut is None else [int(v) for v in label_lut]
+        table = _h2d([int(o) for o in offsets] + lut, torch.int64, dev)
+        off_d, lut_d = table[:nf + 1], table[nf + 1:]
+        winner = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+        out = {"scan_rv": torch.empty((nf, 6, h, w), dtype=torch.float32, device=dev),
+               "label_rv": torch.empty((nf, h, w), dtype=torch.int64, device=dev),
+               "mask_rv": torch.empty((nf, h, w), dtype=torch.float32, device=dev),
+               "proj_idx": torch.empty((nf, h, w), dtype=torch.int32, device=dev),
+               "proj_x": torch.empty(n, dtype=torch.int32, device=dev), "proj_y": torch.empty(n, dtype=torch.int32, device=dev),
+               "unproj_range": torch.empty(n, dtype=torch.float32, device=dev), "bad": torch.empty(1, dtype=torch.int32, device=dev)}
+        _check(self.lib.pcs_range_scan_f32(_ptr(points), n, c, _ptr(off_d), nf, _ptr(labels), _ptr(lut_d), len(lut), h, w,
+                                           float(fov_consts[0]), float(fov_consts[1]), int(bool(mask_hit)), _ptr(winner),
+                                           _ptr(out["scan_rv"]), _ptr(out["label_rv"]), _ptr(out["mask_rv"]), _ptr(out["proj_idx"]),
+                                           _ptr(out["proj_x"]), _ptr(out["proj_y"]), _ptr(out["unproj_range"]), _ptr(out["bad"]),
+                                           _stream()), "pcs_range_scan_f32")
+        return out
+
+    def range_knn_vote(self, proj_range, proj_argmax, unproj_range, proj_x, proj_y, point_offset, knn, search, weights, cutoff,
+                       num_class, labels=None, hist=None):
+        """The KNN label vote of a batch in one launch (rangescan.knn_vote): proj_range (B, H, W) fp32, proj_argmax (B, H, W) int64,
+        unproj_range (n,) fp32, proj_x / proj_y (n,) int32, point_offset: HOST list of B + 1 boundaries, weights: host (search^2,)
+        float32 -> pred (n,) int64. labels (n,) int64 + hist (num_class, num_class) int64 (updated in place) count in the launch."""
+        import numpy as np
+        proj_range = _dev(proj_range, "proj_range", torch.float32)
+        proj_argmax = _dev(proj_argmax, "proj_argmax", torch.int64)
+        if proj_range.dim() != 3 or tuple(proj_argmax.shape) != tuple(proj_range.shape):
+            raise ValueError("openpcseg_amd: range_knn_vote wants (B, H, W) proj_range and proj_argmax, got %s and %s"
+                             % (tuple(proj_range.shape), tuple(proj_argmax.shape)))
+        b, h, w = proj_range.shape
+        unproj_range = _dev(unproj_range, "unproj_range", torch.float32).reshape(-1)
+        proj_x, proj_y = _dev(proj_x, "proj_x", torch.int32).reshape(-1), _dev(proj_y, "proj_y", torch.int32).reshape(-1)
+        n = unproj_range.numel()
+        off = [int(o) for o in point_offset]
+        if proj_x.numel() != n or proj_y.numel() != n or len(off) != b + 1 or off[0] != 0 or off[-1] != n or any(
+                off[i + 1] < off[i] for i in range(b)):
+            raise ValueError("openpcseg_amd: range_knn_vote wants one pixel and one range per point and %d boundaries ascending from 0 "
+                             "to the %d points, got %s" % (b + 1, n, off))
+        weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if weights.shape[0] != int(search) ** 2:
+            raise ValueError("openpcseg_amd: range_knn_vote wants search^2 weights, got %d" % weights.shape[0])
+        dev = proj_range.device
+        if labels is not None:
+            labels = _dev(labels, "labels", torch.int64).reshape(-1)
+            if labels.numel() != n:
+                raise ValueError("openpcseg_amd: %d labels for %d points" % (labels.numel(), n))
+        if hist is not None:
+            if hist.dtype != torch.int64 or not hist.is_cuda or not hist.is_contiguous() or tuple(hist.shape) != (num_class, num_class):
+                raise ValueError("openpcseg_amd: hist must be a contiguous (%d, %d) int64 device tensor (updated in place)"
+                                 % (num_class, num_class))
+            if labels is None:
+                raise ValueError("openpcseg_amd: hist needs labels")
+        off_d = _h2d(off, torch.int64, dev)
+        pred = torch.empty(n, dtype=torch.int64, device=dev)
+        _check(self.lib.pcs_range_knn_vote(_ptr(proj_range), _ptr(proj_argmax), b, h, w, _ptr(unproj_range), _ptr(proj_x), _ptr(proj_y), n,
+                                           _ptr(off_d), int(search), int(knn), float(cutoff), weights.ctypes.data_as(c_void_p),
+                                           int(num_class), _ptr(labels), _ptr(hist), _ptr(pred), _stream()), "pcs_range_knn_vote")
+        return pred
 
     # -- PolarMix / LaserMix of two raw batches (csrc/scanmix.hip) -------------------------------------------
     def scan_mix(self, points1, labels1, offsets1, points2, labels2, offsets2, plan, omega, classes, ring=False):
