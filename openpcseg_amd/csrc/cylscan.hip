@@ -3,15 +3,15 @@
 // semantickitti_cylinder.py:104-160: aug_points, the augmented xyz stored back as float32, cart2polar, the partition), once per
 // vote under test-time augmentation (:92-99, ten votes per frame). Here, for every raw row i of frame f and every vote v, with
 // the parameter row of (v, f):
-//   (x', y', z') = affine_row(x, y, z)          scan_affine.h -- float64, the order of section 7h, one rounding to float32
+//   (x', y', z') = affine_row(x, y, z)          raw_scan.h    -- float64, the order of section 7h, one rounding to float32
 //   pol, cell, centre = cyl_cell(x', y', z')    cyl_cell.h    -- the arithmetic of cyl_partition_kernel
 //   feat  row v * n + i = [centre (3), rho, phi in degrees, z', x', y', extras...]      (8 + c - 3 floats)
 //   coord row v * n + i = cell;  scenes[v * n + i] = v * F + f
 // Cells are >= 0 after the clip: no minimum, no ticket, no workspace. Traffic: the scan is read once (4 c B per row) whatever
 // the number of votes; per vote 4 (8 + c - 3) + 12 + 8 B are written (56 B at c = 4).
 // A workgroup stays inside one frame (the frame is a grid axis), the grid along a frame is sized to the chip, the V parameter
-// rows sit in LDS. The store: a feature row is 36 B at c = 4, so a lane that writes its own row issues nine dword stores at a
-// 36-byte stride. Per vote the workgroup's 256 rows are ONE contiguous range of `feat` (and of `coord`): the staged form puts
+// rows sit in LDS: the row range of a frame, the row load, the staging, the grid and the vote dispatch are raw_scan.h's.
+// The store: a feature row is 36 B at c = 4, so a lane that writes its own row issues nine dword stores at a 36-byte stride. Per vote the workgroup's 256 rows are ONE contiguous range of `feat` (and of `coord`): the staged form puts
 // the range into LDS (an odd row width falls on distinct banks as it is, an even one is skewed by a pad word per 64) and writes
 // it out with consecutive lanes on consecutive addresses -- 16-byte stores over the aligned middle, dwords at the head and the
 // tail, because the range starts at (v n + i0) (8 + c - 3) 4 bytes. Two LDS buffers alternate, so a vote costs one barrier.
@@ -23,14 +23,14 @@
 
 #include "cyl_cell.h"
 #include "pcs_common.h"
-#include "scan_affine.h"
+#include "raw_scan.h"
 
 using namespace pcs;
 
 namespace {
 
 constexpr int kBlock = kScanBlock;
-constexpr int kMaxExtra = PCS_SCAN_MAX_COLUMNS - 3;
+constexpr int kMaxExtra = kScanMaxExtra;
 
 enum StoreForm { kStaged = 0, kDirect = 1, kStagedFeat = 2 };
 
@@ -100,13 +100,12 @@ __global__ void __launch_bounds__(kBlock) cyl_scan_kernel(const float *__restric
   __shared__ __align__(16) float fstage[2][ROW16 ? kStageWords : kStageWords + kStageWords / 64 + 1];   // general width: skewed
   __shared__ __align__(16) int32_t cstage[2][kBlock * 3 + 4];
   const int f = blockIdx.y, tid = threadIdx.x;
-  int64_t lo = frame_offsets[f], hi = frame_offsets[f + 1];
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > n ? n : hi;   // nothing outside the votes * n rows is ever addressed, whatever the offsets say
+  const FrameRows fr = frame_rows(frame_offsets, f, n);
+  const int64_t lo = fr.lo, hi = fr.hi;
   if (hi <= lo) return;   // an empty frame writes nothing
   const int64_t want = (hi - lo + kBlock - 1) / kBlock;
   if ((int64_t)blockIdx.x >= want) return;   // the same for the whole workgroup
-  for (int j = tid; j < V * 8; j += kBlock) sp[j] = params[((int64_t)(j >> 3) * F + f) * 8 + (j & 7)];
+  stage_params(sp, params, V, F, f);
   if (tid == 0) scfg = cfg;
   __syncthreads();
   const int extras = ROW16 ? 1 : C - 3, fdim = 8 + extras;
@@ -114,27 +113,14 @@ __global__ void __launch_bounds__(kBlock) cyl_scan_kernel(const float *__restric
   for (int64_t base = lo + (int64_t)blockIdx.x * kBlock; base < hi; base += (int64_t)gridDim.x * kBlock) {
     const int rows = hi - base < kBlock ? (int)(hi - base) : kBlock;   // this round's rows of the workgroup: base .. base + rows
     const bool live = tid < rows;
-    float x = 0.f, y = 0.f, z = 0.f, extra[kMaxExtra];
-#pragma unroll
-    for (int k = 0; k < kMaxExtra; ++k) extra[k] = 0.f;
-    if (live) {
-      if (ROW16) {
-        const float4 r = *reinterpret_cast<const float4 *>(pts + (base + tid) * 4);
-        x = r.x; y = r.y; z = r.z; extra[0] = r.w;
-      } else {
-        const float *p = pts + (base + tid) * C;
-        x = p[0]; y = p[1]; z = p[2];
-#pragma unroll
-        for (int k = 0; k < kMaxExtra; ++k)
-          if (k < extras) extra[k] = p[3 + k];
-      }
-    }
+    RawRow r = {};
+    if (live) r = load_raw_row<ROW16>(pts, base + tid, C);
 #pragma unroll kUnroll
     for (int v = 0; v < VB; ++v) {
       if (v >= V) continue;   // uniform; a constant trip count, so that the loop unrolls around its barrier
       float fx, fy, fz, pol[3], centre[3];
       int idx[3];
-      affine_row(x, y, z, sp + v * 8, fx, fy, fz);
+      affine_row(r.x, r.y, r.z, sp + v * 8, fx, fy, fz);
       cyl_cell(fx, fy, fz, scfg, pol, idx, centre);
       const float head[8] = {centre[0], centre[1], centre[2], pol[0], pol[1], pol[2], fx, fy};
       const int64_t row0 = (int64_t)v * n + base;   // first output row of the workgroup's range under this vote
@@ -148,7 +134,7 @@ __global__ void __launch_bounds__(kBlock) cyl_scan_kernel(const float *__restric
           for (int k = 0; k < 8; ++k) o[k] = head[k];
 #pragma unroll
           for (int k = 0; k < kMaxExtra; ++k)
-            if (k < extras) o[8 + k] = extra[k];
+            if (k < extras) o[8 + k] = r.extra[k];
         }
       } else {
         const int w0 = word_phase(fdst) + tid * fdim;   // the row's first word of the staged range
@@ -158,7 +144,7 @@ __global__ void __launch_bounds__(kBlock) cyl_scan_kernel(const float *__restric
           for (int k = 0; k < 8; ++k) s[stage_at<!ROW16>(w0 + k)] = head[k];
 #pragma unroll
           for (int k = 0; k < kMaxExtra; ++k)
-            if (k < extras) s[stage_at<!ROW16>(w0 + 8 + k)] = extra[k];
+            if (k < extras) s[stage_at<!ROW16>(w0 + 8 + k)] = r.extra[k];
         }
       }
       if (form != kStaged) {
@@ -175,18 +161,6 @@ __global__ void __launch_bounds__(kBlock) cyl_scan_kernel(const float *__restric
       }
     }
   }
-}
-
-// 256 CUs x 4 workgroups of the light instances (<= 4 votes), x 2 of the heavy ones, as the transform's
-int scan_grid(int64_t n, int num_frames, int num_votes) { return frame_grid(n, 1, num_frames, num_votes <= 4 ? 1024 : 512); }
-
-template <int VB>
-void launch_scan(bool row16, dim3 grid, hipStream_t st, const float *pts, int64_t n, int C, const int64_t *fo, int F,
-                 const double *params, int V, const CylCfg &cfg, int form, float *feat, int32_t *coord, int64_t *scenes) {
-  if (row16)
-    hipLaunchKernelGGL((cyl_scan_kernel<VB, true>), grid, dim3(kBlock), 0, st, pts, n, C, fo, F, params, V, cfg, form, feat, coord, scenes);
-  else
-    hipLaunchKernelGGL((cyl_scan_kernel<VB, false>), grid, dim3(kBlock), 0, st, pts, n, C, fo, F, params, V, cfg, form, feat, coord, scenes);
 }
 
 }  // namespace
@@ -214,14 +188,11 @@ extern "C" int pcs_cylinder_scan_batch_f32(const float *points, int64_t n, int32
     return PCS_EINVAL;
   }
   const bool row16 = c == 4 && ((uintptr_t)points & 15) == 0;
-  const dim3 grid(scan_grid(n, num_frames, num_votes), num_frames);
+  const dim3 grid(vote_grid(n, num_frames, num_votes), num_frames);
   const int form = g_store_override >= 0 ? g_store_override : store_env();
-#define PCS_CYLSCAN_LAUNCH(VB) \
-  launch_scan<VB>(row16, grid, as_stream(stream), points, n, c, frame_offsets, num_frames, params, num_votes, cfg, form, feat, coord, scenes)
-  if (num_votes == 1) PCS_CYLSCAN_LAUNCH(1);
-  else if (num_votes <= 4) PCS_CYLSCAN_LAUNCH(4);
-  else if (num_votes <= 10) PCS_CYLSCAN_LAUNCH(10);
-  else PCS_CYLSCAN_LAUNCH(PCS_SCAN_MAX_VOTES);
-#undef PCS_CYLSCAN_LAUNCH
+  dispatch_votes(num_votes, row16, [&](auto vb, auto r16) {
+    hipLaunchKernelGGL((cyl_scan_kernel<decltype(vb)::value, decltype(r16)::value>), grid, dim3(kBlock), 0, as_stream(stream), points, n,
+                       c, frame_offsets, num_frames, params, num_votes, cfg, form, feat, coord, scenes);
+  });
   return check_launch("pcs_cylinder_scan_batch_f32");
 }

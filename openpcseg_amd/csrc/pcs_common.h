@@ -13,6 +13,28 @@ void set_error(const char *fmt, ...);
 // wave width on CDNA4; hard-coded on purpose (guide: never assume 32)
 constexpr int kWave = 64;
 
+// reductions and the inclusive scan over one wave
+__device__ __forceinline__ int wave_min(int v) {
+  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <typename T>   // int, int64_t; `lane` is the caller's lane of the wave
+__device__ __forceinline__ T wave_inclusive(T v, int lane) {
+  for (int o = 1; o < kWave; o <<= 1) {
+    const T t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int check_launch(const char *what) {
@@ -22,6 +44,21 @@ inline int check_launch(const char *what) {
     return PCS_ELAUNCH;
   }
   return PCS_OK;
+}
+
+// the one refusal of a workspace that is smaller than its size query says
+inline int ws_too_small(const char *what, int64_t have, int64_t need) {
+  set_error("%s: workspace of %lld bytes, %lld needed", what, (long long)have, (long long)need);
+  return PCS_EWORKSPACE;
+}
+
+// hipMemsetAsync whose failure is the entry's PCS_ELAUNCH
+inline int fill_async(const char *what, hipStream_t stream, void *ptr, int byte, size_t bytes) {
+  const hipError_t e = hipMemsetAsync(ptr, byte, bytes, stream);
+  if (e == hipSuccess) return PCS_OK;
+  (void)hipGetLastError();
+  set_error("%s: hipMemsetAsync failed: %s", what, hipGetErrorString(e));
+  return PCS_ELAUNCH;
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -8,14 +8,19 @@
 //   hist[labels[i]][pred[i]] += 1         for labels in [0, c)  (fast_hist's mask)
 // One thread per point, 16-byte row loads when c % 4 == 0. The confusion matrix is counted per workgroup in LDS (int32, c * c
 // cells: 1.6 KB at c = 20) and flushed once per workgroup with 64-bit global atomic adds of the non-zero cells: integer sums,
-// so the result is exact and identical from run to run. A row outside its scene is refused BEFORE an address is formed.
+// so the result is exact and identical from run to run (lds_hist_* of raw_scan.h, shared with the KNN vote of rangescan.hip, as is
+// span_of: the scene whose span holds a point). A row outside its scene is refused BEFORE an address is formed.
 #include <math.h>
 
 #include "pcs_common.h"
+#include "raw_scan.h"
 
 using namespace pcs;
 
 namespace {
+
+constexpr int kBlock = 256;   // the kernel's launch bound AND its launch
+static_assert(kBlock == kScanBlock, "lds_hist_clear / lds_hist_flush stride by kScanBlock: the workgroup must have as many lanes");
 
 struct PredictArgs {
   const float *logits;
@@ -95,22 +100,17 @@ __device__ __forceinline__ int row_vote(const float *__restrict__ x, float *__re
 }
 
 template <bool VEC>
-__global__ void __launch_bounds__(256) predict_points_kernel(PredictArgs a) {
-  extern __shared__ int32_t lhist[];   // c * c cells when a.hist, else nothing
+__global__ void __launch_bounds__(kBlock) predict_points_kernel(PredictArgs a) {
+  int32_t *lhist = lds_hist();   // c * c cells when a.hist, else nothing
   const int c = a.c, cells = a.hist ? c * c : 0;
-  for (int j = threadIdx.x; j < cells; j += blockDim.x) lhist[j] = 0;
+  lds_hist_clear(lhist, cells);
   if (cells) __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
     int64_t r = a.inverse ? a.inverse[i] : i;
     int64_t base = 0, rows = a.m;
     bool ok = true;
     if (a.n_scenes > 0) {
-      // the scene whose point span holds i: the last b with point_offset[b] <= i
-      int lo = 0, hi = a.n_scenes;
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.point_offset[mid] <= i) lo = mid; else hi = mid;
-      }
+      const int lo = span_of(a.point_offset, a.n_scenes, i);   // the scene whose point span holds i
       ok = i >= a.point_offset[lo] && i < a.point_offset[lo + 1];
       base = a.row_offset[lo];
       rows = a.row_offset[lo + 1] - base;
@@ -125,17 +125,11 @@ __global__ void __launch_bounds__(256) predict_points_kernel(PredictArgs a) {
       atomicOr(a.bad, 1);
     }
     if (a.pred) a.pred[i] = p;
-    if (cells && p >= 0) {
-      const int64_t l = a.labels[i];
-      if (l >= 0 && l < c) atomicAdd(&lhist[(int)l * c + p], 1);
-    }
+    if (cells && p >= 0) lds_hist_count(lhist, c, a.labels[i], p);
   }
   if (cells) {
     __syncthreads();
-    for (int j = threadIdx.x; j < cells; j += blockDim.x) {
-      const int32_t v = lhist[j];
-      if (v) atomicAdd(reinterpret_cast<unsigned long long *>(a.hist) + j, (unsigned long long)v);
-    }
+    lds_hist_flush(lhist, cells, a.hist);
   }
 }
 
@@ -159,7 +153,7 @@ extern "C" int pcs_predict_points_f32(const float *logits, int64_t m, int32_t c,
   a.labels = labels; a.votes = votes; a.pred = pred; a.hist = hist; a.bad = bad_flag;
   const bool vec = c % 4 == 0 && (((uintptr_t)logits | (uintptr_t)votes) & 15) == 0;
   const size_t lds = hist ? (size_t)c * c * sizeof(int32_t) : 0;
-  const dim3 grid(stream_grid(n, 256)), block(256);
+  const dim3 grid(stream_grid(n, kBlock)), block(kBlock);
   if (vec)
     hipLaunchKernelGGL(predict_points_kernel<true>, grid, block, lds, as_stream(stream), a);
   else

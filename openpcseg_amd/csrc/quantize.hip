@@ -14,15 +14,6 @@ using namespace pcs;
 
 namespace {
 
-__device__ __forceinline__ int wave_min(int v) {
-  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
-  return v;
-}
-
 // bbox[0..2] = min, bbox[3..5] = max (initialised to INT_MAX / INT_MIN by the caller)
 template <typename TIn>
 __global__ void __launch_bounds__(256) quantize_floor_kernel(const TIn *__restrict__ pts, int64_t n, int stride,

@@ -16,14 +16,13 @@
 #include <math.h>
 
 #include "pcs_common.h"
+#include "raw_scan.h"   // kPiF, kTwoPiF
 
 using namespace pcs;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr float kPiF = 3.14159265358979323846f;        // float32(np.pi)
-constexpr float kTwoPiF = 6.28318530717958647692f;     // float32(2 * np.pi)
+constexpr int kBlock = kScanBlock;
 
 bool range_sizes_ok(int32_t S, int32_t H, int32_t W) {
   return S >= 1 && H >= 2 && W >= 2 && (int64_t)S * H * W < ((int64_t)1 << 31);
@@ -152,12 +151,8 @@ extern "C" int pcs_range_project_f32(const float *feats, int64_t n, int32_t c, c
     return PCS_EINVAL;
   }
   hipStream_t st = as_stream(stream);
-  if (hipMemsetAsync(winner, 0xFF, (size_t)num_scenes * H * W * sizeof(int32_t), st) != hipSuccess ||
-      hipMemsetAsync(bad, 0, sizeof(int32_t), st) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("pcs_range_project_f32: hipMemsetAsync failed");
-    return PCS_ELAUNCH;
-  }
+  if (const int rc = fill_async("pcs_range_project_f32", st, winner, 0xFF, (size_t)num_scenes * H * W * sizeof(int32_t))) return rc;
+  if (const int rc = fill_async("pcs_range_project_f32", st, bad, 0, sizeof(int32_t))) return rc;
   if (n == 0) return PCS_OK;
   hipLaunchKernelGGL(range_project_kernel, dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, feats, n, (int)c, scenes, cuts32,
                      (int)num_scenes, (int)H, (int)W, winner, pxpy, bad);

@@ -17,35 +17,27 @@
 //                             unrolled pairwise comparisons -- rank of a candidate = the candidates ahead of it in (distance,
 //                             position) order; votes of a candidate's class = the selected candidates with its class -- so every
 //                             array index is a compile-time constant and nothing goes to scratch. The optional confusion matrix is
-//                             counted per workgroup in LDS and flushed with 64-bit atomic adds, as csrc/predict.hip does.
+//                             counted per workgroup in LDS and flushed with 64-bit atomic adds: lds_hist_* of raw_scan.h, shared
+//                             with csrc/predict.hip, as is span_of (the frame or scene whose rows hold a point).
 // Traffic per point at c = 4: the projection reads 16 B (+ 8 B of offsets, cached) and writes 12 B plus one atomic; the pixel pass
 // reads 8 B and gathers 16 (+ 8) B per hit pixel and writes 40 B per pixel; the vote reads 12 B per point and S^2 x 12 B of the two
 // images through the caches and writes 8 B.
 #include <math.h>
 
 #include "pcs_common.h"
+#include "raw_scan.h"
 
 using namespace pcs;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr float kPiF = 3.14159265358979323846f;   // float32(np.pi)
+constexpr int kBlock = 256;   // every kernel's launch bound AND its launch
+static_assert(kBlock == kScanBlock, "lds_hist_clear / lds_hist_flush stride by kScanBlock: the workgroup must have as many lanes");
 constexpr unsigned long long kEmptyPixel = ~0ULL;
 constexpr int kMaxClass = 64;
 
-bool scan_sizes_ok(int32_t S, int32_t H, int32_t W) {
+bool image_sizes_ok(int32_t S, int32_t H, int32_t W) {
   return S >= 1 && H >= 1 && W >= 1 && (int64_t)S * H * W < ((int64_t)1 << 31);
-}
-
-// the frame whose rows hold i: the last f with off[f] <= i (off ascending, off[0] = 0)
-__device__ __forceinline__ int frame_of(const int64_t *__restrict__ off, int F, int64_t i) {
-  int lo = 0, hi = F;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 struct ScanArgs {
@@ -73,7 +65,7 @@ __global__ void __launch_bounds__(kBlock) range_scan_point_kernel(ScanArgs a) {
     d = d + yy;
     d = d + zz;
     const float depth = sqrtf(d);
-    const int f = frame_of(a.off, a.F, i);
+    const int f = span_of(a.off, a.F, i);
     const int64_t local = i - a.off[f];
     const float ratio = z / depth;
     // every comparison is false for a NaN: a row that is not finite anywhere fails here, before any address is formed. |z / depth|
@@ -161,16 +153,16 @@ template <int S>
 __global__ void __launch_bounds__(kBlock) range_knn_vote_kernel(VoteArgs a) {
 #pragma clang fp contract(off)
   constexpr int K = S * S, PAD = (S - 1) / 2, CENTRE = (K - 1) / 2;
-  extern __shared__ int32_t lhist[];   // num_class^2 cells when a.hist, else nothing
+  int32_t *lhist = lds_hist();   // num_class^2 cells when a.hist, else nothing
   const int nc = a.num_class, cells = a.hist ? nc * nc : 0;
-  for (int j = threadIdx.x; j < cells; j += kBlock) lhist[j] = 0;
+  lds_hist_clear(lhist, cells);
   if (cells) __syncthreads();
   const int64_t plane = (int64_t)a.H * a.W;
   // ONE point per lane, no grid stride: in a loop the compiler keeps every kernel argument, the S * S weights among them, in scalar
   // registers across the iterations and spills them (102 for S = 7). The loop below runs once; it is a loop for its `continue`.
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   for (bool once = i < a.n; once; once = false) {
-    const int b = frame_of(a.off, a.B, i);
+    const int b = span_of(a.off, a.B, i);
     const int px = a.px[i], py = a.py[i];
     // the pixel is checked before any address is formed; a bad point predicts 0 and is not counted
     if (!(i >= a.off[b] && i < a.off[b + 1] && px >= 0 && px < a.W && py >= 0 && py < a.H)) {
@@ -239,24 +231,18 @@ __global__ void __launch_bounds__(kBlock) range_knn_vote_kernel(VoteArgs a) {
     }
     const int p = 127 - (best & 127);
     a.pred[i] = p;
-    if (cells) {
-      const int64_t l = a.labels[i];
-      if (l >= 0 && l < nc) atomicAdd(&lhist[(int)l * nc + p], 1);
-    }
+    if (cells) lds_hist_count(lhist, nc, a.labels[i], p);
   }
   if (cells) {
     __syncthreads();
-    for (int j = threadIdx.x; j < cells; j += kBlock) {
-      const int32_t v = lhist[j];
-      if (v) atomicAdd(reinterpret_cast<unsigned long long *>(a.hist) + j, (unsigned long long)v);
-    }
+    lds_hist_flush(lhist, cells, a.hist);
   }
 }
 
 }  // namespace
 
 extern "C" int64_t pcs_range_scan_ws_bytes(int32_t num_frames, int32_t H, int32_t W) {
-  if (!scan_sizes_ok(num_frames, H, W)) {
+  if (!image_sizes_ok(num_frames, H, W)) {
     set_error("pcs_range_scan_ws_bytes: bad sizes (frames >= 1, H >= 1, W >= 1, frames * H * W < 2^31)");
     return -1;
   }
@@ -268,7 +254,7 @@ extern "C" int pcs_range_scan_f32(const float *points, int64_t n, int32_t c, con
                                   float fov_down_abs, float fov_total, int32_t mask_hit, void *winner, float *scan,
                                   int64_t *label_rv, float *mask_rv, int32_t *proj_idx, int32_t *proj_x, int32_t *proj_y,
                                   float *unproj_range, int32_t *bad, void *stream) {
-  if (!scan_sizes_ok(num_frames, H, W) || c < 4 || n < 0 || n >= ((int64_t)1 << 31) || lut_size < 0 || !(fov_total > 0.f) ||
+  if (!image_sizes_ok(num_frames, H, W) || c < 4 || n < 0 || n >= ((int64_t)1 << 31) || lut_size < 0 || !(fov_total > 0.f) ||
       !isfinite(fov_total) || !isfinite(fov_down_abs)) {
     set_error("pcs_range_scan_f32: bad args (0 <= n < 2^31, c >= 4, frames >= 1, H >= 1, W >= 1, frames * H * W < 2^31, "
               "lut_size >= 0, finite fov with a positive total)");
@@ -281,12 +267,8 @@ extern "C" int pcs_range_scan_f32(const float *points, int64_t n, int32_t c, con
   }
   hipStream_t st = as_stream(stream);
   const int64_t pixels = (int64_t)num_frames * H * W;
-  if (hipMemsetAsync(winner, 0xFF, (size_t)pixels * sizeof(unsigned long long), st) != hipSuccess ||
-      hipMemsetAsync(bad, 0, sizeof(int32_t), st) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("pcs_range_scan_f32: hipMemsetAsync failed");
-    return PCS_ELAUNCH;
-  }
+  if (const int rc = fill_async("pcs_range_scan_f32", st, winner, 0xFF, (size_t)pixels * sizeof(unsigned long long))) return rc;
+  if (const int rc = fill_async("pcs_range_scan_f32", st, bad, 0, sizeof(int32_t))) return rc;
   ScanArgs a;
   a.points = points; a.n = n; a.c = c; a.off = frame_offsets; a.F = num_frames; a.H = H; a.W = W;
   a.fov_down_abs = fov_down_abs; a.fov_total = fov_total;
@@ -324,7 +306,7 @@ extern "C" int pcs_range_knn_vote(const float *proj_range, const int64_t *proj_a
     set_error("pcs_range_knn_vote: 2 <= num_class <= %d (got %d)", kMaxClass, (int)num_class);
     return PCS_EINVAL;
   }
-  if (!scan_sizes_ok(num_scenes, H, W) || n < 0 || n >= ((int64_t)1 << 31)) {
+  if (!image_sizes_ok(num_scenes, H, W) || n < 0 || n >= ((int64_t)1 << 31)) {
     set_error("pcs_range_knn_vote: bad sizes (0 <= n < 2^31, scenes >= 1, H >= 1, W >= 1, scenes * H * W < 2^31)");
     return PCS_EINVAL;
   }

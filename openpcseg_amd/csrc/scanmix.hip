@@ -17,7 +17,8 @@
 // LDS. In the place pass the two scans of a stretch are grid axis z: no bucket takes rows of both scans, so the halves share the
 // workgroup's bases without sharing a running count (and each half holds one scan's pointers: with both, and the bases in
 // registers, the kernel spilled scalar registers). The bucket loops stay rolled for the same reason.
-// The rotated copies go through affine_row() of scan_affine.h under (cos w, sin w, 1, 1, 1, 0, 0, 0): np.dot(float32 rows,
+// The clamped row range of a frame (frame_rows) and the wave scans are shared: raw_scan.h, pcs_common.h.
+// The rotated copies go through affine_row() of raw_scan.h under (cos w, sin w, 1, 1, 1, 0, 0, 0): np.dot(float32 rows,
 // float64 matrix) stored as float32. The sector test is float32: yaw = -float(atan2(double(y), double(x))), strictly between
 // the float32 edges. The ring column (get_kitti_points_ringID) is a flag per mixed row, rocprim's inclusive scan over the batch
 // and a pass that subtracts the frame's base: the first row of a frame never flags.
@@ -26,7 +27,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "pcs_common.h"
-#include "scan_affine.h"
+#include "raw_scan.h"
 
 using namespace pcs;
 
@@ -109,19 +110,13 @@ __device__ __forceinline__ Buckets row_buckets(const FramePlan &fp, const signed
   return b;
 }
 
-struct Stretch {
-  int64_t lo, hi;
-};
-
 // rows [lo, hi) of workgroup b of G along a frame's rows [flo, fhi): contiguous, ascending in b, whole tiles of kBlock rows
-__device__ __forceinline__ Stretch stretch_of(const int64_t *__restrict__ offsets, int f, int64_t n, int G, int b) {
-  int64_t flo = offsets[f], fhi = offsets[f + 1];
-  flo = flo < 0 ? 0 : flo;
-  fhi = fhi > n ? n : fhi;   // nothing outside the n rows is ever addressed, whatever the offsets say
-  if (fhi < flo) fhi = flo;
+__device__ __forceinline__ FrameRows stretch_of(const int64_t *__restrict__ offsets, int f, int64_t n, int G, int b) {
+  const FrameRows fr = frame_rows(offsets, f, n);
+  const int64_t flo = fr.lo, fhi = fr.hi;
   int64_t per = (fhi - flo + G - 1) / G;
   per = (per + kBlock - 1) / kBlock * kBlock;
-  Stretch s;
+  FrameRows s;
   s.lo = flo + (int64_t)b * per;
   s.hi = s.lo + per;
   if (s.lo > fhi) s.lo = fhi;
@@ -129,6 +124,8 @@ __device__ __forceinline__ Stretch stretch_of(const int64_t *__restrict__ offset
   return s;
 }
 
+// Not raw_scan.h's load_raw_row: a mixed row is always four columns and travels whole, as the float4 it is stored back as, and
+// ROW16 says only that the array is 16-byte aligned.
 template <bool ROW16>
 __device__ __forceinline__ float4 load_row(const float *__restrict__ pts, int64_t i) {
   if (ROW16) return *reinterpret_cast<const float4 *>(pts + i * 4);
@@ -144,19 +141,6 @@ __device__ __forceinline__ void store_row(float *__restrict__ out, int64_t row, 
     float *o = out + row * cout;
     o[0] = x; o[1] = y; o[2] = z; o[3] = w;
   }
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ int wave_inclusive(int v, int lane) {
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
 }
 
 // counts (F, G, kBuckets) int32: every cell is written
@@ -175,7 +159,7 @@ __global__ void __launch_bounds__(kBlock) mix_count_kernel(const float *__restri
   for (int k = 0; k < kBuckets; ++k) c[k] = 0;
   for (int scan = 0; scan < 2; ++scan) {
     const float *pts = scan ? pts2 : pts1;
-    const Stretch s = stretch_of(scan ? off2 : off1, f, scan ? n2 : n1, G, b);
+    const FrameRows s = stretch_of(scan ? off2 : off1, f, scan ? n2 : n1, G, b);
     for (int64_t i = s.lo + threadIdx.x; i < s.hi; i += kBlock) {
       const float4 r = load_row<ROW16>(pts, i);
       const int64_t label = (scan && fp.mode == 1) ? lab2[i] : -1;
@@ -217,7 +201,7 @@ __global__ void __launch_bounds__(kBlock) mix_bases_kernel(int32_t *__restrict__
   }
 }
 
-__device__ __forceinline__ int64_t frame_rows(const int32_t *__restrict__ totals, const double *__restrict__ plan, int f) {
+__device__ __forceinline__ int64_t mixed_rows(const int32_t *__restrict__ totals, const double *__restrict__ plan, int f) {
   int64_t all = 0, inst = 0;
 #pragma unroll
   for (int k = 0; k < kBuckets; ++k) {
@@ -236,12 +220,8 @@ __global__ void __launch_bounds__(kBlock) mix_frame_base_kernel(const int32_t *_
   int64_t carry = 0;
   for (int f0 = 0; f0 < F; f0 += kBlock) {
     const int f = f0 + threadIdx.x;
-    const int64_t v = f < F ? frame_rows(totals, plan, f) : 0;
-    int64_t incl = v;
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int64_t t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
+    const int64_t v = f < F ? mixed_rows(totals, plan, f) : 0;
+    const int64_t incl = wave_inclusive(v, lane);
     if (lane == kWave - 1) wsum[wave] = incl;
     __syncthreads();
     int64_t before = 0, block = 0;
@@ -297,7 +277,7 @@ __global__ void __launch_bounds__(kBlock) mix_place_kernel(const float *__restri
     const int scan = blockIdx.z;
     const float *pts = scan ? pts2 : pts1;
     const int64_t *lab = scan ? lab2 : lab1;
-    const Stretch s = stretch_of(scan ? off2 : off1, f, scan ? n2 : n1, G, b);
+    const FrameRows s = stretch_of(scan ? off2 : off1, f, scan ? n2 : n1, G, b);
     for (int64_t i0 = s.lo; i0 < s.hi; i0 += kBlock) {   // the same trips for the whole workgroup
       const int64_t i = i0 + threadIdx.x;
       const bool valid = i < s.hi;
@@ -359,23 +339,15 @@ __global__ void __launch_bounds__(kBlock) mix_place_kernel(const float *__restri
 __device__ __forceinline__ float ring_proj_x(float x, float y) {
 #pragma clang fp contract(off)
   const float yaw = -(float)atan2((double)y, (double)(-x));
-  const float t = __fdiv_rn(yaw, 3.14159274101257324f) + 1.0f;   // float32(pi)
+  const float t = __fdiv_rn(yaw, kPiF) + 1.0f;
   return 0.5f * t;
-}
-
-// rows of frame f: [frame_base[f], frame_base[f + 1]) clamped to [0, m]
-__device__ __forceinline__ Stretch mixed_frame(const int64_t *__restrict__ frame_base, int f, int64_t m) {
-  Stretch s = {frame_base[f], frame_base[f + 1]};
-  s.lo = s.lo < 0 ? 0 : s.lo;
-  s.hi = s.hi > m ? m : s.hi;
-  return s;
 }
 
 __global__ void __launch_bounds__(kBlock) ring_flag_kernel(const float *__restrict__ pts, int64_t m, int c,
                                                            const int64_t *__restrict__ frame_base, int32_t *__restrict__ flags) {
   const int f = blockIdx.y;
   const int lane = threadIdx.x & (kWave - 1);
-  const Stretch s = mixed_frame(frame_base, f, m);
+  const FrameRows s = frame_rows(frame_base, f, m);   // the mixed rows of frame f
   for (int64_t i0 = s.lo + (int64_t)blockIdx.x * kBlock; i0 < s.hi; i0 += (int64_t)gridDim.x * kBlock) {   // uniform per workgroup
     const int64_t i = i0 + threadIdx.x;
     const bool valid = i < s.hi;
@@ -389,7 +361,7 @@ __global__ void __launch_bounds__(kBlock) ring_flag_kernel(const float *__restri
 __global__ void __launch_bounds__(kBlock) ring_store_kernel(float *__restrict__ pts, int64_t m, int c, const int64_t *__restrict__ frame_base,
                                                             const int32_t *__restrict__ scanned) {
   const int f = blockIdx.y;
-  const Stretch s = mixed_frame(frame_base, f, m);
+  const FrameRows s = frame_rows(frame_base, f, m);   // the mixed rows of frame f
   const int32_t before = s.lo > 0 && s.lo < s.hi ? scanned[s.lo - 1] : 0;
   for (int64_t i = s.lo + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < s.hi; i += (int64_t)gridDim.x * kBlock) {
     int r = scanned[i] - before;
@@ -440,11 +412,8 @@ extern "C" int pcs_scan_mix_count(const float *points1, int64_t n1, const int64_
     set_error("pcs_scan_mix_count: null pointer");
     return PCS_EINVAL;
   }
-  if (ws_bytes < pcs_scan_mix_ws_bytes(n1, n2, num_frames)) {
-    set_error("pcs_scan_mix_count: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-              (long long)pcs_scan_mix_ws_bytes(n1, n2, num_frames));
-    return PCS_EWORKSPACE;
-  }
+  const int64_t need = pcs_scan_mix_ws_bytes(n1, n2, num_frames);
+  if (ws_bytes < need) return ws_too_small("pcs_scan_mix_count", ws_bytes, need);
   hipStream_t st = as_stream(stream);
   int32_t *counts = reinterpret_cast<int32_t *>(ws);
   const int G = mix_grid(n1, n2, num_frames);
@@ -477,11 +446,8 @@ extern "C" int pcs_scan_mix_place(const float *points1, const int64_t *labels1, 
     set_error("pcs_scan_mix_place: null pointer");
     return PCS_EINVAL;
   }
-  if (ws_bytes < pcs_scan_mix_ws_bytes(n1, n2, num_frames)) {
-    set_error("pcs_scan_mix_place: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-              (long long)pcs_scan_mix_ws_bytes(n1, n2, num_frames));
-    return PCS_EWORKSPACE;
-  }
+  const int64_t need = pcs_scan_mix_ws_bytes(n1, n2, num_frames);
+  if (ws_bytes < need) return ws_too_small("pcs_scan_mix_place", ws_bytes, need);
   if (m == 0) return PCS_OK;
   hipStream_t st = as_stream(stream);
   const int32_t *wbase = reinterpret_cast<const int32_t *>(ws);
@@ -517,17 +483,14 @@ extern "C" int pcs_scan_ring_f32(float *points, int64_t m, int32_t c, const int6
   size_t temp = 0;
   if (!ring_temp_bytes(m, &temp)) return PCS_EINVAL;
   const int64_t cells = align256(m * (int64_t)sizeof(int32_t));
-  if (ws_bytes < 2 * cells + align256((int64_t)temp)) {
-    set_error("pcs_scan_ring_f32: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)(2 * cells + align256((int64_t)temp)));
-    return PCS_EWORKSPACE;
-  }
+  const int64_t need = 2 * cells + align256((int64_t)temp);
+  if (ws_bytes < need) return ws_too_small("pcs_scan_ring_f32", ws_bytes, need);
   hipStream_t st = as_stream(stream);
   char *base = reinterpret_cast<char *>(ws);
   int32_t *flags = reinterpret_cast<int32_t *>(base), *scanned = reinterpret_cast<int32_t *>(base + cells);
   const dim3 grid(frame_grid(m, 1, num_frames, 2048), num_frames);
   // rows outside every frame (frame_base not covering [0, m)) would keep garbage flags: clear them first
-  const hipError_t e0 = hipMemsetAsync(flags, 0, (size_t)m * sizeof(int32_t), st);
-  if (e0 != hipSuccess) { set_error("pcs_scan_ring_f32: hipMemsetAsync: %s", hipGetErrorString(e0)); return PCS_ELAUNCH; }
+  if (const int rc = fill_async("pcs_scan_ring_f32", st, flags, 0, (size_t)m * sizeof(int32_t))) return rc;
   hipLaunchKernelGGL(ring_flag_kernel, grid, dim3(kBlock), 0, st, points, m, c, frame_base, flags);
   const hipError_t e = rocprim::inclusive_scan(base + 2 * cells, temp, (const int32_t *)flags, scanned, (size_t)m, rocprim::plus<int32_t>(), st);
   if (e != hipSuccess) { set_error("pcs_scan_ring_f32: rocprim::inclusive_scan: %s", hipGetErrorString(e)); return PCS_ELAUNCH; }

@@ -16,22 +16,18 @@
 // (measured: ~8 ns each -- 24 576 of them, one per wave, vote and axis, took 190 of the kernel's 193 us on twelve full scans).
 // Instead every workgroup reduces its waves through LDS, stores its 3 V partial minima, and takes a ticket of its frame (one
 // atomic add per workgroup); the workgroup that draws the frame's last ticket reduces the partials into `mins`.
+// The row range of a frame, the row load, the parameter rows in LDS, the grid and the vote dispatch are raw_scan.h's.
 #include <math.h>
 
 #include "pcs_common.h"
-#include "scan_affine.h"
+#include "raw_scan.h"
 
 using namespace pcs;
 
 namespace {
 
 constexpr int kBlock = kScanBlock;
-constexpr int kMaxExtra = PCS_SCAN_MAX_COLUMNS - 3;
-
-__device__ __forceinline__ int wave_min(int v) {
-  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-  return v;
-}
+constexpr int kMaxExtra = kScanMaxExtra;
 
 __global__ void __launch_bounds__(kBlock) scan_fill_kernel(int32_t *__restrict__ dst, int count, int32_t value) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) dst[i] = value;
@@ -50,9 +46,8 @@ __global__ void __launch_bounds__(kBlock) scan_transform_kernel(const float *__r
   __shared__ int red[kBlock / kWave][VB * 3];
   __shared__ int is_last;
   const int f = blockIdx.y;
-  int64_t lo = frame_offsets[f], hi = frame_offsets[f + 1];
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > n ? n : hi;   // nothing outside the n rows is ever addressed, whatever the offsets say
+  const FrameRows fr = frame_rows(frame_offsets, f, n);
+  const int64_t lo = fr.lo, hi = fr.hi;
   // the workgroups of this frame that have rows: the others leave at once and take no ticket
   const int64_t want = hi > lo ? (hi - lo + kBlock - 1) / kBlock : 0;
   const int active = want < (int64_t)gridDim.x ? (int)want : (int)gridDim.x;
@@ -62,36 +57,27 @@ __global__ void __launch_bounds__(kBlock) scan_transform_kernel(const float *__r
     return;
   }
   if ((int)blockIdx.x >= active) return;   // the same for the whole workgroup
-  for (int j = threadIdx.x; j < V * 8; j += kBlock) sp[j] = params[((int64_t)(j >> 3) * F + f) * 8 + (j & 7)];
+  stage_params(sp, params, V, F, f);
   __syncthreads();
   int mn[VB][3];
 #pragma unroll
   for (int v = 0; v < VB; ++v) mn[v][0] = mn[v][1] = mn[v][2] = INT32_MAX;
   for (int64_t i = lo + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < hi; i += (int64_t)gridDim.x * kBlock) {
-    float x, y, z, extra[kMaxExtra];
-    if (ROW16) {
-      const float4 r = *reinterpret_cast<const float4 *>(pts + i * 4);
-      x = r.x; y = r.y; z = r.z; extra[0] = r.w;
-    } else {
-      const float *p = pts + i * C;
-      x = p[0]; y = p[1]; z = p[2];
-#pragma unroll
-      for (int k = 0; k < kMaxExtra; ++k) extra[k] = 3 + k < C ? p[3 + k] : 0.f;
-    }
+    const RawRow r = load_raw_row<ROW16>(pts, i, C);
 #pragma unroll
     for (int v = 0; v < VB; ++v) {
       if (v < V) {
         float fx, fy, fz;
-        affine_row(x, y, z, sp + v * 8, fx, fy, fz);
+        affine_row(r.x, r.y, r.z, sp + v * 8, fx, fy, fz);
         const int64_t row = (int64_t)v * n + i;
         if (ROW16) {
-          *reinterpret_cast<float4 *>(feats + row * 4) = make_float4(fx, fy, fz, extra[0]);
+          *reinterpret_cast<float4 *>(feats + row * 4) = make_float4(fx, fy, fz, r.extra[0]);
         } else {
           float *o = feats + row * C;
           o[0] = fx; o[1] = fy; o[2] = fz;
 #pragma unroll
           for (int k = 0; k < kMaxExtra; ++k)
-            if (3 + k < C) o[3 + k] = extra[k];
+            if (3 + k < C) o[3 + k] = r.extra[k];
         }
         const int q[3] = {(int)rintf(__fdiv_rn(fx, voxel)), (int)rintf(__fdiv_rn(fy, voxel)), (int)rintf(__fdiv_rn(fz, voxel))};
 #pragma unroll
@@ -152,9 +138,8 @@ __global__ void __launch_bounds__(kBlock) scan_shift_kernel(int32_t *__restrict_
                                                             const int64_t *__restrict__ frame_offsets, int F,
                                                             const int32_t *__restrict__ mins, int64_t *__restrict__ frames) {
   const int f = blockIdx.y, v = blockIdx.z;
-  int64_t lo = frame_offsets[f], hi = frame_offsets[f + 1];
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > n ? n : hi;
+  const FrameRows rows = frame_rows(frame_offsets, f, n);
+  const int64_t lo = rows.lo, hi = rows.hi;
   const int64_t scene = (int64_t)v * F + f;
   const int32_t m0 = mins[scene * 3 + 0], m1 = mins[scene * 3 + 1], m2 = mins[scene * 3 + 2];
   int32_t *c = coords + (int64_t)v * n * 3;
@@ -167,26 +152,11 @@ __global__ void __launch_bounds__(kBlock) scan_shift_kernel(int32_t *__restrict_
   }
 }
 
-// the transform's: 256 CUs x 4 workgroups of the light instances (<= 4 votes), x 2 of the heavy ones (2 waves per SIMD fit)
-int transform_grid(int64_t n, int num_frames, int num_votes) { return frame_grid(n, 1, num_frames, num_votes <= 4 ? 1024 : 512); }
-
-template <int VB>
-void launch_transform(bool row16, dim3 grid, hipStream_t st, const float *pts, int64_t n, int C, const int64_t *fo, int F,
-                      const double *params, int V, float voxel, float *feats, int32_t *coords, int32_t *mins, int32_t *counters,
-                      int32_t *partials) {
-  if (row16)
-    hipLaunchKernelGGL((scan_transform_kernel<VB, true>), grid, dim3(kBlock), 0, st, pts, n, C, fo, F, params, V, voxel, feats, coords,
-                       mins, counters, partials);
-  else
-    hipLaunchKernelGGL((scan_transform_kernel<VB, false>), grid, dim3(kBlock), 0, st, pts, n, C, fo, F, params, V, voxel, feats, coords,
-                       mins, counters, partials);
-}
-
 }  // namespace
 
 extern "C" int64_t pcs_scan_transform_ws_bytes(int64_t n, int32_t num_frames, int32_t num_votes) {
   if (!scan_sizes_ok(n, num_frames, num_votes)) { set_error("pcs_scan_transform_ws_bytes: bad sizes"); return PCS_EINVAL; }
-  const int64_t g = transform_grid(n, num_frames, num_votes);
+  const int64_t g = vote_grid(n, num_frames, num_votes);
   return (int64_t)sizeof(int32_t) * num_frames * (1 + g * num_votes * 3);   // tickets, then the partial minima
 }
 
@@ -202,23 +172,17 @@ extern "C" int pcs_scan_transform(const float *points, int64_t n, int32_t c, con
     set_error("pcs_scan_transform: null pointer");
     return PCS_EINVAL;
   }
-  if (ws_bytes < pcs_scan_transform_ws_bytes(n, num_frames, num_votes)) {
-    set_error("pcs_scan_transform: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-              (long long)pcs_scan_transform_ws_bytes(n, num_frames, num_votes));
-    return PCS_EWORKSPACE;
-  }
+  const int64_t need = pcs_scan_transform_ws_bytes(n, num_frames, num_votes);
+  if (ws_bytes < need) return ws_too_small("pcs_scan_transform", ws_bytes, need);
   hipStream_t st = as_stream(stream);
   int32_t *counters = reinterpret_cast<int32_t *>(ws), *partials = counters + num_frames;
   hipLaunchKernelGGL(scan_fill_kernel, dim3(stream_grid(num_frames, kBlock)), dim3(kBlock), 0, st, counters, num_frames, 0);
   const bool row16 = c == 4 && (((uintptr_t)points | (uintptr_t)feats) & 15) == 0;
-  const dim3 grid(transform_grid(n, num_frames, num_votes), num_frames);   // n == 0: one workgroup per frame writes INT32_MAX
-#define PCS_SCAN_LAUNCH(VB) \
-  launch_transform<VB>(row16, grid, st, points, n, c, frame_offsets, num_frames, params, num_votes, voxel_size, feats, coords, mins, counters, partials)
-  if (num_votes == 1) PCS_SCAN_LAUNCH(1);
-  else if (num_votes <= 4) PCS_SCAN_LAUNCH(4);
-  else if (num_votes <= 10) PCS_SCAN_LAUNCH(10);
-  else PCS_SCAN_LAUNCH(PCS_SCAN_MAX_VOTES);
-#undef PCS_SCAN_LAUNCH
+  const dim3 grid(vote_grid(n, num_frames, num_votes), num_frames);   // n == 0: one workgroup per frame writes INT32_MAX
+  dispatch_votes(num_votes, row16, [&](auto vb, auto r16) {
+    hipLaunchKernelGGL((scan_transform_kernel<decltype(vb)::value, decltype(r16)::value>), grid, dim3(kBlock), 0, st, points, n, c,
+                       frame_offsets, num_frames, params, num_votes, voxel_size, feats, coords, mins, counters, partials);
+  });
   return check_launch("pcs_scan_transform");
 }
 

@@ -215,6 +215,30 @@ def _check(rc, what):
         raise RuntimeError("openpcseg_amd: %s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
 
 
+def _ws_bytes(query_name, *args):
+    """The answer of a workspace-size query of the library; a negative one raises with the library's message."""
+    ws_bytes = getattr(load_library(), query_name)(*args)
+    if ws_bytes < 0:
+        _check(-1, query_name)
+    return int(ws_bytes)
+
+
+def _cyl_space(lo, hi, grid):
+    """The cylinder space as the three host arrays the entries take: (min3, max3) float64, grid3 int32."""
+    return ((c_double * 3)(*[float(v) for v in lo]), (c_double * 3)(*[float(v) for v in hi]),
+            (c_int32 * 3)(*[int(v) for v in grid]))
+
+
+def _hist_arg(hist, num_class, labels):
+    """The one check of a confusion matrix that a launch updates in place."""
+    if hist is not None:
+        if hist.dtype != torch.int64 or not hist.is_cuda or not hist.is_contiguous() or tuple(hist.shape) != (num_class, num_class):
+            raise ValueError("openpcseg_amd: hist must be a contiguous (%d, %d) int64 device tensor (updated in place)"
+                             % (num_class, num_class))
+        if labels is None:
+            raise ValueError("openpcseg_amd: hist needs labels")
+
+
 def _dev(t, name, dtype=None):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError("openpcseg_amd: `%s` must be a HIP device tensor (got %s); the MI355X "
@@ -1421,10 +1445,7 @@ class HipBackend:
         feats = torch.empty((v * n, c), dtype=torch.float32, device=dev)
         coords = torch.empty((v * n, 3), dtype=torch.int32, device=dev)
         mins = torch.empty((v * nf, 3), dtype=torch.int32, device=dev)
-        ws_bytes = self.lib.pcs_scan_transform_ws_bytes(n, nf, v)
-        if ws_bytes < 0:
-            _check(-1, "pcs_scan_transform_ws_bytes")
-        ws = torch.empty(max(int(ws_bytes), 4), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(_ws_bytes("pcs_scan_transform_ws_bytes", n, nf, v), 4), dtype=torch.uint8, device=dev)
         _check(self.lib.pcs_scan_transform(_ptr(points), n, c, _ptr(off), nf, _ptr(par), v, float(voxel_size), _ptr(feats), _ptr(coords),
                                            _ptr(mins), _ptr(ws), ws.numel(), _stream()), "pcs_scan_transform")
         return feats, coords, mins, off
@@ -1465,9 +1486,7 @@ class HipBackend:
         """points (n, >=3) float32 -> (polar (n,3) f32 | None, coord (n,3) int32, feat (n, 8 + extras) f32 | None)."""
         points = _dev(points, "points", torch.float32)
         n, stride = points.shape
-        lo = (c_double * 3)(*[float(v) for v in space_min])
-        hi = (c_double * 3)(*[float(v) for v in space_max])
-        grid = (c_int32 * 3)(*[int(v) for v in grid_size])
+        lo, hi, grid = _cyl_space(space_min, space_max, grid_size)
         dev = points.device
         polar = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_polar else None
         coord = torch.empty((n, 3), dtype=torch.int32, device=dev)
@@ -1483,9 +1502,7 @@ class HipBackend:
         after frame; offsets, params, votes as scan_transform -> (feat (votes * n, 8 + C - 3) fp32, coord (votes * n, 3) int32,
         scenes (votes * n,) int64 = vote * num_frames + frame). Nothing is read back."""
         points, n, c, nf, v, par, off = self._scan_args("cylinder_scan_batch", points, offsets, params, votes)
-        lo = (c_double * 3)(*[float(x) for x in space_min])
-        hi = (c_double * 3)(*[float(x) for x in space_max])
-        grid = (c_int32 * 3)(*[int(x) for x in grid_size])
+        lo, hi, grid = _cyl_space(space_min, space_max, grid_size)
         dev = points.device
         feat = torch.empty((v * n, 8 + c - 3), dtype=torch.float32, device=dev)
         coord = torch.empty((v * n, 3), dtype=torch.int32, device=dev)
@@ -1512,9 +1529,7 @@ class HipBackend:
         if scenes.numel() != n or cuts32.shape[0] != s:
             raise ValueError("openpcseg_amd: range_project wants one scene per row and one cut per scene (%d rows, %d scene entries, "
                              "%d scenes, %d cuts)" % (n, scenes.numel(), s, cuts32.shape[0]))
-        ws_bytes = self.lib.pcs_range_project_ws_bytes(s, h, w)
-        if ws_bytes < 0:
-            _check(-1, "pcs_range_project_ws_bytes")
+        ws_bytes = _ws_bytes("pcs_range_project_ws_bytes", s, h, w)
         dev = feats.device
         cuts_dev = _h2d(cuts32.tolist(), torch.float32, dev)   # float32 -> Python float -> float32 is exact
         winner = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
@@ -1540,9 +1555,7 @@ class HipBackend:
             labels = _dev(labels, "labels", torch.int64)
         n, c = points.shape
         nf, (h, w) = len(offsets) - 1, (int(v) for v in hw)
-        ws_bytes = self.lib.pcs_range_scan_ws_bytes(nf, h, w)
-        if ws_bytes < 0:
-            _check(-1, "pcs_range_scan_ws_bytes")
+        ws_bytes = _ws_bytes("pcs_range_scan_ws_bytes", nf, h, w)
         dev = points.device
         lut = [] if label_lut is None else [int(v) for v in label_lut]
         table = _h2d([int(o) for o in offsets] + lut, torch.int64, dev)
@@ -1589,12 +1602,7 @@ class HipBackend:
             labels = _dev(labels, "labels", torch.int64).reshape(-1)
             if labels.numel() != n:
                 raise ValueError("openpcseg_amd: %d labels for %d points" % (labels.numel(), n))
-        if hist is not None:
-            if hist.dtype != torch.int64 or not hist.is_cuda or not hist.is_contiguous() or tuple(hist.shape) != (num_class, num_class):
-                raise ValueError("openpcseg_amd: hist must be a contiguous (%d, %d) int64 device tensor (updated in place)"
-                                 % (num_class, num_class))
-            if labels is None:
-                raise ValueError("openpcseg_amd: hist needs labels")
+        _hist_arg(hist, num_class, labels)
         off_d = _h2d(off, torch.int64, dev)
         pred = torch.empty(n, dtype=torch.int64, device=dev)
         _check(self.lib.pcs_range_knn_vote(_ptr(proj_range), _ptr(proj_argmax), b, h, w, _ptr(unproj_range), _ptr(proj_x), _ptr(proj_y), n,
@@ -1627,10 +1635,7 @@ class HipBackend:
         a = nf * 16
         plan_d, omega_d, cls_d = table[:a].view(torch.float64), table[a:a + 16].view(torch.float64), table[a + 16:a + 24]
         off1_d, off2_d = table[a + 24:a + 25 + nf], table[a + 25 + nf:]
-        ws_bytes = self.lib.pcs_scan_mix_ws_bytes(n1, n2, nf)
-        if ws_bytes < 0:
-            _check(-1, "pcs_scan_mix_ws_bytes")
-        ws = torch.empty(max(int(ws_bytes), 4), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(_ws_bytes("pcs_scan_mix_ws_bytes", n1, n2, nf), 4), dtype=torch.uint8, device=dev)
         totals = torch.empty((nf, 10), dtype=torch.int32, device=dev)
         frame_base = torch.empty(nf + 1, dtype=torch.int64, device=dev)
         _check(self.lib.pcs_scan_mix_count(_ptr(points1), n1, _ptr(off1_d), _ptr(points2), _ptr(labels2), n2, _ptr(off2_d), nf, _ptr(plan_d),
@@ -1646,10 +1651,7 @@ class HipBackend:
                                            _ptr(plan_d), _ptr(cls_d), len(classes), _ptr(omega_d), _ptr(ws), ws.numel(), _ptr(totals),
                                            _ptr(frame_base), m, c_out, _ptr(out), _ptr(out_labels), _stream()), "pcs_scan_mix_place")
         if ring and m:
-            ring_bytes = self.lib.pcs_scan_ring_ws_bytes(m)
-            if ring_bytes < 0:
-                _check(-1, "pcs_scan_ring_ws_bytes")
-            ring_ws = torch.empty(max(int(ring_bytes), 4), dtype=torch.uint8, device=dev)
+            ring_ws = torch.empty(max(_ws_bytes("pcs_scan_ring_ws_bytes", m), 4), dtype=torch.uint8, device=dev)
             _check(self.lib.pcs_scan_ring_f32(_ptr(out), m, c_out, _ptr(frame_base), nf, _ptr(ring_ws), ring_ws.numel(), _stream()),
                    "pcs_scan_ring_f32")
         return out, out_labels, offsets
@@ -1707,11 +1709,7 @@ class HipBackend:
         if votes is not None:
             if votes.dtype != torch.float32 or not votes.is_cuda or not votes.is_contiguous() or tuple(votes.shape) != (n, c):
                 raise ValueError("openpcseg_amd: votes must be a contiguous (%d, %d) float32 device tensor (updated in place)" % (n, c))
-        if hist is not None:
-            if hist.dtype != torch.int64 or not hist.is_cuda or not hist.is_contiguous() or tuple(hist.shape) != (c, c):
-                raise ValueError("openpcseg_amd: hist must be a contiguous (%d, %d) int64 device tensor (updated in place)" % (c, c))
-            if labels is None:
-                raise ValueError("openpcseg_amd: hist needs labels")
+        _hist_arg(hist, c, labels)
         if bad is None:
             bad = torch.zeros(1, dtype=torch.int32, device=dev)
         pred = torch.empty(n, dtype=torch.int64, device=dev) if want_pred else None
@@ -1729,10 +1727,8 @@ class HipBackend:
         if labels.numel() != n:
             raise ValueError("openpcseg_amd: %d labels for %d probability rows" % (labels.numel(), n))
         has_ignore, ign = (0, 0) if ignore is None else (1, int(ignore))
-        ws_bytes = self.lib.pcs_lovasz_workspace_bytes(n, nc, has_ignore, ign)
-        if ws_bytes < 0:
-            _check(-1, "pcs_lovasz_workspace_bytes")
-        ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=probas.device)
+        ws_bytes = _ws_bytes("pcs_lovasz_workspace_bytes", n, nc, has_ignore, ign)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=probas.device)
         loss = torch.empty((), dtype=torch.float32, device=probas.device)
         grad = torch.empty_like(probas) if need_grad else None
         _check(self.lib.pcs_lovasz_softmax_f32(_ptr(probas), _ptr(labels), n, nc, has_ignore, ign, _ptr(loss),

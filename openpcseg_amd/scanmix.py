@@ -146,7 +146,7 @@ def sector_mask(points, alpha, atan="numpy32"):
 
 
 def omega_params(omega):
-    """The parameter rows under which transform_scan_host / affine_row of csrc/scan_affine.h IS rotate_copy's np.dot(float32
+    """The parameter rows under which transform_scan_host / affine_row of csrc/raw_scan.h IS rotate_copy's np.dot(float32
     rows, float64 matrix) stored as float32: (cos w, sin w, 1, 1, 1, 0, 0, 0) per angle."""
     out = transform.identity_params(2)
     for j, w in enumerate(_check_omega(omega)):

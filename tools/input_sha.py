@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""The device input builders and the voted evaluations (DESIGN.md 7h to 7k) on two small unequal frames: per case one line with the
+"""The device input builders and the voted evaluations (DESIGN.md 7h to 7m) on two small unequal frames: per case one line with the
 SHA-256 of every tensor or host array of the returned dict, in sorted key order (a SparseTensor as F then C, a list entry by entry).
 Two trees that compute the same bits print the same file.
 
   python tools/input_sha.py > new.txt
 
-The frames are make_scan(1, 200) and make_scan(2, 137); the cases are transform / cylinder / rangeview `device_batch`, `device_mix`
-and the three `predict_tta` on seeded small models with 3 votes in chunks of 1 and None. Uses public names only (`device_batch`,
-`device_mix`, `tta_params`, `predict_tta`, SegEvaluator), so it runs on any tree that has them."""
+The frames are make_scan(1, 200) and make_scan(2, 137); the cases are transform / cylinder / rangeview `device_batch`, `device_mix`,
+the range-view scan (`rangescan.device_batch` with and without a label table, both masks), its `knn_vote` for every search window
+and one `native.predict_points` with scenes, votes and a confusion matrix, and the three `predict_tta` on seeded small models with
+3 votes in chunks of 1 and None. Uses public names only (`device_batch`, `device_mix`, `tta_params`, `knn_vote`, `predict_points`,
+`predict_tta`, SegEvaluator), so it runs on any tree that has them."""
 import hashlib
 import os
 import sys
@@ -58,7 +60,7 @@ def make_raw(dev, shift=0, ring=False):
 
 
 def main():
-    from openpcseg_amd import cylinder, rangeview, scanmix, transform
+    from openpcseg_amd import cylinder, native, rangescan, rangeview, scanmix, transform
     from openpcseg_amd.inference import SegEvaluator, predict_tta
     from openpcseg_amd.workloads import minkunet as mk
     from openpcseg_amd.workloads.cylinder import CylinderTS
@@ -83,6 +85,29 @@ def main():
     for lasermix in ("reference", "radians"):
         line("scanmix.device_mix ring lasermix=%s" % lasermix,
              scanmix.device_mix(raw, make_raw(dev, shift=1000), plan, OMEGA, ring=True, lasermix=lasermix))
+    # the range-view scan, its KNN vote and the prediction tail: seeded inputs, every confusion matrix counted in the launch
+    lut = [(7 * i + 3) % C for i in range(C)]
+    for table in (None, lut):
+        for mask in ("reference", "hit"):
+            view = rangescan.device_batch(raw, hw=HW, label_lut=table, mask=mask)
+            line("rangescan.device_batch lut=%d mask=%s" % (table is not None, mask), view)
+    gen = torch.Generator().manual_seed(11)
+    argmax = torch.randint(0, C, tuple(view["scan_rv"][:, 4].shape), generator=gen).to(dev)
+    for search in (3, 5, 7):
+        hist = torch.zeros((C, C), dtype=torch.int64, device=dev)
+        pred = rangescan.knn_vote(view["scan_rv"][:, 4] * 80, argmax, view["unproj_range"], view["proj_x"], view["proj_y"],
+                                  view["point_offset"], knn=5, search=search, num_class=C, labels=raw["labels"], hist=hist)
+        line("rangescan.knn_vote search=%d hist" % search, {"pred": pred, "hist": hist})
+    rows = (50, 40)   # voxel rows of the two scenes
+    logits = torch.randn((sum(rows), C), generator=gen).to(dev)
+    inverse = torch.cat([torch.randint(0, r, (n,), generator=gen) for r, (_, n) in zip(rows, SIZES)]).to(dev)
+    hist = torch.zeros((C, C), dtype=torch.int64, device=dev)
+    votes = torch.zeros((inverse.numel(), C), dtype=torch.float32, device=dev)
+    for _ in range(2):   # two passes summed into the votes
+        pred, bad = native.predict_points(logits, inverse=inverse, point_offset=torch.tensor(raw["offsets"], device=dev),
+                                          row_offset=torch.tensor([0, rows[0], sum(rows)], device=dev), labels=raw["labels"],
+                                          votes=votes, hist=hist)
+    line("native.predict_points scenes votes hist", {"pred": pred, "bad": bad, "votes": votes, "hist": hist})
 
     def seeded(model):
         model = model.eval()
