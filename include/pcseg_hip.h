@@ -938,6 +938,47 @@ int64_t pcs_lovasz_workspace_bytes(int64_t n, int32_t num_class, int32_t has_ign
 int pcs_lovasz_softmax_f32(const float *probas, const int64_t *labels, int64_t n, int32_t num_class, int32_t has_ignore,
                            int64_t ignore, float *loss, float *grad, void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- the range-view training criterion (csrc/rangeloss.hip; added under ABI v12, additive) ------------
+ * What the reference's range segmentors run on their logits every training step
+ * (R:pcseg/model/segmentor/range/fidnet/model/semantic/fidnet.py:62-84, salsanext.py:250-271, cenet.py:248-318):
+ *   loss = w_ce * mean_pixels(CE + Dice) + w_ls * Lovasz_softmax(ignore) + w_bd * BoundaryLoss(theta0 = 3)
+ * with CrossEntropyLoss(reduction='none', weight) / CrossEntropyDiceLoss, DiceLoss._dice_loss_multichannel, BoundaryLoss and
+ * one_hot of R:pcseg/model/segmentor/range/utils.py:520-724, value and gradient by the logits.
+ *   logits (B, C, H, W) contiguous NCHW, dtype 0 fp32 / 1 bf16 / 2 fp16 (upcast exactly; fp32 arithmetic, double folds);
+ *   labels (B, H, W) int64; class_weight (C) fp32 or NULL (= 1): the weight of CrossEntropyLoss; 2 <= C <= 32, B, H, W >= 1,
+ *   B * C * H * W < 2^32 - 1. flags: PCS_RANGE_LOSS_DICE (the Dice term is on) | PCS_RANGE_LOSS_BOUNDARY (the boundary term is on).
+ *   A label outside [0, C) is handled like ignore_index (the reference raises): CE term 0 but counted in the mean's divisor, no
+ *   one-hot row, left out of Dice's denominator. This is the one extension.
+ * pcs_range_loss_stats (utils.py:552, :594-608, :689-702; fidnet.py:63, :74, :80): softmax and log-softmax once per pixel; into ws the
+ *   CE sum, per class sum p onehot and sum (p + onehot) of Dice, per (image, class) sum pred_b gt_b, sum pred_b, sum gt_b with
+ *   pred_b = p - min3x3(p), gt_b = onehot - min3x3(onehot), the window clipped at the image border (max_pool2d(1 - x, 3, 1, 1) -
+ *   (1 - x): the padding is minus infinity). probas (B H W, C) fp32 or NULL: the softmax as flatten_probas (utils.py:489-506) lays
+ *   it out, the input of pcs_lovasz_softmax_f32. Per-workgroup partials, then a fixed-order sum in double: no float atomics.
+ * pcs_range_loss_fold (utils.py:604-624, :705-712; fidnet.py:67, :84): on the device, no host read. lovasz: 1 DEVICE float (the
+ *   loss of pcs_lovasz_softmax_f32) or NULL (term off). terms (5) DEVICE floats <- total, ce, dice, ls, bd with total = w_ce (ce +
+ *   dice) + w_ls ls + w_bd bd; into ws the coefficients of the gradient pass: per class, with den = D + 1e-4, dDice / dp(x) =
+ *   -(1 / C)(2 onehot / den - 2 I / den^2); per (image, class), with P = I / (S + 1e-7), R = I / (G + 1e-7), BF1 = 2 P R / (P + R +
+ *   1e-7), d bd / d pred_b(x) = a gt_b(x) + b. Dice is 0 with zero coefficients when every D is zero (utils.py:609-611).
+ * pcs_range_loss_grad (the autograd mirror of all of the above): grad (B, C, H, W) in the logits' dtype, every element written,
+ *   d logit_c = p_c (g_c - sum_k p_k g_k) + w_ce class_weight[label] (p_c - onehot_c) / (B H W), one rounding, g_c = w_ls
+ *   lovasz_grad[pixel][c] + dice_c + bd_c; lovasz_grad (B H W, C) fp32 = the grad of pcs_lovasz_softmax_f32 or NULL. The boundary
+ *   term is gathered: bd_c(q) = coef(q) - the coef(r) of every centre r around q whose window has its minimum at q. Among equal
+ *   minima the FIRST in row-major order of the clipped window takes the gradient (torch's max_pool2d backward): part of the contract.
+ *   flags, class_weight and w_ce as given to the two earlier calls on the same ws.
+ * ws: pcs_range_loss_ws_bytes(B, C, H, W) bytes (-1 + pcs_last_error on sizes the entries refuse), contents irrelevant on entry.
+ * Sizes are checked before any pointer: bad sizes give PCS_EINVAL also with null pointers. Nothing allocates, nothing is read back;
+ * the results are a pure function of the inputs, bit for bit. */
+#define PCS_RANGE_LOSS_DICE 1
+#define PCS_RANGE_LOSS_BOUNDARY 2
+int64_t pcs_range_loss_ws_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int pcs_range_loss_stats(const void *logits, int32_t dtype, const int64_t *labels, const float *class_weight, int32_t B, int32_t C,
+                         int32_t H, int32_t W, int32_t flags, float *probas, void *ws, int64_t ws_bytes, void *stream);
+int pcs_range_loss_fold(int32_t B, int32_t C, int32_t H, int32_t W, int32_t flags, const float *lovasz, float w_ce, float w_ls,
+                        float w_bd, float *terms, void *ws, int64_t ws_bytes, void *stream);
+int pcs_range_loss_grad(const void *logits, int32_t dtype, const int64_t *labels, const float *class_weight, const float *lovasz_grad,
+                        int32_t B, int32_t C, int32_t H, int32_t W, int32_t flags, float w_ce, float w_ls, const void *ws,
+                        int64_t ws_bytes, void *grad, void *stream);
+
 /* ---- measurement switches (NOT part of the drop-in contract: no reference function stands behind them; results never depend on
  * them; used by tools/convh_ws_ab.py and tools/wgrad_interleave_ab.py to A/B two kernel policies inside one process) -------------
  * pcs_debug_convh_ws: mode -1 = environment (PCS_CONVH_WS, default on), 0 = the 16-bit convolution on conv_os5h only, 1 = the

@@ -155,6 +155,11 @@ SIGNATURES = {
     "pcs_step_apply": (c_int32, [_P, c_int32, c_int64, _P, _P, c_int32, _P]),
     "pcs_lovasz_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int64]),
     "pcs_lovasz_softmax_f32": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int64, _P, _P, _P, c_int64, _P]),
+    "pcs_range_loss_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "pcs_range_loss_stats": (c_int32, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int64, _P]),
+    "pcs_range_loss_fold": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, c_float, c_float, _P, _P, c_int64, _P]),
+    "pcs_range_loss_grad": (c_int32, [_P, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _P,
+                                      c_int64, _P, _P]),
     "pcs_debug_convh_ws": (None, [c_int32, c_int32, c_int32]),       # measurement switches (A/B tools), not part of the contract
     "pcs_debug_wgrad_interleave": (None, [c_int32]),
     "pcs_debug_conv_plan": (None, [c_int32] * 7 + [_P]),             # host only: the route's plan for a call (tests read it)
@@ -181,7 +186,7 @@ class _StepHyper(ctypes.Structure):   # pcs_step_hyper of include/pcseg_hip.h
                 ("nesterov", c_int32 * STEP_MAX_GROUPS), ("n_groups", c_int32)]
 
 
-ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_step_plan / pcs_step_norm / pcs_step_apply, pcs_scan_mix_* / pcs_scan_ring_*, pcs_range_project_* / pcs_range_image_fill_f32, pcs_range_scan_* / pcs_range_knn_vote, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
+ABI_VERSION = 12  # include/pcseg_hip.h PCS_ABI_VERSION (12, additive since: pcs_range_loss_*, pcs_step_plan / pcs_step_norm / pcs_step_apply, pcs_scan_mix_* / pcs_scan_ring_*, pcs_range_project_* / pcs_range_image_fill_f32, pcs_range_scan_* / pcs_range_knn_vote, pcs_conv_epilogue.flags / PCS_EP_RELU in place of the reserved word, pcs_predict_points_f32; 12: pcs_conv_epilogue without the BatchNorm backward-statistics fields, and their partials reduction removed; 11: pcs_sort_unique_i64, pcs_index_csr_i32; 10: pcs_conv_gather_gemm_*_ex + pcs_conv_epilogue, BatchNorm backward partials reduction; 9: pcs_quantize_frame_keys; 8: sums2 size argument of pcs_bn_bwd_stats_*, ring switch removed; 7: pcs_lovasz_*; 6: ring kernel switch / query; 5: fp32 convolution on the bf16 MFMAs, pcs_conv_*_x3; 4: tile order)
 _lib = None
 
 
@@ -1735,6 +1740,65 @@ class HipBackend:
                                                _ptr(grad), _ptr(ws), int(ws_bytes), _stream()),
                "pcs_lovasz_softmax_f32")
         return loss, grad
+
+    _RANGE_LOSS_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+    RANGE_LOSS_DICE, RANGE_LOSS_BOUNDARY = 1, 2   # PCS_RANGE_LOSS_DICE, PCS_RANGE_LOSS_BOUNDARY
+
+    def _range_loss_args(self, logits, labels, class_weight):
+        if not isinstance(logits, torch.Tensor) or logits.dtype not in self._RANGE_LOSS_DTYPES:
+            raise TypeError("openpcseg_amd: range-loss logits must be float32, bfloat16 or float16, got %s"
+                            % getattr(logits, "dtype", type(logits)))
+        logits = _dev(logits, "logits")
+        labels = _dev(labels, "labels", torch.int64)
+        if logits.dim() != 4 or tuple(labels.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
+            raise ValueError("openpcseg_amd: range loss wants (B, C, H, W) logits and (B, H, W) labels, got %s and %s"
+                             % (tuple(logits.shape), tuple(labels.shape)))
+        if class_weight is not None:
+            class_weight = _dev(class_weight, "class_weight", torch.float32)
+            if tuple(class_weight.shape) != (logits.shape[1],):
+                raise ValueError("openpcseg_amd: class_weight must hold one float per class (%d), got %s"
+                                 % (logits.shape[1], tuple(class_weight.shape)))
+        return logits, labels, class_weight
+
+    def range_loss_stats(self, logits, labels, class_weight=None, flags=3, want_probas=True):
+        """Statistics pass of the range-view criterion (csrc/rangeloss.hip) -> (ws, probas (B H W, C) float32 or None).
+        ws holds the per-image sums; range_loss_fold and range_loss_grad take it."""
+        logits, labels, class_weight = self._range_loss_args(logits, labels, class_weight)
+        b, c, h, w = logits.shape
+        ws_bytes = _ws_bytes("pcs_range_loss_ws_bytes", b, c, h, w)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=logits.device)
+        probas = torch.empty((b * h * w, c), dtype=torch.float32, device=logits.device) if want_probas else None
+        _check(self.lib.pcs_range_loss_stats(_ptr(logits), self._RANGE_LOSS_DTYPES[logits.dtype], _ptr(labels), _ptr(class_weight),
+                                             b, c, h, w, int(flags), _ptr(probas), _ptr(ws), ws_bytes, _stream()),
+               "pcs_range_loss_stats")
+        return ws, probas
+
+    def range_loss_fold(self, ws, shape, flags, lovasz, weights):
+        """Fold of the range-view criterion on the device -> terms (5) float32: total, ce, dice, ls, bd; the gradient pass's
+        coefficients go into ws. lovasz: the 0-dim device loss of lovasz_softmax, or None."""
+        b, c, h, w = (int(v) for v in shape)
+        ws = _dev(ws, "ws", torch.uint8)
+        if lovasz is not None:
+            lovasz = _dev(lovasz, "lovasz", torch.float32)
+        terms = torch.empty(5, dtype=torch.float32, device=ws.device)
+        _check(self.lib.pcs_range_loss_fold(b, c, h, w, int(flags), _ptr(lovasz), float(weights[0]), float(weights[1]),
+                                            float(weights[2]), _ptr(terms), _ptr(ws), ws.numel(), _stream()), "pcs_range_loss_fold")
+        return terms
+
+    def range_loss_grad(self, logits, labels, ws, class_weight=None, lovasz_grad=None, flags=3, weights=(1.0, 3.0, 1.0)):
+        """Gradient pass of the range-view criterion -> d loss / d logits, (B, C, H, W) in the logits' dtype."""
+        logits, labels, class_weight = self._range_loss_args(logits, labels, class_weight)
+        b, c, h, w = logits.shape
+        ws = _dev(ws, "ws", torch.uint8)
+        if lovasz_grad is not None:
+            lovasz_grad = _dev(lovasz_grad, "lovasz_grad", torch.float32)
+            if tuple(lovasz_grad.shape) != (b * h * w, c):
+                raise ValueError("openpcseg_amd: lovasz_grad must be (%d, %d), got %s" % (b * h * w, c, tuple(lovasz_grad.shape)))
+        grad = torch.empty_like(logits)
+        _check(self.lib.pcs_range_loss_grad(_ptr(logits), self._RANGE_LOSS_DTYPES[logits.dtype], _ptr(labels), _ptr(class_weight),
+                                            _ptr(lovasz_grad), b, c, h, w, int(flags), float(weights[0]), float(weights[1]),
+                                            _ptr(ws), ws.numel(), _ptr(grad), _stream()), "pcs_range_loss_grad")
+        return grad
 
 
 _BACKEND = None

@@ -39,14 +39,15 @@ def lovasz_softmax_per_class(probas, labels, ignore=None):
     return torch.stack(losses).mean()
 
 
-def lovasz_softmax(probas, labels, ignore=None):
+def lovasz_softmax(probas, labels, ignore=None, stable=False):
     """The same function with the present classes as the rows of (C', n) tensors: one sort, one gather and a dozen
     elementwise kernels for all classes instead of ~25 small launches per class (19 classes x 1.4 M points: the
     per-class loop spent ~5 ms of a 70 ms bf16 step in launch-bound kernels). The Lovasz gradient depends on the
     labels only, so it is built outside autograd; (1 - fg).cumsum is position - fg.cumsum (integers, exact in fp32).
     Ignored points are not compacted away (a nonzero + gather forward, an index_put backward over (n, C)): their error
     is set to zero, which sorts them behind every point that matters -- each term they could touch is multiplied by
-    a zero error, so the value and the gradient are the compacted ones."""
+    a zero error, so the value and the gradient are the compacted ones. stable=True: equal errors keep point order (the HIP kernel's
+    order); the value does not depend on it, the gradient among tied points does."""
     if probas.numel() == 0:
         return probas.sum() * 0.0
     n, nc = probas.shape
@@ -72,7 +73,7 @@ def lovasz_softmax(probas, labels, ignore=None):
     err = (fg - pt).abs()
     if valid is not None:
         err = err * valid.to(probas.dtype).unsqueeze(0)
-    err_sorted, perm = torch.sort(err, dim=1, descending=True)
+    err_sorted, perm = torch.sort(err, dim=1, descending=True, stable=stable)
     with torch.no_grad():
         fg_sorted = torch.gather(fg, 1, perm)
         gts = fg_sorted.sum(1, keepdim=True)
